@@ -2,6 +2,10 @@
 """bench.py -- GRAPE iterations/s (forward chain + first-order backward + regularisers + Adam) on N MI355X.
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line from rank 0.
+  * a plain run only sets up, warms up, times the K steps and prints the line (`metric`, `value`, `ms_per_step`, ...).  `--full`
+    adds everything else below: the roofline pass, the one-trajectory latency, the BASELINE config 3 / 5 entries (`secondary`),
+    the live PMC passes and the CPU baselines.  `--dump-outputs DIR` writes what the timed path returned after its last step
+    (per-seed fidelities and scalars, controls, final unitaries) as DIR/<name>.npy, float64, before any of the `--full` extras run.
   * workload (BASELINE.json configs[1] / SURVEY.md 8d "C2"): n=32, k=4, time slices=500, m=8, (T,s)=(5,3), fp64
     complex, synthetic Hamiltonians from numpy.random.default_rng(0); SEEDS_PER_GPU independent random-restart control
     sets per GPU (config 4: 512 seeds / 8 GPUs = 64 per GPU) -> weak scaling, no data-path collective; the final
@@ -89,6 +93,20 @@ def cpu_model():
     return 'unknown'
 
 
+def usable_cpus():
+    """CPUs this run may use: the affinity mask, capped by OMP_NUM_THREADS when the host sets it (a shared host may show far more
+    CPUs than a job is given)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 4
+    try:
+        n = min(n, int(os.environ.get('OMP_NUM_THREADS', '')))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baseline(budget_s=15.0):
     """CPU oracle timed on a bounded sample of the same workload: whole iterations (evaluate + Adam) of one seed per
     thread, all host threads busy (seeds are the parallel axis on the CPU too).  Compiled C port (oracle/qoc_oracle.c)
@@ -173,7 +191,7 @@ def cpu_baseline_reference_ops(max_evals=6, budget_s=10.0):
                                      '%.1f s; 2 evaluations per reference iteration; torch-CPU emulation of the TF graph' % (evals, el)}
     try:                                                            # all cores: one control set per process of 4 threads
         per = 4
-        procs = max(1, min(64, (os.cpu_count() or 4) // per))
+        procs = max(1, min(64, usable_cpus() // per))
         w_evals = 2                                                 # 64 processes x 4 threads share the memory system: ~5 s per evaluation each
         t0 = time.perf_counter()
         kids = [subprocess.Popen([sys.executable, os.path.abspath(__file__), '--reference-ops-worker', '%d,%d,%d' % (i, w_evals, per)],
@@ -447,6 +465,22 @@ class _GlooTransport(object):
         self.dist.destroy_process_group()
 
 
+def dump_outputs(directory, engs, fidelity):
+    """What a caller of the timed path receives after its last step, one float64 .npy per array (about 3 MB at the default
+    64 seeds): the gathered fidelities, this rank's per-seed scalars, the control variable after the last Adam update, the
+    controls the last evaluation ran on and the final unitaries of that evaluation (complex as a trailing (re, im) axis)."""
+    os.makedirs(directory, exist_ok=True)
+    parts = [e.scalars() for e in engs]
+    out = {'fidelity': fidelity}
+    for key in ('loss', 'reg_loss', 'grad_squared', 'unitary_scale'):
+        out[key] = np.concatenate([q[key] for q in parts])
+    out['base'] = np.concatenate([e.get_base() for e in engs])
+    out['uks_evaluated'] = np.concatenate([e.get_uks(evaluated=True) for e in engs])
+    out['final_unitary'] = np.concatenate([e.get_final_unitary() for e in engs]).view(np.float64).reshape(-1, N, N, 2)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -456,6 +490,10 @@ def main():
     ap.add_argument('--chunks', type=int, default=0)
     ap.add_argument('--path', type=int, default=0)
     ap.add_argument('--variant', type=int, default=0, help='MFMA path: kernel of the exponentials (qoc_config.variant)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the roofline pass, the one-trajectory latency, the '
+                                                         'secondary configs, the live PMC passes and the CPU baselines (the --no-* options below '
+                                                         'leave single ones out)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy (float64)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-single', action='store_true', help='skip the one-trajectory latency measurement')
     ap.add_argument('--no-secondary', action='store_true', help='skip the BASELINE config 3 / config 5 entries (`secondary`)')
@@ -579,10 +617,12 @@ def main():
     ms_all = [q['ms_total'] for q in per_rank]
     if transport is not None:
         elapsed = float(transport.all_reduce_max([elapsed])[0])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, engs, fidelity)
 
     # ---- roofline of the dominant kernel, hipEvents on the engine stream (separate pass, rank 0) -----------------
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.profile_enable(True)
         eng.iterate(params, min(50, args.steps))
         pr = eng.profile_read()
@@ -620,7 +660,7 @@ def main():
                 'frac_of_measured_4x4x4_ceiling': ach_exec / 73.0}
     # ---- latency of ONE trajectory of the same workload (what a plain Grape() call runs), outside the timed region ----
     single = None
-    if rank == 0 and not args.no_single:
+    if rank == 0 and args.full and not args.no_single:
         e1 = hip_engine.HipEngine(Hs, U0, V, W, c['maxA'], dt, c['total_time'], SLICES, TAYLOR[0], TAYLOR[1],
                                   reg_coeffs={}, n_seeds=1, device=local_rank)
         e1.set_base(seed_bases(0, 1))
@@ -633,7 +673,7 @@ def main():
         e1.close()
     # ---- BASELINE configs 3 and 5, driver-visible (rank 0, N = 1, after the timed region) ------------------------------
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         secondary = secondary_configs(local_rank)
     # ---- HBM traffic of the dominant kernel, re-measured in this run (two rocprofv3 PMC passes beside the CPU legs) --------
     pmc = None
@@ -667,8 +707,9 @@ def main():
             'secondary': secondary,
             'best_fidelity': float(np.max(fidelity)),
             'roofline': roof,
+            'full': bool(args.full),
         }
-        if not args.no_cpu_baseline and world == 1:          # reported at N=1 only (contract)
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported at N=1 only (contract)
             out['cpu_baseline'] = cpu_baseline()
             try:
                 out['cpu_baseline_reference_ops'] = cpu_baseline_reference_ops()

@@ -505,7 +505,7 @@ def test_bench_line_n1_carries_secondary_configs_and_a_measured_traffic_figure()
     (rocprofv3 on PATH) or taken from the committed profile -- the line says which."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--prewarm', '5', '--no-cpu-baseline'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--prewarm', '5', '--no-cpu-baseline', '--full'],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -523,6 +523,33 @@ def test_bench_line_n1_carries_secondary_configs_and_a_measured_traffic_figure()
     assert roof['bound'] == 'mfma' and 0.3 < roof['frac'] < 1.0
     assert roof['traffic'] is None or roof['traffic'] > 1e8
     assert 'measured in this run' in roof['traffic_source'] or 'committed profile' in roof['traffic_source']
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain N = 1 run (no --full): one line with the headline keys and none of the extras, and --dump-outputs writes the state after the
+    last timed step as float64 arrays that agree with the line (fidelity = 1 - loss, best_fidelity) and with each other (controls against base)."""
+    import json
+    import subprocess
+    out_dir = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--prewarm', '5', '--dump-outputs', str(out_dir)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines[:3]
+    out = json.loads(lines[0])
+    assert out['steps'] == 4 and out['ms_per_step'] > 0 and out['value'] > 0 and out['dtype'] == 'f64' and out['full'] is False
+    assert out['roofline'] is None and out['secondary'] is None and out['single_trajectory'] is None and 'cpu_baseline' not in out
+    got = {f[:-4]: np.load(str(out_dir / f)) for f in os.listdir(str(out_dir))}
+    assert sorted(got) == sorted(['fidelity', 'loss', 'reg_loss', 'grad_squared', 'unitary_scale', 'base', 'uks_evaluated', 'final_unitary'])
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in got.values())
+    B = out['config']['total_seeds']
+    assert got['base'].shape == got['uks_evaluated'].shape == (B, 4, 500) and got['final_unitary'].shape == (B, 32, 32, 2)
+    np.testing.assert_array_equal(got['fidelity'], 1.0 - got['loss'])
+    assert float(np.max(got['fidelity'])) == out['best_fidelity']
+    # the last evaluation ran on maxA sin(base) of the variable BEFORE the last Adam update (rate 0.01 per step, maxA = 4)
+    moved = np.max(np.abs(got['uks_evaluated'] - 4.0 * np.sin(got['base'])))
+    assert 0.0 < moved < 0.2, moved
 
 
 # ---- round 6: first-contact hardening of the N > 1 start-up (VERDICT r5, "Next round" 7) ----------------------------------------------------------------

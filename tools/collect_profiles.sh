@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/collect
 mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 # kernel table of the driver command's timed workload (its dominant-kernel average must reproduce roofline.avg_launch_ms); the secondary configs and the
 # live PMC passes of the line (which start rocprofv3 themselves) are left out of this run: their kernels have their own tables below
