@@ -256,8 +256,31 @@ static int enqueue_small(qoc_engine* e, const QocAdamDev& ap, int iters) {
     return QOC_OK;
 }
 
+// Which kernel runs the tail of an iteration (regularisers, chain rule, stop rule, Adam; qoc_kernels_finish.h): a function of the engine alone,
+// used by enqueue_iteration to launch it, by qoc_create for gm.reduce_in_tail and by qoc_plan_describe to report it
+enum TailKind {
+    TAIL_IN_LAUNCH,          // workgroup-resident path: inside its own launch
+    TAIL_LATENCY_FUSED,      // MFMA latency mode without bandpass: the last-arriving workgroup of a seed in k_mfma_grad_lat* (64 (16 / NT) NT threads)
+    TAIL_SPLIT,              // k_finish_split_a / _b over fin_S workgroups per control set
+    TAIL_SPLIT_PARTIALS,     // ... part A summing the per-tile gradient partials of the GEMM path's persistent chains (no k_gemm_grad_reduce_wide)
+    TAIL_FINISH4,            // k_finish_t<., 4>: 256 threads below 2048 elements per control set, else 1024
+    TAIL_FINISH8,            // k_finish_t<., 8>: 4097 .. 8192 elements without the split tail (QOC_EXPERIMENTAL=1 QOC_FINISH_SPLIT=0)
+};
+
+static TailKind tail_kind(const qoc_engine* e) {
+    const QocDev& d = e->d;
+    const int ks = d.k * d.steps;
+    if (e->path == QOC_PATH_SMALL) return TAIL_IN_LAUNCH;
+    if (e->path == QOC_PATH_MFMA && e->mf.latency && (!e->mf.lat_sources || e->mf.lat_src_fast) && !d.has_band && !(e->skip_mask & (16 | 32)))
+        return TAIL_LATENCY_FUSED;
+    if (ks > 4 * 1024 && e->fin_part)
+        return e->path == QOC_PATH_GEMM && e->gm.persistent && e->skip_mask == 0 ? TAIL_SPLIT_PARTIALS : TAIL_SPLIT;
+    return ks <= 8 * 1024 && ks > 4 * 1024 ? TAIL_FINISH8 : TAIL_FINISH4;
+}
+
 static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     if (e->path == QOC_PATH_SMALL) return enqueue_small(e, ap, 1);
+    const TailKind tail = tail_kind(e);
     // the slice kernel of the n <= 32 latency mode forms its own controls; everybody else reads u / w: from k_controls, or -- when the Adam
     // tail of the previous iteration (or qoc_get_uks) has left them in u2 / w2 -- by swapping the two pairs (one launch less per iteration)
     const bool own_controls = e->path == QOC_PATH_MFMA && e->mf.latency && e->mf.NT == 2;
@@ -275,8 +298,7 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     const bool plain = !(d.has_amp || d.has_env || d.has_dwdt || d.has_d2wdt2 || d.has_band);
     // latency mode: the tail of the iteration runs in the last workgroup of the gradient kernel
     // (with the local pulse regularisers too -- amplitude, envelope, dwdt, d2wdt2; the bandpass DFT keeps its own launch)
-    const bool fused_tail = e->path == QOC_PATH_MFMA && e->mf.latency && (!e->mf.lat_sources || e->mf.lat_src_fast) && !d.has_band
-        && !(skip & (16 | 32));
+    const bool fused_tail = tail == TAIL_LATENCY_FUSED;
     // (latency mode of the MFMA path: the slice kernel of the exponentials forms its own controls)
     if (!(skip & 1) && !own_controls && !swap_in) hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, d);
     if (e->path == QOC_PATH_MFMA) {
@@ -342,13 +364,12 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         // seeds of 4097 .. 8192 (k, t) elements (C3: 6 x 1000) keep their Adam slots in registers too: eight elements per thread
         // ... or, since round 6, spread over fin_S workgroups in two launches: one control set of 6000 elements is bound by the fp64 sin / cos / sqrt / divide of the
         // ONE compute unit k_finish_t runs it on (C3, one trajectory: 32.5 us; profiles/r06_kernel_stats_c3_single_trajectory.txt)
-        const bool wide = d.k * d.steps > 4 * 1024 && d.k * d.steps <= 8 * 1024;
-        const bool split = d.k * d.steps > 4 * 1024 && e->fin_part;
-        if (split) {
+        const bool wide = tail == TAIL_FINISH8;
+        if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS) {
             const dim3 sg((unsigned)e->fin_S, (unsigned)d.B);
             // (GEMM path, persistent chains: the wide gradient product left per-tile partial dots -- qoc_gemm_backward skipped its reduce launch, part A sums them)
             QocGradPartial gp{nullptr, 0, 0, 0};
-            if (e->path == QOC_PATH_GEMM && e->gm.reduce_in_tail) gp = QocGradPartial{e->gm.partial, e->gm.N / 32, e->gm.ldW, e->gm.MV};
+            if (tail == TAIL_SPLIT_PARTIALS) gp = QocGradPartial{e->gm.partial, e->gm.N / 32, e->gm.ldW, e->gm.MV};
             if (plain) {
                 hipLaunchKernelGGL(k_finish_split_a<true>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part, gp);
                 hipLaunchKernelGGL(k_finish_split_b<true>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part);
@@ -769,7 +790,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
         if (rc) return bail(fail(rc, "qoc_create: %s", msg.c_str()));
         if (!qoc_gemm_lds_opt_in()) return bail(fail(QOC_ERR_HIP, "qoc_create: cannot reserve LDS for the GEMM-path kernels"));
         e->chunks = e->gm.NC;
-        e->gm.reduce_in_tail = e->gm.persistent && e->fin_part != nullptr && e->skip_mask == 0;      // (the split tail sums the gradient partials: one launch less)
+        e->gm.reduce_in_tail = tail_kind(e) == TAIL_SPLIT_PARTIALS;      // (the split tail sums the gradient partials: one launch less)
         if (e->gm.ts_G > 0) {
             std::string why;
             if (!qoc_gemm_ts_supported(e->gm, d, e->gm.ts_G, why))
@@ -1049,6 +1070,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 // sweeps=<downup|split|row_tile_gradient|latency|latency_sources|one_wave>
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
+// and on every path tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
     char tmp[256];
@@ -1076,6 +1098,18 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
             e->sm.src ? 1 : 0, (int)((e->sm.lds_bytes + 1023) / 1024));
     } else {
         snprintf(tmp, sizeof tmp, "path=%s", e->path == QOC_PATH_ST_FUSED ? "st_fused" : "generic");
+    }
+    // the kernel of the Adam tail (tail_kind) and where its elements live: registers while ks <= QFE x threads (finish_body's in_regs)
+    const int ks = e->d.k * e->d.steps, w = (int)strlen(tmp);
+    const TailKind tail = tail_kind(e);
+    if (tail == TAIL_IN_LAUNCH) snprintf(tmp + w, sizeof tmp - w, " tail=in_launch");
+    else if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS)
+        snprintf(tmp + w, sizeof tmp - w, " tail=split%d%s", e->fin_S, tail == TAIL_SPLIT_PARTIALS ? "_partials" : "");
+    else if (tail == TAIL_LATENCY_FUSED)
+        snprintf(tmp + w, sizeof tmp - w, " tail=latency_fused_%s", ks <= QF_E * 64 * (16 / e->mf.NT) * e->mf.NT ? "regs" : "memory");
+    else {
+        const int threads = ks >= 2048 ? 1024 : QOC_BLOCK, qfe = tail == TAIL_FINISH8 ? 8 : QF_E;
+        snprintf(tmp + w, sizeof tmp - w, " tail=finish%d_%s", threads, tail == TAIL_FINISH8 ? "regs8" : (ks <= qfe * threads ? "regs" : "memory"));
     }
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
