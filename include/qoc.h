@@ -127,6 +127,36 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
                const double* forbidden_coeffs, const double* Vs, qoc_handle* out);
 int qoc_destroy(qoc_handle h);
 
+/* ---- robust GRAPE: one pulse per control set over a weighted ensemble of Hamiltonians (no counterpart in the reference) --------
+ * Member e is the reference problem with drift H0 + sum_q offsets[e][q] P_q and controls amp_scales[e][j] H_j; it shares U0, V, W, maxA,
+ * the regularisers and the control set's pulse.  Per control set:
+ *   loss      = sum_e weights[e] loss_e         (the value the stop rule tests)
+ *   reg_loss  = loss + sum_e weights[e] (forbidden levels + speed_up)_e + the pulse regularisers of the shared pulse (counted once)
+ *   grad      = d reg_loss / d base             (the members' first-order GRAPE gradients, weighted)
+ *   unitary_scale = sum_e weights[e] unitary_scale_e;  grad_squared = sum grad^2 / 2 of that gradient
+ * With sum weights = 1 these are the weighted means of the members' own values.  The engine runs n_seeds x members trajectories of k + q
+ * controls (trajectory (g, e) = g * members + e; a perturbation is a frozen control row) and one Adam variable per control set.
+ * Every other entry point keeps its per-control-set shapes ([n_seeds] ...); qoc_get_final_unitary and qoc_get_inter_vecs return member 0
+ * of each control set.  Not available: the workgroup-resident path, the latency mode of the MFMA path (variant 5), time sharding, and
+ * k + q > 8 on the paths limited to 8 controls (QOC_ERR_INVALID); AUTO never resolves to them for an ensemble. */
+typedef struct qoc_ensemble {
+    int32_t members;            /* E >= 1 */
+    int32_t n_perturb;          /* q >= 0 */
+    const double* P;            /* [q][n][n] complex: -i*dt*P_q (may be NULL when q = 0) */
+    const double* offsets;      /* [E][q] */
+    const double* amp_scales;   /* [E][k] */
+    const double* weights;      /* [E], >= 0, used as given (the Python layer normalises them to sum 1) */
+} qoc_ensemble;
+/* cfg describes ONE member with n_seeds control sets (k = the real controls); the remaining arguments are exactly qoc_create's. */
+int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V,
+                        const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out);
+/* Per-member values of the last evaluation: loss [n_seeds][E] and reg_state [n_seeds][E] (forbidden levels + speed_up); any pointer may
+ * be NULL.  QOC_ERR_STATE on an engine made by qoc_create. */
+int qoc_get_member_scalars(qoc_handle h, double* loss, double* reg_state);
+/* Every member's final unitary of the last evaluation: [n_seeds][E][n][n] complex (unitary mode only). */
+int qoc_get_member_final_unitary(qoc_handle h, double* Uf);
+
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).
  * qoc_set_base also resets the Adam slots and the per-seed iteration counters / done flags. */

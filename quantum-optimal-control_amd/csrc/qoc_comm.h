@@ -206,6 +206,7 @@ int qoc_comm_all_gather_scalar(qoc_comm_handle c, qoc_handle e, int32_t which, i
     CHECK_C(c);
     if (!e || !out) return fail(QOC_ERR_INVALID, "qoc_comm_all_gather_scalar: null argument");
     if (e->cfg.device != c->device) return fail(QOC_ERR_INVALID, "qoc_comm_all_gather_scalar: engine on device %d, communicator on %d", e->cfg.device, c->device);
+    if (e->ens_E) return fail(QOC_ERR_INVALID, "qoc_comm_all_gather_scalar: ensemble engines are not supported");
     const QocDev& d = e->d;
     if (width < d.B) return fail(QOC_ERR_INVALID, "qoc_comm_all_gather_scalar: width %d < n_seeds %d", width, d.B);
     const double* src = which == 0 ? d.loss : which == 1 ? d.reg_loss : which == 2 ? d.g2 : which == 3 ? d.uscale : nullptr;

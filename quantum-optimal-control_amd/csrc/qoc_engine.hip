@@ -24,6 +24,7 @@
 #include "qoc_kernels_gemm.h"
 #include "qoc_gemm_ts.h"
 #include "qoc_small.h"
+#include "qoc_ensemble.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
 // (QOC_PLAN_LAT_WORK = 4608 seeds x time slices: since the batch sweeps take their chunk boundaries and final_state from k_mfma_bnd_scan
@@ -82,7 +83,16 @@ struct qoc_engine {
     double prof_ms = 0.0;
     int64_t prof_launches = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;
+    // robust ensemble (qoc_create_ensemble, csrc/qoc_ensemble.h): d is then the TRAJECTORY view (G E trajectories, k + q controls, read by
+    // the heavy kernels) and g the GROUP view (G control sets, k controls: variable, Adam slots, stop rule, pulse regularisers, the tail)
+    int ens_E = 0;
+    QocDev g;
+    QocEns en{};
+    std::vector<double> ens_wt;     // host copy of the weights (unitary_scale of a group is formed on read-back)
 };
+
+// the view that holds the control sets: the engine itself, or the group view of an ensemble engine
+static inline QocDev& sets(qoc_engine* e) { return e->ens_E ? e->g : e->d; }
 
 template <typename T>
 static int dev_alloc(qoc_engine* e, T** p, size_t count) {
@@ -268,8 +278,11 @@ enum TailKind {
 };
 
 static TailKind tail_kind(const qoc_engine* e) {
-    const QocDev& d = e->d;
+    const QocDev& d = e->ens_E ? e->g : e->d;
     const int ks = d.k * d.steps;
+    // an ensemble runs the stand-alone tails on its group view: never on one of the paths with a tail of their own, and its gradient is a
+    // plain array (k_ens_reduce), never the persistent chains' partials
+    if (e->ens_E) return ks > 4 * 1024 && e->fin_part ? TAIL_SPLIT : (ks <= 8 * 1024 && ks > 4 * 1024 ? TAIL_FINISH8 : TAIL_FINISH4);
     if (e->path == QOC_PATH_SMALL) return TAIL_IN_LAUNCH;
     if (e->path == QOC_PATH_MFMA && e->mf.latency && (!e->mf.lat_sources || e->mf.lat_src_fast) && !d.has_band && !(e->skip_mask & (16 | 32)))
         return TAIL_LATENCY_FUSED;
@@ -285,22 +298,33 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     // tail of the previous iteration (or qoc_get_uks) has left them in u2 / w2 -- by swapping the two pairs (one launch less per iteration)
     const bool own_controls = e->path == QOC_PATH_MFMA && e->mf.latency && e->mf.NT == 2;
     const bool swap_in = e->controls_ready && !own_controls && !(e->skip_mask & 1);
-    if (swap_in) { std::swap(e->d.u, e->d.u2); std::swap(e->d.w, e->d.w2); }
+    const bool ens = e->ens_E > 0;
+    QocDev& cv = sets(e);                    // (an ensemble: the group view holds the controls of the control sets)
+    if (swap_in) { std::swap(cv.u, cv.u2); std::swap(cv.w, cv.w2); }
     e->controls_ready = false;
     QocDev d = e->d;
     if (own_controls) { d.u2 = nullptr; d.w2 = nullptr; }
     d.skip_done = ap.mode == 1 ? 1 : 0;      // qoc_eval / explicit steps always evaluate every seed
+    QocDev gd = e->g;
+    gd.skip_done = d.skip_done;
     d.uscale_in_loss = (e->path == QOC_PATH_MFMA && !e->mf.latency && !e->mf.updown) ? 1 : 0;
     const int total = d.B * d.k * d.steps;
     int cgrid = (total + QOC_BLOCK - 1) / QOC_BLOCK;
     if (cgrid > 2048) cgrid = 2048;
     const int skip = e->skip_mask;
-    const bool plain = !(d.has_amp || d.has_env || d.has_dwdt || d.has_d2wdt2 || d.has_band);
+    const QocDev& td = ens ? gd : d;        // the view the tail runs on
+    const bool plain = !(td.has_amp || td.has_env || td.has_dwdt || td.has_d2wdt2 || td.has_band);
     // latency mode: the tail of the iteration runs in the last workgroup of the gradient kernel
     // (with the local pulse regularisers too -- amplitude, envelope, dwdt, d2wdt2; the bandpass DFT keeps its own launch)
     const bool fused_tail = tail == TAIL_LATENCY_FUSED;
     // (latency mode of the MFMA path: the slice kernel of the exponentials forms its own controls)
-    if (!(skip & 1) && !own_controls && !swap_in) hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, d);
+    if (ens) {
+        // every member's controls from its group's (formed from the variable unless the last tail left them), and the done flags
+        const size_t items = (size_t)gd.B * d.k * d.steps;
+        size_t eg = (items + QOC_BLOCK - 1) / QOC_BLOCK;
+        if (eg > 2048) eg = 2048;
+        if (!(skip & 1)) hipLaunchKernelGGL(k_ens_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+    } else if (!(skip & 1) && !own_controls && !swap_in) hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, d);
     if (e->path == QOC_PATH_MFMA) {
         TRY(prof_begin(e));
         if (!(skip & 2)) qoc_mfma_launch_expm(e->mf, d, e->stream);
@@ -354,34 +378,39 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         launch_loss(d, e->stream);
         hipLaunchKernelGGL(k_st_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
     }
+    // an ensemble: the members' gradients and losses, weighted, into the group view
+    if (ens && !(skip & 32)) {
+        const int ks = gd.k * gd.steps;
+        hipLaunchKernelGGL(k_ens_reduce, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en);
+    }
     if (!(skip & 32) && !fused_tail) {
-        const dim3 fb(d.k * d.steps >= 2048 ? 1024 : QOC_BLOCK);
-        if (d.has_band) {
-            const size_t items = (size_t)d.B * d.k * d.steps, g1 = (items + 3) / 4, g2 = (items + 255) / 256;
-            hipLaunchKernelGGL(k_band_spectrum, dim3((unsigned)(g1 > 8192 ? 8192 : g1)), dim3(256), 0, e->stream, d);
-            hipLaunchKernelGGL(k_band_gradient, dim3((unsigned)(g2 > 8192 ? 8192 : g2)), dim3(256), 0, e->stream, d);
+        const dim3 fb(td.k * td.steps >= 2048 ? 1024 : QOC_BLOCK);
+        if (td.has_band) {
+            const size_t items = (size_t)td.B * td.k * td.steps, g1 = (items + 3) / 4, g2 = (items + 255) / 256;
+            hipLaunchKernelGGL(k_band_spectrum, dim3((unsigned)(g1 > 8192 ? 8192 : g1)), dim3(256), 0, e->stream, td);
+            hipLaunchKernelGGL(k_band_gradient, dim3((unsigned)(g2 > 8192 ? 8192 : g2)), dim3(256), 0, e->stream, td);
         }
         // seeds of 4097 .. 8192 (k, t) elements (C3: 6 x 1000) keep their Adam slots in registers too: eight elements per thread
         // ... or, since round 6, spread over fin_S workgroups in two launches: one control set of 6000 elements is bound by the fp64 sin / cos / sqrt / divide of the
         // ONE compute unit k_finish_t runs it on (C3, one trajectory: 32.5 us; profiles/r06_kernel_stats_c3_single_trajectory.txt)
         const bool wide = tail == TAIL_FINISH8;
         if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS) {
-            const dim3 sg((unsigned)e->fin_S, (unsigned)d.B);
+            const dim3 sg((unsigned)e->fin_S, (unsigned)td.B);
             // (GEMM path, persistent chains: the wide gradient product left per-tile partial dots -- qoc_gemm_backward skipped its reduce launch, part A sums them)
             QocGradPartial gp{nullptr, 0, 0, 0};
             if (tail == TAIL_SPLIT_PARTIALS) gp = QocGradPartial{e->gm.partial, e->gm.N / 32, e->gm.ldW, e->gm.MV};
             if (plain) {
-                hipLaunchKernelGGL(k_finish_split_a<true>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part, gp);
-                hipLaunchKernelGGL(k_finish_split_b<true>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part);
+                hipLaunchKernelGGL(k_finish_split_a<true>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part, gp);
+                hipLaunchKernelGGL(k_finish_split_b<true>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part);
             } else {
-                hipLaunchKernelGGL(k_finish_split_a<false>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part, gp);
-                hipLaunchKernelGGL(k_finish_split_b<false>, sg, dim3(256), 0, e->stream, d, ap, e->fin_part);
+                hipLaunchKernelGGL(k_finish_split_a<false>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part, gp);
+                hipLaunchKernelGGL(k_finish_split_b<false>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part);
             }
         }
-        else if (plain && wide) hipLaunchKernelGGL((k_finish_t<true, 8>), dim3(d.B), fb, 0, e->stream, d, ap);
-        else if (plain) hipLaunchKernelGGL(k_finish_t<true>, dim3(d.B), fb, 0, e->stream, d, ap);
-        else if (wide) hipLaunchKernelGGL((k_finish_t<false, 8>), dim3(d.B), fb, 0, e->stream, d, ap);
-        else hipLaunchKernelGGL(k_finish_t<false>, dim3(d.B), fb, 0, e->stream, d, ap);
+        else if (plain && wide) hipLaunchKernelGGL((k_finish_t<true, 8>), dim3(td.B), fb, 0, e->stream, td, ap);
+        else if (plain) hipLaunchKernelGGL(k_finish_t<true>, dim3(td.B), fb, 0, e->stream, td, ap);
+        else if (wide) hipLaunchKernelGGL((k_finish_t<false, 8>), dim3(td.B), fb, 0, e->stream, td, ap);
+        else hipLaunchKernelGGL(k_finish_t<false>, dim3(td.B), fb, 0, e->stream, td, ap);
     }
     HIP_TRY(hipGetLastError());
     e->evaluated = true;
@@ -487,9 +516,18 @@ int qoc_device_peer_access(int32_t device, int32_t peer, int32_t* can_access) {
     return QOC_OK;
 }
 
-int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
-               const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-               const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+// what qoc_create_ensemble adds to the trajectory engine it creates: the caller's own configuration (k controls, n_seeds control sets, the
+// pulse regularisers) for the group view, and the member description
+struct EnsArgs {
+    const qoc_config* user;
+    const double* maxA;              // [k]
+    const double* one_minus_gauss;   // [k][steps] or null
+    const qoc_ensemble* ens;
+};
+
+static int create_engine(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
+                         const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                         const double* forbidden_coeffs, const double* Vs, const EnsArgs* ens, qoc_handle* out) {
     if (!cfg || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create: null argument");
     if (cfg->plan_seeds < 0) return fail(QOC_ERR_INVALID,
         "qoc_create: plan_seeds = %d (0 = plan for n_seeds, > 0 = the batch AUTO plans for)", cfg->plan_seeds);
@@ -519,6 +557,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
 
     qoc_engine* e = new qoc_engine();
     e->cfg = *cfg;
+    if (ens) e->ens_E = ens->ens->members;
     QocDev& d = e->d;
     memset(&d, 0, sizeof d);
     const int n = cfg->n, k = cfg->k, steps = cfg->steps, m = cfg->m, B = cfg->n_seeds;
@@ -583,7 +622,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     ALLOC(d.base, B * ks); ALLOC(d.adam_m, B * ks); ALLOC(d.adam_v, B * ks);
     ALLOC(d.adam_t, (size_t)B); ALLOC(d.iters, (size_t)B); ALLOC(d.done, (size_t)B);
     ALLOC(d.w, B * ks); ALLOC(d.u, B * ks); ALLOC(d.w2, B * ks); ALLOC(d.u2, B * ks); ALLOC(d.dLdu, B * ks); ALLOC(d.grad, B * ks);
-    if (ks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {      // (the tail of such control sets runs over fin_S workgroups each; the switch: A/B runs)
+    if (!ens && ks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {      // (the tail of such control sets runs over fin_S workgroups each; the switch: A/B runs)
         e->fin_S = (int)((ks + 255) / 256);
         if (e->fin_S > 64) e->fin_S = 64;                          // (longer pulses: several elements per thread)
         ALLOC(e->fin_part, (size_t)B * (e->fin_S + 2) * 2);
@@ -711,7 +750,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
         // -- n = 32 x 8: 0.220 against 0.261 ms, with forbidden levels 0.272 / 0.316
         const int lat_sets = n > 16 ? ((st && qa_g >= 7) ? QOC_PLAN_LAT_SETS_N32_ST_WIDE : QOC_PLAN_LAT_SETS_N32) : (st
             ? QOC_PLAN_LAT_SETS_N16_ST : QOC_PLAN_LAT_SETS_N16);
-        const bool latency = cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && mfma_auto && qoc_mfma_latency_ok(d)
+        const bool latency = !ens && cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && mfma_auto && qoc_mfma_latency_ok(d)
             && steps >= QOC_PLAN_LAT_MIN_SLICES &&
                               (((n > 48 || (n > 32 && k > 4)) ? (lat_work <= QOC_PLAN_LAT_WORK_NT4 && Bp <= QOC_PLAN_LAT_SETS_NT4)
                                 : n > 32 ? (lat_work <= QOC_PLAN_LAT_WORK_NT3 && Bp <= QOC_PLAN_LAT_SETS_NT3)
@@ -731,7 +770,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     // n <= 12, one or a few control sets (the reference's own use) and small batches: the workgroup-resident iteration (csrc/qoc_small.h) --
     // 5-20 us per iteration where the paths above pay 42-57 us of launches and dependent round trips whatever n (profiles/r06_small_n_latency.txt)
     // (QOC_EXPERIMENTAL=1 QOC_SMALL_AUTO=0: AUTO as it was before round 6, for A/B runs -- tools/small_n_latency.py)
-    if (cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && cfg->chunks == 0 && cfg->time_shards < 1 && !qoc_exp_is("QOC_SMALL_AUTO", 0) && qoc_small_auto(d, antiherm))
+    if (!ens && cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && cfg->chunks == 0 && cfg->time_shards < 1 && !qoc_exp_is("QOC_SMALL_AUTO", 0) && qoc_small_auto(d, antiherm))
         path = QOC_PATH_SMALL;
     if (d.Bplan < B) {
         // a plan for FEWER control sets than the engine holds is legal (a rank that holds several shards of a planned batch keeps
@@ -790,7 +829,7 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
         if (rc) return bail(fail(rc, "qoc_create: %s", msg.c_str()));
         if (!qoc_gemm_lds_opt_in()) return bail(fail(QOC_ERR_HIP, "qoc_create: cannot reserve LDS for the GEMM-path kernels"));
         e->chunks = e->gm.NC;
-        e->gm.reduce_in_tail = tail_kind(e) == TAIL_SPLIT_PARTIALS;      // (the split tail sums the gradient partials: one launch less)
+        e->gm.reduce_in_tail = !ens && tail_kind(e) == TAIL_SPLIT_PARTIALS;   // (an ensemble reduces the members' gradients first)      // (the split tail sums the gradient partials: one launch less)
         if (e->gm.ts_G > 0) {
             std::string why;
             if (!qoc_gemm_ts_supported(e->gm, d, e->gm.ts_G, why))
@@ -825,6 +864,51 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     } else if (path == QOC_PATH_GENERIC) {
         ALLOC(e->seed_scratch, (size_t)B * (nn + 3 * nm));
     }
+    if (ens) {
+        // the group view: the caller's G control sets of k controls -- variable, Adam slots, stop rule, pulse regularisers, the tail's arrays
+        const qoc_config* uc = ens->user;
+        const qoc_ensemble* en = ens->ens;
+        QocDev& gv = e->g;
+        gv = d;
+        const int kg = uc->k, G = uc->n_seeds, E = en->members, q = en->n_perturb;
+        const size_t gks = (size_t)kg * steps;
+        gv.k = kg; gv.B = G; gv.Bplan = G;
+        gv.has_amp = uc->has_amplitude; gv.a_amp = uc->c_amplitude * inv_steps;
+        gv.has_env = uc->has_envelope; gv.a_env = uc->c_envelope * inv_steps;
+        gv.has_dwdt = uc->has_dwdt; gv.a_dwdt = uc->c_dwdt * inv_steps;
+        gv.has_d2wdt2 = uc->has_d2wdt2; gv.a_d2wdt2 = uc->c_d2wdt2 * inv_steps;
+        gv.has_band = uc->has_bandpass; gv.a_band = uc->c_bandpass * inv_steps;
+        gv.band_lo = uc->band_lo; gv.band_hi = uc->band_hi;
+        gv.inter = nullptr; gv.Xfinal = nullptr; gv.ztau = nullptr; gv.Fpop = nullptr; gv.Fd = nullptr; gv.zfin = nullptr; gv.su_resid = nullptr;
+        gv.omg = nullptr; gv.band_ph = nullptr; gv.band_tw = nullptr; gv.band_mag = nullptr; gv.band_dR = nullptr;
+        if ((rc = dev_upload(e, &gv.maxA, ens->maxA, (size_t)kg))) return bail(rc);
+        if (ens->one_minus_gauss && (rc = dev_upload(e, &gv.omg, ens->one_minus_gauss, gks))) return bail(rc);
+        ALLOC(gv.base, G * gks); ALLOC(gv.adam_m, G * gks); ALLOC(gv.adam_v, G * gks);
+        ALLOC(gv.adam_t, (size_t)G); ALLOC(gv.iters, (size_t)G); ALLOC(gv.done, (size_t)G);
+        ALLOC(gv.w, G * gks); ALLOC(gv.u, G * gks); ALLOC(gv.w2, G * gks); ALLOC(gv.u2, G * gks); ALLOC(gv.dLdu, G * gks); ALLOC(gv.grad, G * gks);
+        ALLOC(gv.loss, (size_t)G); ALLOC(gv.reg_state, (size_t)G); ALLOC(gv.reg_loss, (size_t)G); ALLOC(gv.g2, (size_t)G); ALLOC(gv.uscale, (size_t)G);
+        if (gv.has_band) { ALLOC(gv.band_ph, G * gks); ALLOC(gv.band_tw, (size_t)steps); ALLOC(gv.band_mag, G * gks); ALLOC(gv.band_dR, G * gks); }
+        if (gks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {
+            e->fin_S = (int)((gks + 255) / 256);
+            if (e->fin_S > 64) e->fin_S = 64;
+            ALLOC(e->fin_part, (size_t)G * (e->fin_S + 2) * 2);
+        }
+        const double* da = nullptr; const double* dd = nullptr; const double* dw = nullptr;
+        if ((rc = dev_upload(e, &da, en->amp_scales, (size_t)E * kg))) return bail(rc);
+        if (q > 0 && (rc = dev_upload(e, &dd, en->offsets, (size_t)E * q))) return bail(rc);
+        if ((rc = dev_upload(e, &dw, en->weights, (size_t)E))) return bail(rc);
+        e->en = QocEns{E, q, da, dd, dw};
+        e->ens_wt.assign(en->weights, en->weights + E);
+        if (hipMemset(gv.base, 0, G * gks * sizeof(double)) != hipSuccess || hipMemset(gv.adam_m, 0, G * gks * sizeof(double)) != hipSuccess ||
+            hipMemset(gv.adam_v, 0, G * gks * sizeof(double)) != hipSuccess || hipMemset(gv.adam_t, 0, G * sizeof(int)) != hipSuccess ||
+            hipMemset(gv.iters, 0, G * sizeof(int)) != hipSuccess || hipMemset(gv.done, 0, G * sizeof(int)) != hipSuccess ||
+            hipMemset(gv.uscale, 0, G * sizeof(double)) != hipSuccess)
+            return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: clearing the state buffers failed"));
+        if (gv.has_band) {
+            hipLaunchKernelGGL(k_band_twiddles, dim3((steps + 255) / 256), dim3(256), 0, 0, gv.band_tw, steps);
+            if (hipGetLastError() != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: the bandpass phase table could not be formed"));
+        }
+    }
 #undef ALLOC
     {
         const hipError_t se = hipDeviceSynchronize();
@@ -832,6 +916,54 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     }
     *out = e;
     return QOC_OK;
+}
+
+int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
+               const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+               const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    return create_engine(cfg, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, nullptr, out);
+}
+
+int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
+                        const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!cfg || !ens || !Hs || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: null argument");
+    const int E = ens->members, q = ens->n_perturb;
+    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: members = %d (>= 1), n_perturb = %d (>= 0)", E, q);
+    if (!ens->amp_scales || !ens->weights || (q > 0 && (!ens->P || !ens->offsets)))
+        return fail(QOC_ERR_INVALID, "qoc_create_ensemble: ensemble arrays missing");
+    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
+        return fail(QOC_ERR_INVALID, "qoc_create_ensemble: n, k, steps, n_seeds must be >= 1");
+    if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: %d x %d trajectories", cfg->n_seeds, E);
+    if (cfg->has_envelope && !one_minus_gauss) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: envelope constant missing");
+    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: d2wdt2 needs dwdt (reference: NameError new_weights)");
+    for (int i = 0; i < E; ++i)
+        if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: weight %d is %g", i, ens->weights[i]);
+    // paths whose tail runs inside their own launch, or that form their controls from the variable, cannot host the member reduction
+    // (checked before any device is touched)
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: an ensemble cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+    if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
+        "inside its launch, where the members' gradients cannot be reduced first");
+    if (cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
+        "qoc_create_ensemble: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail");
+    if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && cfg->k + q > 8) return fail(QOC_ERR_INVALID,
+        "qoc_create_ensemble: path %d is limited to 8 controls; the ensemble's trajectories have k + q = %d", cfg->path, cfg->k + q);
+    // the trajectories: G E of them, k + q controls (the perturbations are frozen control rows), no pulse regulariser (the group view has them)
+    qoc_config tc = *cfg;
+    const int n = cfg->n, k = cfg->k;
+    const size_t nn = (size_t)n * n;
+    tc.k = k + q;
+    tc.n_seeds = cfg->n_seeds * E;
+    tc.plan_seeds = cfg->plan_seeds > 0 ? cfg->plan_seeds * E : 0;
+    tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
+    tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
+    std::vector<double> Hst(2 * nn * (size_t)(k + q + 1));
+    memcpy(Hst.data(), Hs, 2 * nn * (size_t)(k + 1) * sizeof(double));
+    if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(k + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
+    std::vector<double> maxAt(maxA, maxA + k);
+    maxAt.resize((size_t)(k + q), 1.0);
+    const EnsArgs ea{cfg, maxA, cfg->has_envelope ? one_minus_gauss : nullptr, ens};
+    return create_engine(&tc, Hst.data(), U0, V, W, maxAt.data(), nullptr, forbidden_states, forbidden_coeffs, Vs, &ea, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -854,8 +986,9 @@ int qoc_destroy(qoc_handle e) {
 int qoc_set_base(qoc_handle e, const double* base) {
     CHECK_H(e);
     if (!base) return fail(QOC_ERR_INVALID, "qoc_set_base: null base");
-    const QocDev& d = e->d;
+    const QocDev& d = sets(e);
     const size_t cnt = (size_t)d.B * d.k * d.steps;
+    if (e->ens_E) HIP_TRY(hipMemsetAsync(e->d.done, 0, e->d.B * sizeof(int), e->stream));     // (the members' flags: k_ens_expand mirrors them)
     // everything on the engine stream (it is non-blocking: the legacy null stream orders nothing against it), then one sync so
     // that the caller may reuse `base` and the next qoc_iterate sees the cleared optimiser state
     HIP_TRY(hipMemcpyAsync(d.base, base, cnt * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -873,14 +1006,15 @@ int qoc_set_base(qoc_handle e, const double* base) {
 int qoc_get_base(qoc_handle e, double* base) {
     CHECK_H(e);
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(base, e->d.base, (size_t)e->d.B * e->d.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    const QocDev& d = sets(e);
+    HIP_TRY(hipMemcpy(base, d.base, (size_t)d.B * d.k * d.steps * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
 int qoc_get_scalars(qoc_handle e, double* loss, double* reg_loss, double* grad_squared, double* unitary_scale,
                     int32_t* iterations, int32_t* done) {
     CHECK_H(e);
-    const QocDev& d = e->d;
+    const QocDev& d = sets(e);
     if (unitary_scale) TRY(refresh_final(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     TRY(small_check(e));
@@ -888,7 +1022,18 @@ int qoc_get_scalars(qoc_handle e, double* loss, double* reg_loss, double* grad_s
     if (loss) HIP_TRY(hipMemcpy(loss, d.loss, sz, hipMemcpyDeviceToHost));
     if (reg_loss) HIP_TRY(hipMemcpy(reg_loss, d.reg_loss, sz, hipMemcpyDeviceToHost));
     if (grad_squared) HIP_TRY(hipMemcpy(grad_squared, d.g2, sz, hipMemcpyDeviceToHost));
-    if (unitary_scale) HIP_TRY(hipMemcpy(unitary_scale, d.uscale, sz, hipMemcpyDeviceToHost));
+    if (unitary_scale && e->ens_E) {
+        // a group's unitary_scale: the weighted sum of its members' (which the lazy paths form only on read-back, refresh_final above), in
+        // member order as k_ens_reduce sums the losses
+        const int E = e->ens_E;
+        std::vector<double> us((size_t)e->d.B);
+        HIP_TRY(hipMemcpy(us.data(), e->d.uscale, us.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int g = 0; g < d.B; ++g) {
+            double acc = e->ens_wt[0] * us[(size_t)g * E];
+            for (int m = 1; m < E; ++m) acc = acc + e->ens_wt[m] * us[(size_t)g * E + m];
+            unitary_scale[g] = acc;
+        }
+    } else if (unitary_scale) HIP_TRY(hipMemcpy(unitary_scale, d.uscale, sz, hipMemcpyDeviceToHost));
     if (iterations) HIP_TRY(hipMemcpy(iterations, d.iters, d.B * sizeof(int), hipMemcpyDeviceToHost));
     if (done) HIP_TRY(hipMemcpy(done, d.done, d.B * sizeof(int), hipMemcpyDeviceToHost));
     return QOC_OK;
@@ -901,7 +1046,8 @@ int qoc_eval(qoc_handle e, double* loss, double* reg_loss, double* grad_squared,
     ap.mode = 0;
     TRY(enqueue_iteration(e, ap));
     TRY(qoc_get_scalars(e, loss, reg_loss, grad_squared, unitary_scale, nullptr, nullptr));
-    if (grad) HIP_TRY(hipMemcpy(grad, e->d.grad, (size_t)e->d.B * e->d.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    const QocDev& d = sets(e);
+    if (grad) HIP_TRY(hipMemcpy(grad, d.grad, (size_t)d.B * d.k * d.steps * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -910,7 +1056,7 @@ int qoc_adam_step(qoc_handle e, const double* lr) {
     if (!lr) return fail(QOC_ERR_INVALID, "qoc_adam_step: null lr");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_adam_step: no evaluation since the last qoc_set_base");
     // per-seed learning rates live in the engine's arena (no allocation per step); the copy is ordered on the engine stream
-    HIP_TRY(hipMemcpyAsync(e->step_lr, lr, e->d.B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->step_lr, lr, sets(e).B * sizeof(double), hipMemcpyHostToDevice, e->stream));
     QocAdamDev ap;
     memset(&ap, 0, sizeof ap);
     ap.mode = 2;
@@ -942,7 +1088,8 @@ int qoc_run_adam(qoc_handle e, const qoc_adam_params* p, int32_t* iterations_out
     if (!p) return fail(QOC_ERR_INVALID, "qoc_run_adam: null params");
     const QocAdamDev ap = loop_params(p);
     const int poll = p->poll_every > 0 ? p->poll_every : 1;
-    std::vector<int> done(e->d.B);
+    const QocDev& sd = sets(e);
+    std::vector<int> done(sd.B);
     // at most max_iterations updates + the evaluation that trips the stop rule
     const long long budget = (long long)p->max_iterations + 1;
     long long launched = 0;
@@ -954,20 +1101,20 @@ int qoc_run_adam(qoc_handle e, const qoc_adam_params* p, int32_t* iterations_out
         launched += burst;
         HIP_TRY(hipStreamSynchronize(e->stream));
         TRY(small_check(e));
-        HIP_TRY(hipMemcpy(done.data(), e->d.done, e->d.B * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(done.data(), sd.done, sd.B * sizeof(int), hipMemcpyDeviceToHost));
         bool all = true;
-        for (int b = 0; b < e->d.B; ++b) all = all && done[b];
+        for (int b = 0; b < sd.B; ++b) all = all && done[b];
         if (all) break;
         if (launched >= budget) return fail(QOC_ERR_STATE, "qoc_run_adam: seeds not finished after %lld evaluations", launched);
     }
-    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, e->d.iters, e->d.B * sizeof(int), hipMemcpyDeviceToHost));
+    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
 int qoc_get_uks(qoc_handle e, double* uks) {
     CHECK_H(e);
     if (!uks) return fail(QOC_ERR_INVALID, "qoc_get_uks: null output");
-    const QocDev& d = e->d;
+    const QocDev& d = sets(e);
     // uks = maxA[k] * sin(base) of the CURRENT variable (run_session.py:112-117), evaluated on the device
     const int total = d.B * d.k * d.steps;
     int cgrid = (total + QOC_BLOCK - 1) / QOC_BLOCK;
@@ -991,7 +1138,8 @@ int qoc_get_uks_evaluated(qoc_handle e, double* uks) {
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_uks_evaluated: nothing evaluated yet");
     // d.u still holds the controls the last evaluation ran on (an Adam step only moves `base`)
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(uks, e->d.u, (size_t)e->d.B * e->d.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    const QocDev& d = sets(e);
+    HIP_TRY(hipMemcpy(uks, d.u, (size_t)d.B * d.k * d.steps * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1001,7 +1149,9 @@ int qoc_get_final_unitary(qoc_handle e, double* Uf) {
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_final_unitary: nothing evaluated yet");
     TRY(refresh_final(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(Uf, e->d.Xfinal, (size_t)e->d.B * e->d.n * e->d.n * sizeof(cplx), hipMemcpyDeviceToHost));
+    const size_t row = (size_t)e->d.n * e->d.n * sizeof(cplx);
+    if (e->ens_E) HIP_TRY(hipMemcpy2D(Uf, row, e->d.Xfinal, row * e->ens_E, row, (size_t)e->g.B, hipMemcpyDeviceToHost));   // member 0 of each group
+    else HIP_TRY(hipMemcpy(Uf, e->d.Xfinal, (size_t)e->d.B * row, hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1017,7 +1167,32 @@ int qoc_get_inter_vecs(qoc_handle e, double* inter) {
         e->inter_stale = false;
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(inter, e->d.inter, (size_t)e->d.B * (e->d.steps + 1) * e->d.n * e->d.m * sizeof(cplx), hipMemcpyDeviceToHost));
+    const size_t row = (size_t)(e->d.steps + 1) * e->d.n * e->d.m * sizeof(cplx);
+    if (e->ens_E) HIP_TRY(hipMemcpy2D(inter, row, e->d.inter, row * e->ens_E, row, (size_t)e->g.B, hipMemcpyDeviceToHost));   // member 0 of each group
+    else HIP_TRY(hipMemcpy(inter, e->d.inter, (size_t)e->d.B * row, hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+int qoc_get_member_scalars(qoc_handle e, double* loss, double* reg_state) {
+    CHECK_H(e);
+    if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_scalars: not an ensemble engine (qoc_create_ensemble)");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_member_scalars: nothing evaluated yet");
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t sz = (size_t)e->d.B * sizeof(double);
+    if (loss) HIP_TRY(hipMemcpy(loss, e->d.loss, sz, hipMemcpyDeviceToHost));
+    if (reg_state) HIP_TRY(hipMemcpy(reg_state, e->d.reg_state, sz, hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+int qoc_get_member_final_unitary(qoc_handle e, double* Uf) {
+    CHECK_H(e);
+    if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: not an ensemble engine (qoc_create_ensemble)");
+    if (!Uf) return fail(QOC_ERR_INVALID, "qoc_get_member_final_unitary: null output");
+    if (e->d.state_transfer) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: state-transfer mode has no final unitary");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: nothing evaluated yet");
+    TRY(refresh_final(e));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(Uf, e->d.Xfinal, (size_t)e->d.B * e->d.n * e->d.n * sizeof(cplx), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1100,7 +1275,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
         snprintf(tmp, sizeof tmp, "path=%s", e->path == QOC_PATH_ST_FUSED ? "st_fused" : "generic");
     }
     // the kernel of the Adam tail (tail_kind) and where its elements live: registers while ks <= QFE x threads (finish_body's in_regs)
-    const int ks = e->d.k * e->d.steps, w = (int)strlen(tmp);
+    const int ks = sets(e).k * sets(e).steps, w = (int)strlen(tmp);
     const TailKind tail = tail_kind(e);
     if (tail == TAIL_IN_LAUNCH) snprintf(tmp + w, sizeof tmp - w, " tail=in_launch");
     else if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS)
@@ -1111,6 +1286,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
         const int threads = ks >= 2048 ? 1024 : QOC_BLOCK, qfe = tail == TAIL_FINISH8 ? 8 : QF_E;
         snprintf(tmp + w, sizeof tmp - w, " tail=finish%d_%s", threads, tail == TAIL_FINISH8 ? "regs8" : (ks <= qfe * threads ? "regs" : "memory"));
     }
+    // ensemble engines only (the plain engines' line stays as it was)
+    if (e->ens_E) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " members=%d perturbations=%d", e->ens_E, e->en.q); }
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }

@@ -29,6 +29,11 @@ class QocConfig(C.Structure):
                 ('variant', C.c_int32), ('plan_seeds', C.c_int32), ('time_shards', C.c_int32), ('time_rank', C.c_int32), ('reserved', C.c_int32 * 3)]
 
 
+class QocEnsemble(C.Structure):
+    _fields_ = [('members', C.c_int32), ('n_perturb', C.c_int32), ('P', C.POINTER(C.c_double)), ('offsets', C.POINTER(C.c_double)),
+                ('amp_scales', C.POINTER(C.c_double)), ('weights', C.POINTER(C.c_double))]
+
+
 class QocAdamParams(C.Structure):
     _fields_ = [('rate', C.c_double), ('learning_rate_decay', C.c_double), ('conv_target', C.c_double),
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
@@ -40,6 +45,10 @@ _lib = None
 
 _SIGNATURES = {
     'qoc_create': (C.c_int, [C.POINTER(QocConfig), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_ensemble': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP,
+                                      C.POINTER(C.c_void_p)]),
+    'qoc_get_member_scalars': (C.c_int, [C.c_void_p, _DP, _DP]),
+    'qoc_get_member_final_unitary': (C.c_int, [C.c_void_p, _DP]),
     'qoc_destroy': (C.c_int, [C.c_void_p]),
     'qoc_set_base': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_base': (C.c_int, [C.c_void_p, _DP]),
@@ -252,12 +261,32 @@ class QocComm(object):
         _check(self._lib.qoc_comm_barrier(self._h))
 
 
+def ensemble_arrays(ensemble, n, k, dt):
+    """The C ABI's qoc_ensemble arrays from a dict with keys `operators` (q Hermitian n x n matrices P_q), `offsets` (E x q), `amp_scales`
+    (E x k) and `weights` (E, used as given): (P = -i dt P_q stacked, offsets, amp_scales, weights), all C-contiguous."""
+    ops = [np.asarray(p, dtype=np.complex128) for p in ensemble.get('operators', [])]
+    q = len(ops)
+    amp = np.ascontiguousarray(np.asarray(ensemble['amp_scales'], dtype=np.float64))
+    E = amp.shape[0]
+    assert amp.shape == (E, k), amp.shape
+    off = np.ascontiguousarray(np.asarray(ensemble.get('offsets', np.zeros((E, 0))), dtype=np.float64).reshape(E, q))
+    wt = np.ascontiguousarray(np.asarray(ensemble['weights'], dtype=np.float64))
+    assert wt.shape == (E,), wt.shape
+    P = np.ascontiguousarray(np.stack([-1j * float(dt) * p for p in ops]) if q else np.zeros((0, n, n), dtype=np.complex128))
+    assert P.shape == (q, n, n), P.shape
+    return P, off, amp, wt
+
+
 class HipEngine(object):
-    """Device-resident GRAPE problem: constants in HBM, n_seeds control sets, one HIP stream."""
+    """Device-resident GRAPE problem: constants in HBM, n_seeds control sets, one HIP stream.
+
+    ensemble (robust GRAPE, include/qoc.h qoc_create_ensemble): a dict with keys `operators`, `offsets`, `amp_scales`, `weights` (see
+    ensemble_arrays); every control set is then optimised for the weighted objective over the members, and the read-backs keep their
+    per-control-set shapes (member 0 for the final unitary and inter_vecs; member_scalars / member_final_unitary give every member)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
-                 time_shards=0, time_rank=-1, time_comm=None):
+                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None):
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
@@ -295,10 +324,22 @@ class HipEngine(object):
             omg = np.ascontiguousarray(np.asarray(one_minus_gauss, dtype=np.float64))
             assert omg.shape == (k, int(steps))
         Vsa = _c128(Vs, (n, n)) if use_vs else None
-        _check(lib.qoc_create(C.byref(cfg), _dp(Hs.view(np.float64)), None if U0a is None else _dp(U0a.view(np.float64)),
-                              _dp(V.view(np.float64)), _dp(W.view(np.float64)), _dp(maxA), _dp(omg),
-                              None if fs is None else fs.ctypes.data_as(_IP), _dp(fc),
-                              None if Vsa is None else _dp(Vsa.view(np.float64)), C.byref(self._h)))
+        args = (_dp(Hs.view(np.float64)), None if U0a is None else _dp(U0a.view(np.float64)), _dp(V.view(np.float64)), _dp(W.view(np.float64)),
+                _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
+                C.byref(self._h))
+        self.members = 0
+        if ensemble is None:
+            _check(lib.qoc_create(C.byref(cfg), *args))
+        else:
+            P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt)
+            ens = QocEnsemble()
+            ens.members, ens.n_perturb = amp.shape[0], P.shape[0]
+            ens.P = _dp(P.view(np.float64)) if P.shape[0] else None
+            ens.offsets = _dp(off) if P.shape[0] else None
+            ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
+            self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
+            _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
+            self.members = int(amp.shape[0])
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
         buf = C.create_string_buffer(256)
@@ -389,6 +430,19 @@ class HipEngine(object):
     def get_final_unitary(self):
         out = np.empty((self.n_seeds, self.n, self.n), dtype=np.complex128)
         _check(self._lib.qoc_get_final_unitary(self._h, _dp(out.view(np.float64))))
+        return out
+
+    def member_scalars(self):
+        """Ensemble engines: dict(loss, reg_state) of the last evaluation, each [n_seeds][members]."""
+        loss = np.empty((self.n_seeds, self.members))
+        reg = np.empty((self.n_seeds, self.members))
+        _check(self._lib.qoc_get_member_scalars(self._h, _dp(loss), _dp(reg)))
+        return dict(loss=loss, reg_state=reg)
+
+    def member_final_unitary(self):
+        """Ensemble engines: every member's final unitary of the last evaluation, [n_seeds][members][n][n]."""
+        out = np.empty((self.n_seeds, self.members, self.n, self.n), dtype=np.complex128)
+        _check(self._lib.qoc_get_member_final_unitary(self._h, _dp(out.view(np.float64))))
         return out
 
     def get_inter_vecs(self):

@@ -114,6 +114,19 @@ class run_session(object):
             self.Uf = self.anly.get_final_state(save=False)
         else:
             self.Uf = []
+        if getattr(self.engine, 'members', 0):
+            self.robust_summary()
+
+    def robust_summary(self):
+        """Robust GRAPE: one line on the members of the reported control set, and their final losses in the run log."""
+        self.member_loss = self.engine.member_scalars()['loss'][self.seed]
+        worst = int(np.argmax(self.member_loss))
+        print('Robust ensemble: %d members, weighted mean infidelity %.3e, worst member infidelity %.3e (member %d)' % (
+            len(self.member_loss), self.l, self.member_loss[worst], worst))
+        if self.sys_para.save:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(self.sys_para.file_path) as hf:
+                hf.add('robust_member_loss', data=np.array(self.member_loss))
 
     def Get_uks(self):
         """Physical pulse amplitudes maxA_k sin(base), (k, steps) (run_session.py:112-117): the controls the reported

@@ -1,0 +1,140 @@
+"""Robust GRAPE: ensembles of perturbed Hamiltonians for ``Grape(..., robust=...)``.
+
+Member e of an ensemble is an ordinary GRAPE problem with the drift H0 + sum_q offsets[e, q] P_q and the control Hamiltonians
+amp_scales[e, j] H_j; all members share U0, the targets, the states of interest, maxA, the regularisers and the one trainable pulse.
+Grape optimises the weighted mean objective over the members (include/qoc.h, qoc_create_ensemble).
+"""
+import itertools
+
+import numpy as np
+
+
+def _rows(values, width, name):
+    """values as a 2-D float array of `width` columns; a scalar row applies to all columns."""
+    out = []
+    for row in values:
+        r = np.asarray(row, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(width, float(r))
+        r = r.reshape(-1)
+        if r.shape != (width,):
+            raise ValueError('%s: a row has %d entries, expected %d' % (name, r.shape[0], width))
+        out.append(r)
+    return np.array(out, dtype=np.float64).reshape(len(out), width)
+
+
+def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=None):
+    """Cartesian product of offset rows (each q values, one per operator) and amplitude-scale rows (each k values, or a scalar for
+    all k controls).  The nominal point (all offsets 0, all scales 1) comes first when the grid contains it; otherwise the
+    product order is kept (offset rows outer).  weights: one per grid point (default uniform), normalised to sum 1.
+    Returns the dict Grape(robust=...) takes."""
+    operators = [np.asarray(p) for p in operators]
+    q = len(operators)
+    if k is None:
+        raise ValueError('ensemble_grid: k (the number of control Hamiltonians) is required')
+    k = int(k)
+    off_rows = _rows(offsets if offsets is not None else [np.zeros(q)], q, 'offsets') if q else np.zeros((1, 0))
+    if q == 0 and offsets is not None and np.size(offsets) != 0:
+        raise ValueError('ensemble_grid: offsets given without operators')
+    amp_rows = _rows(amp_scales if amp_scales is not None else [1.0], k, 'amp_scales')
+    pts = [(o, a) for o, a in itertools.product(off_rows, amp_rows)]
+    if weights is None:
+        w = np.ones(len(pts))
+    else:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != len(pts):
+            raise ValueError('ensemble_grid: %d weights for %d grid points' % (w.shape[0], len(pts)))
+    nominal = [i for i, (o, a) in enumerate(pts) if np.all(o == 0.0) and np.all(a == 1.0)]
+    order = list(range(len(pts)))
+    if nominal:
+        order = [nominal[0]] + [i for i in order if i != nominal[0]]
+    ens = dict(operators=operators, offsets=np.array([pts[i][0] for i in order]).reshape(len(pts), q),
+               amp_scales=np.array([pts[i][1] for i in order]).reshape(len(pts), k), weights=w[order])
+    return validate(ens, None, k)
+
+
+def validate(robust, n, k):
+    """Checks a robust dict (keys operators, offsets, amp_scales, weights) against a problem of n levels (None: from the operators) and
+    k controls and returns it normalised: operators a list of q complex n x n Hermitian matrices, offsets (E, q), amp_scales (E, k)
+    (default ones), weights (E,) summing to 1 (default uniform).  Raises ValueError."""
+    if not isinstance(robust, dict):
+        raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights')
+    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights'}
+    if unknown:
+        raise ValueError('robust: unknown keys %s' % sorted(unknown))
+    ops = [np.asarray(p, dtype=np.complex128) for p in robust.get('operators', [])]
+    q = len(ops)
+    for i, p in enumerate(ops):
+        if p.ndim != 2 or p.shape[0] != p.shape[1] or (n is not None and p.shape[0] != n):
+            raise ValueError('robust: operator %d has shape %s, expected %s' % (i, p.shape, (n, n) if n is not None else 'square'))
+        if n is None:
+            n = p.shape[0]
+        if not np.allclose(p, p.conj().T, rtol=0.0, atol=1e-12 * max(1.0, float(np.max(np.abs(p))))):
+            raise ValueError('robust: operator %d is not Hermitian' % i)
+    E = None
+    offsets = robust.get('offsets')
+    if q:
+        if offsets is None:
+            raise ValueError('robust: offsets (E x q) are required with operators')
+        offsets = np.asarray(offsets, dtype=np.float64)
+        if offsets.ndim != 2 or offsets.shape[1] != q:
+            raise ValueError('robust: offsets have shape %s, expected (E, %d)' % (offsets.shape, q))
+        E = offsets.shape[0]
+    elif offsets is not None and np.size(offsets) != 0:
+        offsets = np.asarray(offsets, dtype=np.float64)
+        if offsets.ndim != 2 or offsets.shape[1] != 0:
+            raise ValueError('robust: offsets given without operators')
+        E = offsets.shape[0]
+    amp = robust.get('amp_scales')
+    if amp is not None:
+        amp = np.asarray(amp, dtype=np.float64)
+        if amp.ndim != 2 or amp.shape[1] != k or (E is not None and amp.shape[0] != E):
+            raise ValueError('robust: amp_scales have shape %s, expected (%s, %d)' % (amp.shape, 'E' if E is None else E, k))
+        E = amp.shape[0]
+    w = robust.get('weights')
+    if w is not None:
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if E is not None and w.shape[0] != E:
+            raise ValueError('robust: %d weights for %d members' % (w.shape[0], E))
+        E = w.shape[0]
+    if E is None or E < 1:
+        raise ValueError('robust: the ensemble has no members')
+    if amp is None:
+        amp = np.ones((E, k))
+    if w is None:
+        w = np.ones(E)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('robust: weights must be finite and >= 0')
+    if not w.sum() > 0:
+        raise ValueError('robust: the weights sum to zero')
+    if not (np.all(np.isfinite(amp)) and (offsets is None or np.all(np.isfinite(offsets)))):
+        raise ValueError('robust: offsets and amp_scales must be finite')
+    return dict(operators=ops, offsets=np.zeros((E, 0)) if offsets is None else offsets.reshape(E, q), amp_scales=amp,
+                weights=w / w.sum())
+
+
+def member_hamiltonians(H0, Hops, robust, e):
+    """(H0_e, [H_j,e]) of member e: the drift with its perturbations, the controls with their amplitude scales."""
+    H0e = np.asarray(H0, dtype=np.complex128).copy()
+    for qq, p in enumerate(robust['operators']):
+        H0e = H0e + robust['offsets'][e, qq] * p
+    return H0e, [robust['amp_scales'][e, j] * np.asarray(h) for j, h in enumerate(Hops)]
+
+
+def choose_taylor(H0, Hops, robust, maxA, U0, total_time, steps, unitary_error, state_transfer, no_scaling):
+    """(Taylor terms, squarings): the maximum over members of what SystemParameters' chooser picks for each member's problem."""
+    from quantum_optimal_control.core.system_parameters import N_CANDIDATES, SystemParameters
+    best_t, best_s = 0, 0
+    for e in range(robust['weights'].shape[0]):
+        H0e, Hopse = member_hamiltonians(H0, Hops, robust, e)
+        ch = SystemParameters.__new__(SystemParameters)      # the chooser alone: no initial guess is drawn
+        ch.H0_c, ch.ops_c, ch.ops_max_amp, ch.U0_c = H0e, Hopse, maxA, U0
+        ch.dt, ch.steps, ch.state_num = float(total_time) / steps, steps, len(H0e)
+        ch.Unitary_error, ch.state_transfer, ch.no_scaling = unitary_error, state_transfer, no_scaling
+        exps, scalings = [], []
+        for d in range(1 if (state_transfer or no_scaling) else N_CANDIDATES):
+            exps.append(ch.Choose_exp_terms(d))
+            scalings.append(ch.scaling)
+        i = int(np.argmin(np.add(exps, scalings)))
+        best_t, best_s = max(best_t, int(exps[i])), max(best_s, int(scalings[i]))
+    return best_t, best_s

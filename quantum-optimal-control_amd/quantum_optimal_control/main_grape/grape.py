@@ -52,12 +52,22 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, _first_seed=0, _device=0, _return_session=False):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, _first_seed=0, _device=0, _return_session=False):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
-    are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity."""
+    are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
+
+    ``robust`` (robust GRAPE): a dict with keys ``operators`` (q Hermitian n x n matrices P_q), ``offsets`` (E x q), ``amp_scales``
+    (E x k, default ones) and ``weights`` (E, default uniform; normalised to sum 1), e.g. from helper_functions.robust.ensemble_grid.
+    Member e has the drift H0 + sum_q offsets[e, q] P_q and the controls amp_scales[e, j] Hops[j]; the pulse is optimised for the
+    weighted mean of the members' objectives.  U_final is member 0's."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
+    if robust is not None:
+        from quantum_optimal_control.helper_functions import robust as _robust
+        if time_comm is not None:
+            raise ValueError('Grape: robust ensembles cannot be time-sharded (time_comm)')
+        robust = _robust.validate(robust, len(H0), len(Hops))
     if use_gpu:
         sparse_H = sparse_U = sparse_K = False          # dense kernels only
 
@@ -71,6 +81,13 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         print("data saved at: " + str(file_path))
         _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_concerned_list, use_gpu, sparse_H,
                      sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info)
+        if robust is not None:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                q = len(robust['operators'])
+                hf.add('robust_operators', data=np.array(robust['operators']).reshape(q, len(H0), len(H0)))
+                for key in ('offsets', 'amp_scales', 'weights'):
+                    hf.add('robust_' + key, data=robust[key])
 
     if U0 is None:
         U0 = np.identity(len(H0))
@@ -85,6 +102,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     else:
         maxAmp = maxA
 
+    if robust is not None and Taylor_terms is None:
+        # the largest Taylor order and squaring count any member's own problem would get (both only lower the truncation error)
+        Taylor_terms = _robust.choose_taylor(H0, Hops, robust, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
+
     sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
                                 maxAmp, draw, initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
                                 reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, sparse_H, sparse_U,
@@ -94,7 +115,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     # bit-identically under any rank count; Grape(restarts=R, plan_seeds=hip_engine.plan_seeds_for(R)) reproduces a sharded run in one process.
     # time_comm (extension): a hip_engine.QocComm whose ranks share ONE large trajectory along the time axis (GrapeTimeSharded below)
     tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
-                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm)   # constants -> HBM
+                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
@@ -153,6 +174,9 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
     (tests/sharded_script.py checks array_equal); an engine that holds more control sets than it plans for says so on stderr when that changes
     the kernels it runs."""
     from quantum_optimal_control.parallel_seeds import SeedShard
+    if kwargs.get('robust') is not None:
+        # (before any rank builds an engine: every rank raises alike)
+        raise ValueError('GrapeSharded: robust ensembles are not supported; run Grape(robust=..., restarts=R) on one GPU')
     if comm is not None:
         world, rank = comm.world, comm.rank
     elif dist is not None:
