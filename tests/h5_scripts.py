@@ -124,5 +124,55 @@ def grape_save(tmp):
     print('OK grape_save')
 
 
+def grape_robust_save(tmp):
+    """GPU: Grape(robust=..., save=True) logs the validated ensemble (robust_operators / _offsets / _amp_scales / _weights) and the members' losses at
+    the returned pulse (robust_member_loss): the latter against one unchanged oracle system per member (NumPy only), built from the logged Taylor
+    order, at base = arcsin(uks / maxA) -- the members' losses depend on the controls alone.  1e-12 relative to max(1, |x|): the project's bound on
+    a scalar of a 40-slice problem."""
+    import h5py
+    sys.path.insert(0, ROOT)
+    from oracle import grape_oracle as go
+    from quantum_optimal_control.helper_functions import robust as rb
+    from quantum_optimal_control.main_grape.grape import Grape
+    rng = np.random.default_rng(17)
+    n, k, steps, T = 9, 2, 40, 2.0
+
+    def herm():
+        A = rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n))
+        return (A + A.conj().T) / 2
+    H0, Hops = 2.0 * herm(), [0.8 * herm() for _ in range(k)]
+    U = np.linalg.qr(rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n)))[0]
+    given = dict(operators=[0.6 * herm(), 0.4 * herm()], offsets=[[0.0, 0.0], [0.2, -0.1], [-0.15, 0.05], [0.1, 0.1]],
+                 amp_scales=[[1.0, 1.0], [1.05, 0.9], [0.95, 1.1], [1.0, 0.0]], weights=[2.0, 1.0, 1.0, 0.5])
+    ens = rb.validate(given, n, k)
+    assert abs(ens['weights'].sum() - 1.0) < 1e-15
+    maxA, states = [1.5, 1.0], list(range(4))
+    regs = {'dwdt': 1e-3, 'forbidden_coeff_list': [5.0], 'states_forbidden_list': [n - 1]}
+    conv = {'rate': 0.02, 'update_step': 5, 'evol_save_step': 10, 'max_iterations': 12, 'conv_target': 1e-12, 'learning_rate_decay': 500}
+    np.random.seed(5)
+    uks, Uf = Grape(H0, Hops, ['x', 'y'], U, T, steps, states, convergence=conv, reg_coeffs=regs, maxA=maxA, show_plots=False, save=True,
+                    file_name='r', data_path=tmp, robust=given, restarts=3)
+    with h5py.File(os.path.join(tmp, '00000_r.h5'), 'r') as f:
+        for key in ('robust_operators', 'robust_offsets', 'robust_amp_scales', 'robust_weights', 'robust_member_loss', 'taylor_terms', 'taylor_scaling'):
+            assert key in f, key
+        assert np.array_equal(f['robust_operators'][()], np.array(ens['operators'])) and f['robust_operators'].shape == (2, n, n)
+        for key in ('offsets', 'amp_scales', 'weights'):
+            assert np.array_equal(f['robust_' + key][()], ens[key]), key
+        logged = f['robust_member_loss'][()]
+        taylor = (int(f['taylor_terms'][()]), int(f['taylor_scaling'][()]))
+        assert np.allclose(f['uks'][-1], uks, rtol=0, atol=0)
+    base = np.arcsin(np.asarray(uks) / np.asarray(maxA)[:, None])
+    want = []
+    for e in range(4):
+        H0e, Hopse = rb.member_hamiltonians(H0, Hops, ens, e)
+        sp = go.OracleSystem(H0e, Hopse, U, T, steps, states, U0=None, reg_coeffs=regs, dressed_info=None, maxA=maxA, state_transfer=False,
+                             Taylor_terms=taylor)
+        want.append(go.evaluate(sp, base, want_grad=False)['loss'])
+    want = np.array(want)
+    print('member losses: logged %s oracle %s' % (logged, want))
+    assert logged.shape == (4,) and np.max(np.abs(logged - want)) <= 1e-12 * max(1.0, np.max(np.abs(want))), (logged, want)
+    print('OK grape_robust_save')
+
+
 if __name__ == '__main__':
     globals()[sys.argv[1]](sys.argv[2])

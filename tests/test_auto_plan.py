@@ -111,10 +111,16 @@ def small_plan(n, k, m, steps, T, s, B, state_transfer=False, n_forb=0, speed_up
     return {'path': 'small', 'n_pad': best[1], 'rows': best[2], 'slices_per_row': best[3], 'workgroups': best[4], 'state_sources': 1 if src else 0}
 
 
-def expected_plan(n, k, m, steps, T, B, state_transfer=False, state_reg=False, hermitian=True, s=2):
-    """DESIGN.md section 4, the AUTO table, as ordered rules -> the dict HipEngine.plan reports."""
+def expected_plan(n, k, m, steps, T, B, state_transfer=False, state_reg=False, hermitian=True, s=2, ensemble=None):
+    """DESIGN.md section 4, the AUTO table, as ordered rules -> the dict HipEngine.plan reports.
+
+    ensemble=(E, q): a robust ensemble engine (qoc_create_ensemble) of B control sets -- the kernels see B E trajectories of k + q controls (the
+    perturbations are frozen control rows), and neither the workgroup-resident path nor the latency mode can host the member reduction."""
     st = state_transfer
-    small = small_plan(n, k, m, steps, T, s, B, state_transfer=st, n_forb=(2 if st else 1) if state_reg else 0, hermitian=hermitian)
+    if ensemble is not None:
+        E, q = ensemble
+        k, B = k + q, B * E
+    small = None if ensemble is not None else small_plan(n, k, m, steps, T, s, B, state_transfer=st, n_forb=(2 if st else 1) if state_reg else 0, hermitian=hermitian)
     if small is not None:                                 # row "n <= 12, one or a few control sets": the whole iteration inside one launch
         return small
     deg = T - 1 if st else T                              # matvecexp sums j < T: the propagator is the Taylor polynomial of degree T - 1
@@ -144,7 +150,7 @@ def expected_plan(n, k, m, steps, T, B, state_transfer=False, state_reg=False, h
         return {'path': 'gemm', 'route': 'unitary'} if m <= 32 else {'path': 'generic'}
     work = B * steps
     # row "latency mode": one or a few control sets
-    if deg >= 2 and steps >= LIM['LAT_MIN_SLICES']:
+    if ensemble is None and deg >= 2 and steps >= LIM['LAT_MIN_SLICES']:
         if n > 48 or (n > 32 and k > 4):
             lat = work <= LAT_WORK_NT4 and B <= LIM['LAT_SETS_NT4']
         elif n > 32:
@@ -372,3 +378,56 @@ def test_auto_plan_small_excluded_shapes():
     c = _problem(8, 2, 64, 3, 5, 2, False, seed=9)
     c['reg_coeffs'] = {'forbidden_coeff_list': [1.0] * 5, 'states_forbidden_list': [7, 6, 5, 4, 3]}
     _run(c, 1, {'path': 'mfma'}, seed=1)
+
+
+# ---- robust ensembles (qoc_create_ensemble): the kernels see G E trajectories of k + q controls ------------------------------------------------------
+# (kind, n, k, m, slices, forbidden levels, control sets G, members E, perturbations q, plan_seeds): both sides of every threshold that is keyed on the
+# control count -- state transfer at n = 40: k' = 4 | 5 (MFMA batch kernels | GEMM routes); unitary at n = 32: k' = 5 | 6 (downup | row_tile_gradient);
+# k' = 8 | 9 (the MFMA and fused paths end); unitary at n = 64: k' = 4 | 5 moves the NT = 4 batch size from NT4_MIN_SETS_K4 to NT4_MIN_SETS -- and of
+# plan_seeds: an engine of ONE control set planned for 8 reports the plan of 8 E trajectories
+ENSEMBLE_ROWS = [('st', 40, 3, 1, 100, False, 3, 3, 1, 0), ('st', 40, 3, 1, 100, False, 3, 3, 2, 0), ('st', 40, 4, 1, 100, True, 3, 3, 1, 0), ('st', 40, 2, 1, 100, True, 3, 3, 2, 0),
+                 ('u', 32, 4, 8, 130, False, 4, 4, 1, 0), ('u', 32, 4, 8, 130, False, 4, 4, 2, 0), ('u', 32, 3, 8, 130, True, 4, 4, 2, 0), ('u', 32, 3, 8, 130, True, 4, 4, 3, 0),
+                 ('u', 24, 6, 8, 130, False, 2, 3, 2, 0), ('u', 24, 6, 8, 130, False, 2, 3, 3, 0), ('u', 64, 6, 8, 70, False, 16, 4, 2, 0), ('u', 64, 6, 8, 70, False, 16, 4, 3, 0),
+                 ('st', 20, 6, 1, 100, False, 2, 3, 2, 0), ('st', 20, 6, 1, 100, False, 2, 3, 3, 0), ('st', 64, 6, 1, 100, True, 2, 3, 2, 0), ('st', 64, 6, 1, 100, True, 2, 3, 3, 0),
+                 ('u', 64, 3, 8, 70, False, 1, 31, 1, 0), ('u', 64, 3, 8, 70, False, 4, 8, 1, 0), ('u', 64, 3, 8, 70, False, 4, 8, 2, 0), ('u', 64, 3, 8, 70, False, 7, 9, 2, 0),
+                 ('u', 64, 3, 8, 70, False, 8, 8, 2, 0),
+                 ('u', 32, 4, 8, 130, False, 1, 4, 1, 0), ('u', 32, 4, 8, 130, False, 1, 4, 1, 8), ('u', 32, 4, 8, 500, False, 1, 8, 1, 8), ('u', 48, 3, 8, 130, False, 1, 2, 1, 0),
+                 ('u', 48, 3, 8, 130, False, 1, 2, 1, 8), ('st', 64, 6, 1, 100, True, 1, 4, 1, 0), ('st', 64, 6, 1, 100, True, 1, 4, 1, 8)]
+
+
+def _ensemble_expect(kind, n, k, m, steps, reg, G, E, q, plan):
+    return expected_plan(n, k, m, steps, 8 if kind == 'st' else 5, plan if plan else G, state_transfer=kind == 'st', state_reg=reg, ensemble=(E, q))
+
+
+def test_auto_plan_ensemble_rows_cover_both_sides():
+    """The rows above do sit on both sides of the thresholds they name (needs no device, like test_auto_plan_small_rows_cover_both_sides)."""
+    plans = {r: _ensemble_expect(*r) for r in ENSEMBLE_ROWS}
+
+    def of(**kw):
+        return [p for r, p in plans.items() if all(dict(zip(('kind', 'n', 'k', 'm', 'steps', 'reg', 'G', 'E', 'q', 'plan'), r))[key] == v for key, v in kw.items())]
+    assert {p['path'] for p in of(kind='st', n=40)} == {'mfma', 'gemm'}
+    assert {p['sweeps'] for p in of(kind='u', n=32, reg=False, plan=0, G=4)} == {'downup', 'row_tile_gradient'}
+    assert {p['sweeps'] for p in of(kind='u', n=32, reg=True)} == {'pair', 'row_tile_gradient'}
+    for kw in (dict(kind='u', n=24), dict(kind='u', n=64, k=6), dict(kind='st', n=20)):
+        assert {p['path'] for p in of(**kw)} == {'mfma', 'gemm'}, kw
+    assert [p['path'] for p in of(kind='u', n=64, k=3)] == ['gemm', 'mfma', 'gemm', 'gemm', 'mfma']
+    for a, b in ((21, 22), (24, 25), (26, 27)):                    # plan_seeds = 0 | 8 of the same engine
+        assert ENSEMBLE_ROWS[a][:9] == ENSEMBLE_ROWS[b][:9] and plans[ENSEMBLE_ROWS[a]] != plans[ENSEMBLE_ROWS[b]], (a, b)
+
+
+@pytest.mark.parametrize('kind,n,k,m,steps,reg,G,E,q,plan', ENSEMBLE_ROWS,
+                         ids=['%s_n%d_k%d+%d_G%dxE%d%s%s' % (r[0], r[1], r[2], r[8], r[6], r[7], '_forb' if r[5] else '', '_plan%d' % r[9] if r[9] else '') for r in ENSEMBLE_ROWS])
+def test_auto_plan_ensemble_rows(kind, n, k, m, steps, reg, G, E, q, plan):
+    """Plan only: the engine is created and closed.  AUTO's table with k -> k + q and B -> G E (plan_seeds E when planned for another batch), the
+    latency mode and the workgroup-resident path excluded."""
+    from tests.test_robust_gpu import ensemble, make_engine, nominal_system
+    c = _st_problem(n, k, m, steps, True, reg) if kind == 'st' else _problem(n, k, steps, m, 5, 2, reg, seed=300 + n)
+    expect = _ensemble_expect(kind, n, k, m, steps, reg, G, E, q, plan)
+    eng = make_engine(nominal_system(c), G, ensemble(c, E, q), plan_seeds=plan)
+    try:
+        got = {key: (int(v) if v.lstrip('-').isdigit() else v) for key, v in eng.plan.items()}
+        for key, want in dict(expect, members=E, perturbations=q).items():
+            assert got.get(key) == want, (key, want, got)
+        assert not got['tail'].startswith(('in_launch', 'latency')) and not got['tail'].endswith('partials'), got
+    finally:
+        eng.close()

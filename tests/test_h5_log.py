@@ -39,3 +39,8 @@ def test_analysis_datasets(tmp_path):
 @pytest.mark.gpu
 def test_grape_save_and_resimulation(tmp_path):
     _run('grape_save', tmp_path)
+
+
+@pytest.mark.gpu
+def test_grape_robust_datasets_of_the_run_log(tmp_path):
+    _run('grape_robust_save', tmp_path)

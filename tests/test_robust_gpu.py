@@ -80,19 +80,19 @@ def nominal_system(c):
                           c['Taylor_terms'])[0]
 
 
-def composed(sps, w, base):
-    """The ensemble's expected values at `base` (k x steps) from the members' oracle evaluations."""
-    rs = [go.evaluate(sp, base) for sp in sps]
+def composed(sps, w, base, want_inter=False):
+    """The ensemble's expected values at `base` (k x steps) from the members' oracle evaluations (`members`: the evaluations themselves)."""
+    rs = [go.evaluate(sp, base, want_inter=want_inter) for sp in sps]
     grad = sum(wi * r['grad'] for wi, r in zip(w, rs))
     return dict(loss=sum(wi * r['loss'] for wi, r in zip(w, rs)), reg_loss=sum(wi * r['reg_loss'] for wi, r in zip(w, rs)),
                 unitary_scale=sum(wi * r['unitary_scale'] for wi, r in zip(w, rs)), grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)),
-                member_loss=np.array([r['loss'] for r in rs]), U0=rs[0]['U_final'] if not sps[0].state_transfer else None)
+                member_loss=np.array([r['loss'] for r in rs]), U0=rs[0]['U_final'] if not sps[0].state_transfer else None, members=rs)
 
 
-def make_engine(sp, G, ens, path=P.PATH_AUTO, variant=0, chunks=0):
+def make_engine(sp, G, ens, path=P.PATH_AUTO, variant=0, chunks=0, plan_seeds=0):
     return hip_engine.HipEngine(sp.Hs, sp.U0, sp.V, sp.W, sp.maxA, sp.dt, sp.total_time, sp.steps, sp.exp_terms, sp.scaling,
                                 state_transfer=sp.state_transfer, reg_coeffs=sp.reg_coeffs, one_minus_gauss=sp.one_minus_gauss, Vs=sp.Vs,
-                                n_seeds=G, path=path, variant=variant, chunks=chunks, ensemble=ens)
+                                n_seeds=G, path=path, variant=variant, chunks=chunks, plan_seeds=plan_seeds, ensemble=ens)
 
 
 def bases_for(sp, G):

@@ -2,6 +2,10 @@
 """Robust GRAPE cost: us per iteration (qoc_time_iterations) of an ensemble engine beside a plain engine of G E control sets on the same
 path and plan -- a qubit ensemble (E = 9, 100 slices) and a C2-sized one (n = 32, k = 4, 500 slices, E = 64, one control set).
 
+This tool only times; it never looks at a result.  The C2 x 64 ensemble it times (plan: path=mfma nt=2 expm=8 chunks=16 sweeps=downup) is checked
+against the ensemble composed from the CPU oracle by tests/test_robust_families.py (row headline_c2_x64_downup_lazy_final: scalars, gradient,
+every member's loss and final unitary, the vectors at every slice, an Adam step), as is every other kernel family an ensemble can run on.
+
     python tools/robust_bench.py [--iters N]"""
 import argparse
 import os
