@@ -157,6 +157,31 @@ int qoc_get_member_scalars(qoc_handle h, double* loss, double* reg_state);
 /* Every member's final unitary of the last evaluation: [n_seeds][E][n][n] complex (unitary mode only). */
 int qoc_get_member_final_unitary(qoc_handle h, double* Uf);
 
+/* ---- transfer-function GRAPE: the variable is the AWG's samples, the pulse a known linear response of them (no counterpart in the
+ * reference, whose dwdt / bandpass / envelope penalties shrink what a line will not pass but do not model what it does) ----------------
+ * T is a real steps x n_samples matrix (zero-order hold, interpolation, a filter or line response).  Per control set, with the variable
+ * theta [k][P]:  w_s = sin(theta), the samples c = maxA_j w_s;  w_f[j][t] = sum_p T[t][p] w_s[j][p];  u_f = maxA_j w_f is the pulse
+ * every trajectory runs on (member e of an ensemble: amp_scales[e][j] u_f).
+ *   loss, unitary_scale, forbidden levels, speed_up : those of the steps-slice problem on u_f (coefficients divided by steps)
+ *   amplitude, dwdt, d2wdt2, bandpass               : act on the SAMPLES, as the reference's terms with steps := P and
+ *                                                     dt := total_time / P (coefficients divided by P; band indices from band * total_time)
+ *   envelope                                        : rejected (its constant is defined per time slice)
+ *   grad = d reg_loss / d theta                     : T^T applied to the members' weighted gradients, then the sample view's chain rule
+ * qoc_set_base, qoc_get_base, qoc_eval's grad, qoc_get_uks and qoc_get_uks_evaluated are [n_seeds][k][P] on such an engine;
+ * qoc_get_final_unitary and qoc_get_inter_vecs keep their steps shapes.  ens may be NULL: one nominal member.  The exclusions are the
+ * ensemble's.  QOC_ERR_INVALID: n_samples < 1, a non-finite T, an all-zero column of T (a sample that never reaches the pulse),
+ * has_envelope. */
+typedef struct qoc_transfer {
+    int32_t n_samples;          /* P >= 1 */
+    const double* T;            /* [steps][n_samples] */
+} qoc_transfer;
+int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* transfer, const double* Hs, const double* U0,
+                      const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out);
+/* u_f of the last evaluation, [n_seeds][k][steps] (the nominal pulse, before any member's amplitude scale).  QOC_ERR_STATE on an engine
+ * not made by qoc_create_shaped. */
+int qoc_get_pulse(qoc_handle h, double* u);
+
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).
  * qoc_set_base also resets the Adam slots and the per-seed iteration counters / done flags. */

@@ -25,6 +25,7 @@
 #include "qoc_gemm_ts.h"
 #include "qoc_small.h"
 #include "qoc_ensemble.h"
+#include "qoc_transfer.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
 // (QOC_PLAN_LAT_WORK = 4608 seeds x time slices: since the batch sweeps take their chunk boundaries and final_state from k_mfma_bnd_scan
@@ -89,6 +90,10 @@ struct qoc_engine {
     QocDev g;
     QocEns en{};
     std::vector<double> ens_wt;     // host copy of the weights (unitary_scale of a group is formed on read-back)
+    // transfer-function GRAPE (qoc_create_shaped, csrc/qoc_transfer.h): an ensemble engine whose group view is the SAMPLE view (P samples per
+    // control in place of the time slices) and whose glue kernels apply the response matrix
+    bool shaped = false;
+    QocShape sh{};
 };
 
 // the view that holds the control sets: the engine itself, or the group view of an ensemble engine
@@ -323,7 +328,17 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         const size_t items = (size_t)gd.B * d.k * d.steps;
         size_t eg = (items + QOC_BLOCK - 1) / QOC_BLOCK;
         if (eg > 2048) eg = 2048;
-        if (!(skip & 1)) hipLaunchKernelGGL(k_ens_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+        if (!(skip & 1) && !e->shaped) hipLaunchKernelGGL(k_ens_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+        else if (!(skip & 1)) {
+            // a pulse response: the samples w_s / u_s from the variable (unless the last tail left them), then the pulse through the response
+            if (!swap_in) {
+                const size_t sitems = (size_t)gd.B * gd.k * gd.steps;
+                size_t sg = (sitems + QOC_BLOCK - 1) / QOC_BLOCK;
+                if (sg > 2048) sg = 2048;
+                hipLaunchKernelGGL(k_controls, dim3((unsigned)sg), dim3(QOC_BLOCK), 0, e->stream, gd);
+            }
+            hipLaunchKernelGGL(k_shape_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
+        }
     } else if (!(skip & 1) && !own_controls && !swap_in) hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, d);
     if (e->path == QOC_PATH_MFMA) {
         TRY(prof_begin(e));
@@ -381,7 +396,10 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     // an ensemble: the members' gradients and losses, weighted, into the group view
     if (ens && !(skip & 32)) {
         const int ks = gd.k * gd.steps;
-        hipLaunchKernelGGL(k_ens_reduce, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en);
+        if (!e->shaped) hipLaunchKernelGGL(k_ens_reduce, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en);
+        else if (e->sh.col_band <= QOC_SHAPE_WAVE_FROM)
+            hipLaunchKernelGGL(k_shape_reduce<1>, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en, e->sh);
+        else hipLaunchKernelGGL(k_shape_reduce<64>, dim3((unsigned)((ks + 3) / 4), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en, e->sh);
     }
     if (!(skip & 32) && !fused_tail) {
         const dim3 fb(td.k * td.steps >= 2048 ? 1024 : QOC_BLOCK);
@@ -523,6 +541,14 @@ struct EnsArgs {
     const double* maxA;              // [k]
     const double* one_minus_gauss;   // [k][steps] or null
     const qoc_ensemble* ens;
+    const struct ShapeHost* shape;   // qoc_create_shaped: the response matrix and its windows, else null
+};
+
+// the response matrix of qoc_create_shaped as the host prepared it: the transposed copy and the nonzero window of every row and column
+struct ShapeHost {
+    int P, band, col_band;
+    std::vector<double> Tt;          // [P][steps]: T transposed (what the kernels read)
+    std::vector<int2> row_win, col_win;
 };
 
 static int create_engine(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
@@ -871,13 +897,19 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
         QocDev& gv = e->g;
         gv = d;
         const int kg = uc->k, G = uc->n_seeds, E = en->members, q = en->n_perturb;
-        const size_t gks = (size_t)kg * steps;
+        // (a pulse response: the group view is the sample view -- P samples of total_time / P each stand where the time slices stood, so the
+        // pulse regularisers act on the samples with their coefficients divided by P)
+        const ShapeHost* shp = ens->shape;
+        const int gsteps = shp ? shp->P : steps;
+        const double inv_gsteps = shp ? 1.0 / (double)gsteps : inv_steps;
+        const size_t gks = (size_t)kg * gsteps;
         gv.k = kg; gv.B = G; gv.Bplan = G;
-        gv.has_amp = uc->has_amplitude; gv.a_amp = uc->c_amplitude * inv_steps;
-        gv.has_env = uc->has_envelope; gv.a_env = uc->c_envelope * inv_steps;
-        gv.has_dwdt = uc->has_dwdt; gv.a_dwdt = uc->c_dwdt * inv_steps;
-        gv.has_d2wdt2 = uc->has_d2wdt2; gv.a_d2wdt2 = uc->c_d2wdt2 * inv_steps;
-        gv.has_band = uc->has_bandpass; gv.a_band = uc->c_bandpass * inv_steps;
+        if (shp) { gv.steps = gsteps; gv.dt = uc->total_time / (double)gsteps; }
+        gv.has_amp = uc->has_amplitude; gv.a_amp = uc->c_amplitude * inv_gsteps;
+        gv.has_env = uc->has_envelope; gv.a_env = uc->c_envelope * inv_gsteps;
+        gv.has_dwdt = uc->has_dwdt; gv.a_dwdt = uc->c_dwdt * inv_gsteps;
+        gv.has_d2wdt2 = uc->has_d2wdt2; gv.a_d2wdt2 = uc->c_d2wdt2 * inv_gsteps;
+        gv.has_band = uc->has_bandpass; gv.a_band = uc->c_bandpass * inv_gsteps;
         gv.band_lo = uc->band_lo; gv.band_hi = uc->band_hi;
         gv.inter = nullptr; gv.Xfinal = nullptr; gv.ztau = nullptr; gv.Fpop = nullptr; gv.Fd = nullptr; gv.zfin = nullptr; gv.su_resid = nullptr;
         gv.omg = nullptr; gv.band_ph = nullptr; gv.band_tw = nullptr; gv.band_mag = nullptr; gv.band_dR = nullptr;
@@ -887,7 +919,7 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
         ALLOC(gv.adam_t, (size_t)G); ALLOC(gv.iters, (size_t)G); ALLOC(gv.done, (size_t)G);
         ALLOC(gv.w, G * gks); ALLOC(gv.u, G * gks); ALLOC(gv.w2, G * gks); ALLOC(gv.u2, G * gks); ALLOC(gv.dLdu, G * gks); ALLOC(gv.grad, G * gks);
         ALLOC(gv.loss, (size_t)G); ALLOC(gv.reg_state, (size_t)G); ALLOC(gv.reg_loss, (size_t)G); ALLOC(gv.g2, (size_t)G); ALLOC(gv.uscale, (size_t)G);
-        if (gv.has_band) { ALLOC(gv.band_ph, G * gks); ALLOC(gv.band_tw, (size_t)steps); ALLOC(gv.band_mag, G * gks); ALLOC(gv.band_dR, G * gks); }
+        if (gv.has_band) { ALLOC(gv.band_ph, G * gks); ALLOC(gv.band_tw, (size_t)gsteps); ALLOC(gv.band_mag, G * gks); ALLOC(gv.band_dR, G * gks); }
         if (gks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {
             e->fin_S = (int)((gks + 255) / 256);
             if (e->fin_S > 64) e->fin_S = 64;
@@ -905,8 +937,17 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
             hipMemset(gv.uscale, 0, G * sizeof(double)) != hipSuccess)
             return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: clearing the state buffers failed"));
         if (gv.has_band) {
-            hipLaunchKernelGGL(k_band_twiddles, dim3((steps + 255) / 256), dim3(256), 0, 0, gv.band_tw, steps);
+            hipLaunchKernelGGL(k_band_twiddles, dim3((gsteps + 255) / 256), dim3(256), 0, 0, gv.band_tw, gsteps);
             if (hipGetLastError() != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: the bandpass phase table could not be formed"));
+        }
+        if (shp) {
+            QocShape& sh = e->sh;
+            sh.P = shp->P; sh.band = shp->band; sh.col_band = shp->col_band;
+            if ((rc = dev_upload(e, &sh.Tt, shp->Tt.data(), (size_t)steps * gsteps))) return bail(rc);
+            if ((rc = dev_upload(e, &sh.row_win, shp->row_win.data(), (size_t)steps))) return bail(rc);
+            if ((rc = dev_upload(e, &sh.col_win, shp->col_win.data(), (size_t)gsteps))) return bail(rc);
+            ALLOC(sh.uf, (size_t)G * kg * steps);
+            e->shaped = true;
         }
     }
 #undef ALLOC
@@ -924,30 +965,31 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     return create_engine(cfg, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, nullptr, out);
 }
 
-int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
-                        const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    if (!cfg || !ens || !Hs || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: null argument");
+// qoc_create_ensemble and qoc_create_shaped (`who` names the caller in the messages; shape: the prepared response of the latter, else null)
+static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0,
+                          const double* V, const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                          const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!cfg || !ens || !Hs || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int E = ens->members, q = ens->n_perturb;
-    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: members = %d (>= 1), n_perturb = %d (>= 0)", E, q);
+    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
     if (!ens->amp_scales || !ens->weights || (q > 0 && (!ens->P || !ens->offsets)))
-        return fail(QOC_ERR_INVALID, "qoc_create_ensemble: ensemble arrays missing");
+        return fail(QOC_ERR_INVALID, "%s: ensemble arrays missing", who);
     if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
-        return fail(QOC_ERR_INVALID, "qoc_create_ensemble: n, k, steps, n_seeds must be >= 1");
-    if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: %d x %d trajectories", cfg->n_seeds, E);
-    if (cfg->has_envelope && !one_minus_gauss) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: envelope constant missing");
-    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: d2wdt2 needs dwdt (reference: NameError new_weights)");
+        return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
+    if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "%s: %d x %d trajectories", who, cfg->n_seeds, E);
+    if (cfg->has_envelope && !one_minus_gauss) return fail(QOC_ERR_INVALID, "%s: envelope constant missing", who);
+    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "%s: d2wdt2 needs dwdt (reference: NameError new_weights)", who);
     for (int i = 0; i < E; ++i)
-        if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: weight %d is %g", i, ens->weights[i]);
+        if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "%s: weight %d is %g", who, i, ens->weights[i]);
     // paths whose tail runs inside their own launch, or that form their controls from the variable, cannot host the member reduction
     // (checked before any device is touched)
-    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: an ensemble cannot be time-sharded (time_shards = %d)", cfg->time_shards);
-    if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
-        "inside its launch, where the members' gradients cannot be reduced first");
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an ensemble cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
+    if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "%s: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
+        "inside its launch, where the members' gradients cannot be reduced first", who);
     if (cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
-        "qoc_create_ensemble: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail");
+        "%s: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail", who);
     if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && cfg->k + q > 8) return fail(QOC_ERR_INVALID,
-        "qoc_create_ensemble: path %d is limited to 8 controls; the ensemble's trajectories have k + q = %d", cfg->path, cfg->k + q);
+        "%s: path %d is limited to 8 controls; the ensemble's trajectories have k + q = %d", who, cfg->path, cfg->k + q);
     // the trajectories: G E of them, k + q controls (the perturbations are frozen control rows), no pulse regulariser (the group view has them)
     qoc_config tc = *cfg;
     const int n = cfg->n, k = cfg->k;
@@ -962,8 +1004,54 @@ int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const do
     if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(k + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
     std::vector<double> maxAt(maxA, maxA + k);
     maxAt.resize((size_t)(k + q), 1.0);
-    const EnsArgs ea{cfg, maxA, cfg->has_envelope ? one_minus_gauss : nullptr, ens};
+    const EnsArgs ea{cfg, maxA, cfg->has_envelope ? one_minus_gauss : nullptr, ens, shape};
     return create_engine(&tc, Hst.data(), U0, V, W, maxAt.data(), nullptr, forbidden_states, forbidden_coeffs, Vs, &ea, out);
+}
+
+int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
+                        const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    return create_members("qoc_create_ensemble", nullptr, cfg, ens, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, out);
+}
+
+int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
+                      const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                      const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!cfg || !tr || !maxA) return fail(QOC_ERR_INVALID, "qoc_create_shaped: null argument");
+    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "qoc_create_shaped: k, steps must be >= 1");
+    const int P = tr->n_samples, steps = cfg->steps, k = cfg->k;
+    if (P < 1) return fail(QOC_ERR_INVALID, "qoc_create_shaped: n_samples = %d (>= 1)", P);
+    if (!tr->T) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the response matrix is missing");
+    if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the envelope regulariser is defined per time slice, not per sample");
+    // the response: finite, every sample reaches the pulse; the nonzero window of every row and column and the transposed copy
+    ShapeHost sh;
+    sh.P = P; sh.band = 0; sh.col_band = 0;
+    sh.Tt.resize((size_t)P * steps);
+    sh.row_win.assign((size_t)steps, make_int2(0, 0));
+    sh.col_win.assign((size_t)P, make_int2(0, 0));
+    for (int t = 0; t < steps; ++t)
+        for (int p = 0; p < P; ++p) {
+            const double v = tr->T[(size_t)t * P + p];
+            if (!std::isfinite(v)) return fail(QOC_ERR_INVALID, "qoc_create_shaped: T[%d][%d] is not finite", t, p);
+            sh.Tt[(size_t)p * steps + t] = v;
+            if (v != 0.0) {
+                int2& r = sh.row_win[t];
+                int2& c = sh.col_win[p];
+                if (r.x == r.y) r.x = p;
+                r.y = p + 1;
+                if (c.x == c.y) c.x = t;
+                c.y = t + 1;
+            }
+        }
+    for (int p = 0; p < P; ++p) {
+        if (sh.col_win[p].x == sh.col_win[p].y) return fail(QOC_ERR_INVALID, "qoc_create_shaped: column %d of T is zero (the sample never reaches the pulse)", p);
+        sh.col_band = std::max(sh.col_band, sh.col_win[p].y - sh.col_win[p].x);
+    }
+    for (int t = 0; t < steps; ++t) sh.band = std::max(sh.band, sh.row_win[t].y - sh.row_win[t].x);
+    // no ensemble: one nominal member
+    const std::vector<double> ones((size_t)k + 1, 1.0);
+    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
+    return create_members("qoc_create_shaped", &sh, cfg, ens ? ens : &nominal, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1143,6 +1231,17 @@ int qoc_get_uks_evaluated(qoc_handle e, double* uks) {
     return QOC_OK;
 }
 
+int qoc_get_pulse(qoc_handle e, double* u) {
+    CHECK_H(e);
+    if (!e->shaped) return fail(QOC_ERR_STATE, "qoc_get_pulse: not a shaped engine (qoc_create_shaped)");
+    if (!u) return fail(QOC_ERR_INVALID, "qoc_get_pulse: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_pulse: nothing evaluated yet");
+    // (k_shape_expand stores the nominal pulse of every evaluation beside the trajectories' scaled copies)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(u, e->sh.uf, (size_t)e->g.B * e->g.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
 int qoc_get_final_unitary(qoc_handle e, double* Uf) {
     CHECK_H(e);
     if (e->d.state_transfer) return fail(QOC_ERR_STATE, "qoc_get_final_unitary: state-transfer mode has no final unitary");
@@ -1288,6 +1387,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     }
     // ensemble engines only (the plain engines' line stays as it was)
     if (e->ens_E) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " members=%d perturbations=%d", e->ens_E, e->en.q); }
+    if (e->shaped) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " samples=%d band=%d", e->sh.P, e->sh.band); }
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }

@@ -38,7 +38,10 @@ class Analysis(object):
 
     def get_ops_weight(self):
         """sin(ops_weight_base), (k, steps) (analysis.py:37-41); physical amplitudes are maxA_k times this."""
-        uks = np.array(self.engine.get_uks()[self.seed])
+        if getattr(self.engine, 'samples', None) is not None:      # transfer-function GRAPE: the pulse on the time axis, not the samples
+            uks = np.array(self.engine.get_pulse()[self.seed])
+        else:
+            uks = np.array(self.engine.get_uks()[self.seed])
         return uks / np.asarray(self.sys_para.ops_max_amp, dtype=np.float64)[:, None]
 
     def get_inter_vecs(self):

@@ -34,6 +34,10 @@ class QocEnsemble(C.Structure):
                 ('amp_scales', C.POINTER(C.c_double)), ('weights', C.POINTER(C.c_double))]
 
 
+class QocTransfer(C.Structure):
+    _fields_ = [('n_samples', C.c_int32), ('T', C.POINTER(C.c_double))]
+
+
 class QocAdamParams(C.Structure):
     _fields_ = [('rate', C.c_double), ('learning_rate_decay', C.c_double), ('conv_target', C.c_double),
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
@@ -47,6 +51,9 @@ _SIGNATURES = {
     'qoc_create': (C.c_int, [C.POINTER(QocConfig), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_ensemble': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP,
                                       C.POINTER(C.c_void_p)]),
+    'qoc_create_shaped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP,
+                                    _DP, C.POINTER(C.c_void_p)]),
+    'qoc_get_pulse': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_member_scalars': (C.c_int, [C.c_void_p, _DP, _DP]),
     'qoc_get_member_final_unitary': (C.c_int, [C.c_void_p, _DP]),
     'qoc_destroy': (C.c_int, [C.c_void_p]),
@@ -282,11 +289,15 @@ class HipEngine(object):
 
     ensemble (robust GRAPE, include/qoc.h qoc_create_ensemble): a dict with keys `operators`, `offsets`, `amp_scales`, `weights` (see
     ensemble_arrays); every control set is then optimised for the weighted objective over the members, and the read-backs keep their
-    per-control-set shapes (member 0 for the final unitary and inter_vecs; member_scalars / member_final_unitary give every member)."""
+    per-control-set shapes (member 0 for the final unitary and inter_vecs; member_scalars / member_final_unitary give every member).
+
+    transfer (transfer-function GRAPE, include/qoc.h qoc_create_shaped): a real steps x P response matrix.  The variable, the gradient and
+    get_uks are then (n_seeds, k, P) -- the AWG's samples --, get_pulse() gives the (n_seeds, k, steps) pulse the trajectories ran on, and the
+    pulse regularisers act on the samples.  Composes with ensemble."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
-                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None):
+                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None):
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
@@ -328,9 +339,9 @@ class HipEngine(object):
                 _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
                 C.byref(self._h))
         self.members = 0
-        if ensemble is None:
-            _check(lib.qoc_create(C.byref(cfg), *args))
-        else:
+        self.samples = None                           # transfer-function GRAPE: P, the length of the variable's rows
+        ens = None
+        if ensemble is not None:
             P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt)
             ens = QocEnsemble()
             ens.members, ens.n_perturb = amp.shape[0], P.shape[0]
@@ -338,8 +349,20 @@ class HipEngine(object):
             ens.offsets = _dp(off) if P.shape[0] else None
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
+        if transfer is not None:
+            T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
+            if T.ndim != 2 or T.shape[0] != int(steps):
+                raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
+            tr = QocTransfer()
+            tr.n_samples, tr.T = T.shape[1], _dp(T)
+            _check(lib.qoc_create_shaped(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(tr), *args))
+            self.samples = int(T.shape[1])
+        elif ens is None:
+            _check(lib.qoc_create(C.byref(cfg), *args))
+        else:
             _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
-            self.members = int(amp.shape[0])
+        if ens is not None:
+            self.members = int(ens.members)
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
         buf = C.create_string_buffer(256)
@@ -367,7 +390,7 @@ class HipEngine(object):
 
     # -- trainable variable ---------------------------------------------------------------------------------------
     def _seed_shape(self):
-        return (self.n_seeds, self.k, self.steps)
+        return (self.n_seeds, self.k, self.steps if self.samples is None else self.samples)
 
     def set_base(self, base):
         base = np.ascontiguousarray(np.asarray(base, dtype=np.float64)).reshape(self._seed_shape())
@@ -425,6 +448,12 @@ class HipEngine(object):
         out = np.empty(self._seed_shape())
         fn = self._lib.qoc_get_uks_evaluated if evaluated else self._lib.qoc_get_uks
         _check(fn(self._h, _dp(out)))
+        return out
+
+    def get_pulse(self):
+        """Transfer-function engines: the (n_seeds, k, steps) pulse u_f = maxA T sin(base) the last evaluation ran on."""
+        out = np.empty((self.n_seeds, self.k, self.steps))
+        _check(self._lib.qoc_get_pulse(self._h, _dp(out)))
         return out
 
     def get_final_unitary(self):

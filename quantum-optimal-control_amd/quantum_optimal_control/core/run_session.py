@@ -114,6 +114,7 @@ class run_session(object):
             self.Uf = self.anly.get_final_state(save=False)
         else:
             self.Uf = []
+        self.samples = self.Get_samples() if self.engine.samples is not None else None
         if getattr(self.engine, 'members', 0):
             self.robust_summary()
 
@@ -131,19 +132,25 @@ class run_session(object):
     def Get_uks(self):
         """Physical pulse amplitudes maxA_k sin(base), (k, steps) (run_session.py:112-117): the controls the reported
         loss / final_state / inter_vecs were evaluated on."""
+        if self.engine.samples is not None:                # transfer-function GRAPE: the pulse behind the response, (k, steps)
+            return self.engine.get_pulse()[self.seed]
+        return self.engine.get_uks(evaluated=True)[self.seed]
+
+    def Get_samples(self):
+        """Transfer-function GRAPE: the sample amplitudes maxA_k sin(base), (k, P), whose response Get_uks returns."""
         return self.engine.get_uks(evaluated=True)[self.seed]
 
     def get_error(self, uks):
         """Loss, regularised loss, flattened gradient, unitary metric and grad_squared at controls `uks`
         (the variable is the pre-sin base, exactly as in the reference where get_error assigns ops_weight_base)."""
         eng = self.engine
-        base = np.broadcast_to(np.reshape(np.asarray(uks, dtype=np.float64), (eng.k, eng.steps)),
-                               (eng.n_seeds, eng.k, eng.steps))
+        shape = eng._seed_shape()                          # (n_seeds, k, steps), or (n_seeds, k, P) samples behind a response
+        base = np.broadcast_to(np.reshape(np.asarray(uks, dtype=np.float64), shape[1:]), shape)
         adam_state_reset = base      # set_base resets the optimiser slots, irrelevant for scipy drivers
         eng.set_base(adam_state_reset)
         r = eng.evaluate(want_grad=True)
         b = self.seed
-        g = np.reshape(r['grad'][b], (eng.k * eng.steps))
+        g = np.reshape(r['grad'][b], -1)
         return float(r['loss'][b]), float(r['reg_loss'][b]), g, float(r['unitary_scale'][b]), float(r['grad_squared'][b])
 
     def save_data(self):
@@ -154,6 +161,8 @@ class run_session(object):
                 hf.append('error', np.array(self.l))
                 hf.append('reg_error', np.array(self.rl))
                 hf.append('uks', np.array(self.Get_uks()))
+                if self.engine.samples is not None:
+                    hf.append('uks_samples', np.array(self.Get_samples()))
                 hf.append('iteration', np.array(self.iterations))
                 hf.append('run_time', np.array(self.elapsed))
                 hf.append('unitary_scale', np.array(self.metric))

@@ -52,7 +52,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, _first_seed=0, _device=0, _return_session=False):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, _first_seed=0, _device=0, _return_session=False):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -60,7 +60,12 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``robust`` (robust GRAPE): a dict with keys ``operators`` (q Hermitian n x n matrices P_q), ``offsets`` (E x q), ``amp_scales``
     (E x k, default ones) and ``weights`` (E, default uniform; normalised to sum 1), e.g. from helper_functions.robust.ensemble_grid.
     Member e has the drift H0 + sum_q offsets[e, q] P_q and the controls amp_scales[e, j] Hops[j]; the pulse is optimised for the
-    weighted mean of the members' objectives.  U_final is member 0's."""
+    weighted mean of the members' objectives.  U_final is member 0's.
+
+    ``transfer`` (transfer-function GRAPE): a helper_functions.transfer.Transfer (or a steps x P matrix): the variable is then the k x P
+    samples an AWG plays, and the pulse the Hamiltonian sees is their response ``samples @ T.T``.  ``initial_guess`` is k x P sample
+    amplitudes; the returned uks is the k x steps pulse, ``transfer.samples`` the k x P samples behind it.  The pulse regularisers
+    (amplitude, dwdt, d2wdt2, bandpass) act on the samples; ``envelope`` is rejected.  Composes with ``robust``."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     if robust is not None:
@@ -68,6 +73,13 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if time_comm is not None:
             raise ValueError('Grape: robust ensembles cannot be time-sharded (time_comm)')
         robust = _robust.validate(robust, len(H0), len(Hops))
+    if transfer is not None:
+        from quantum_optimal_control.helper_functions import transfer as _transfer
+        if time_comm is not None:
+            raise ValueError('Grape: a transfer function cannot be time-sharded (time_comm)')
+        transfer = _transfer.validate(transfer, steps)
+        if reg_coeffs is not None and 'envelope' in reg_coeffs:
+            raise ValueError('Grape: the envelope regulariser is defined per time slice; it cannot act on the samples of a transfer function')
     if use_gpu:
         sparse_H = sparse_U = sparse_K = False          # dense kernels only
 
@@ -88,6 +100,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                 hf.add('robust_operators', data=np.array(robust['operators']).reshape(q, len(H0), len(H0)))
                 for key in ('offsets', 'amp_scales', 'weights'):
                     hf.add('robust_' + key, data=robust[key])
+        if transfer is not None:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                hf.add('transfer_matrix', data=transfer.matrix)
 
     if U0 is None:
         U0 = np.identity(len(H0))
@@ -106,20 +122,43 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         # the largest Taylor order and squaring count any member's own problem would get (both only lower the truncation error)
         Taylor_terms = _robust.choose_taylor(H0, Hops, robust, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
 
+    sample_base = None
+    if transfer is not None and initial_guess is not None:
+        # sample amplitudes -> the variable, by the reference's rule for a pulse (core/system_parameters.py: base = arcsin(u / maxA))
+        guess = np.asarray(initial_guess, dtype=np.float64)
+        if guess.shape != (len(Hops), transfer.n_samples):
+            raise ValueError('Grape: with a transfer function the initial guess is (%d, %d) sample amplitudes, got %s'
+                             % (len(Hops), transfer.n_samples, guess.shape))
+        ratio = guess / np.asarray(maxAmp, dtype=np.float64)[:, None]
+        for row in range(len(ratio)):
+            if max(ratio[row]) > 1.0:
+                raise ValueError('Initial guess has strength > max_amp for op %d' % (row))
+        sample_base = np.arcsin(ratio)
+
     sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
-                                maxAmp, draw, initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
+                                maxAmp, draw, None if transfer is not None else initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
                                 reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, sparse_H, sparse_U,
                                 sparse_K)
     # plan_seeds (extension): the batch size the engine plans its path / kernels / chunking for instead of `restarts` (None: its own batch,
     # the fastest choice for this process).  GrapeSharded passes hip_engine.plan_seeds_for(all restarts), so that a restart evolves
     # bit-identically under any rank count; Grape(restarts=R, plan_seeds=hip_engine.plan_seeds_for(R)) reproduces a sharded run in one process.
     # time_comm (extension): a hip_engine.QocComm whose ranks share ONE large trajectory along the time axis (GrapeTimeSharded below)
+    if transfer is not None:
+        # the variable is k x P; drawn after SystemParameters' own draw, so that calls without a transfer keep their RNG stream
+        P = transfer.n_samples
+        if sample_base is None:
+            sample_base = np.random.normal(0, 1. / np.sqrt(P), [len(Hops), P])
+        sys_para.ops_weight_base = sample_base
+        sys_para.raw_shape = np.shape(sample_base)
     tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
-                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust)   # constants -> HBM
+                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust,
+                   transfer=None if transfer is None else transfer.matrix)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
         SS = run_session(tfs, graph, conv, sys_para, method, show_plots=sys_para.show_plots, use_gpu=use_gpu)
+        if transfer is not None:
+            transfer.samples = np.array(SS.samples)
         if save:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -177,6 +216,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
     if kwargs.get('robust') is not None:
         # (before any rank builds an engine: every rank raises alike)
         raise ValueError('GrapeSharded: robust ensembles are not supported; run Grape(robust=..., restarts=R) on one GPU')
+    if kwargs.get('transfer') is not None:
+        raise ValueError('GrapeSharded: transfer functions are not supported; run Grape(transfer=..., restarts=R) on one GPU')
     if comm is not None:
         world, rank = comm.world, comm.rank
     elif dist is not None:
