@@ -97,7 +97,13 @@ typedef struct qoc_config {
                                  * main_grape/grape.py:106-109) */
     int32_t time_rank;          /* this engine's rank 0 .. time_shards - 1 (give it its communicator: qoc_set_time_comm), or -1: all
                                  * ranks emulated inside this one engine on one GPU (how the decomposition is tested) */
-    int32_t reserved[3];
+    int32_t gradient;           /* 0: the reference's first-order GRAPE gradient dK_t/du_k ~ H_k' K_t (the default); 1: the exact gradient -- the
+                                 * derivative of the slice propagators the engine computes, Taylor truncation and squarings included, so that
+                                 * value and gradient belong to the same function (what a line search assumes; it matters for few, long
+                                 * slices).  Costates, regularisers, chain rule, Adam tail and stop rule are unchanged.  Runs on the generic
+                                 * path (AUTO resolves to it); QOC_ERR_INVALID with any other explicit path or time_shards > 0, and for
+                                 * taylor_terms > 60 or scaling > 12 (csrc/qoc_exact_grad.h) */
+    int32_t reserved[2];
 } qoc_config;
 
 /* Adam loop hyper-parameters == Convergence (core/convergence.py:16-49). */
@@ -132,7 +138,7 @@ int qoc_destroy(qoc_handle h);
  * the regularisers and the control set's pulse.  Per control set:
  *   loss      = sum_e weights[e] loss_e         (the value the stop rule tests)
  *   reg_loss  = loss + sum_e weights[e] (forbidden levels + speed_up)_e + the pulse regularisers of the shared pulse (counted once)
- *   grad      = d reg_loss / d base             (the members' first-order GRAPE gradients, weighted)
+ *   grad      = d reg_loss / d base             (the members' gradients, weighted: first-order GRAPE, or exact with qoc_config.gradient = 1)
  *   unitary_scale = sum_e weights[e] unitary_scale_e;  grad_squared = sum grad^2 / 2 of that gradient
  * With sum weights = 1 these are the weighted means of the members' own values.  The engine runs n_seeds x members trajectories of k + q
  * controls (trajectory (g, e) = g * members + e; a perturbation is a frozen control row) and one Adam variable per control set.
@@ -191,7 +197,8 @@ int qoc_get_base(qoc_handle h, double* base);
 /* ---- one evaluation == session.run([grad_pack, loss, reg_loss, unitary_scale, grad_squared])
  * (run_session.py:53-54 and get_error :119-127).  Arrays are [n_seeds]; grad is [n_seeds][k][steps] =
  * d reg_loss / d ops_weight_base with the reference's first-order GRAPE gradient (tensorflow_state.py:49-65,
- * 100-133); any output pointer may be NULL. */
+ * 100-133) -- or, on an engine created with qoc_config.gradient = 1, with the exact derivative of the computed slice
+ * propagators in its place; any output pointer may be NULL. */
 int qoc_eval(qoc_handle h, double* loss, double* reg_loss, double* grad_squared, double* unitary_scale,
              double* grad);
 

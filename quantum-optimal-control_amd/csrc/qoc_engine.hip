@@ -26,6 +26,7 @@
 #include "qoc_small.h"
 #include "qoc_ensemble.h"
 #include "qoc_transfer.h"
+#include "qoc_exact_grad.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
 // (QOC_PLAN_LAT_WORK = 4608 seeds x time slices: since the batch sweeps take their chunk boundaries and final_state from k_mfma_bnd_scan
@@ -94,6 +95,8 @@ struct qoc_engine {
     // control in place of the time slices) and whose glue kernels apply the response matrix
     bool shaped = false;
     QocShape sh{};
+    // exact gradient (qoc_config.gradient = 1, csrc/qoc_exact_grad.h): the generic path's forward, a costate-storing sweep and k_exact_grad
+    QocExact xg{};
 };
 
 // the view that holds the control sets: the engine itself, or the group view of an ensemble engine
@@ -379,7 +382,8 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         TRY(prof_end(e));
         hipLaunchKernelGGL(k_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
         launch_loss(d, e->stream);
-        hipLaunchKernelGGL(k_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
+        if (e->xg.on) qoc_exact_backward(e->xg, d, e->K, nullptr, e->stream);
+        else hipLaunchKernelGGL(k_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
     } else if (e->path == QOC_PATH_ST_FUSED) {
         TRY(prof_begin(e));
         st_fused_launch(d, e->stream, true);
@@ -391,7 +395,8 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         hipLaunchKernelGGL(k_st_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
         TRY(prof_end(e));
         launch_loss(d, e->stream);
-        hipLaunchKernelGGL(k_st_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
+        if (e->xg.on) qoc_exact_backward(e->xg, d, nullptr, e->seed_scratch, e->stream);
+        else hipLaunchKernelGGL(k_st_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
     }
     // an ensemble: the members' gradients and losses, weighted, into the group view
     if (ens && !(skip & 32)) {
@@ -573,6 +578,15 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
     for (int f = 0; f < cfg->n_forbidden; ++f)
         if (forbidden_states[f] < 0 || forbidden_states[f] >= cfg->n)
             return fail(QOC_ERR_INVALID, "qoc_create: forbidden state %d out of range", forbidden_states[f]);
+    if (cfg->gradient != 0 && cfg->gradient != 1)
+        return fail(QOC_ERR_INVALID, "qoc_create: gradient = %d (0 = first-order, the reference's; 1 = exact gradient)", cfg->gradient);
+    if (cfg->gradient == 1) {
+        // the exact gradient runs behind the generic path's forward (csrc/qoc_exact_grad.h); the other paths keep K_t in layouts of their own
+        if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_GENERIC)
+            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient runs on the generic path (QOC_PATH_GENERIC or AUTO), not on path %d", cfg->path);
+        if (cfg->time_shards > 0)
+            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+    }
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0)
@@ -798,7 +812,8 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
     // (QOC_EXPERIMENTAL=1 QOC_SMALL_AUTO=0: AUTO as it was before round 6, for A/B runs -- tools/small_n_latency.py)
     if (!ens && cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && cfg->chunks == 0 && cfg->time_shards < 1 && !qoc_exp_is("QOC_SMALL_AUTO", 0) && qoc_small_auto(d, antiherm))
         path = QOC_PATH_SMALL;
-    if (d.Bplan < B) {
+    if (cfg->gradient == 1) path = QOC_PATH_GENERIC;             // (whatever AUTO's table says: the exact gradient has one home)
+    if (d.Bplan < B && cfg->gradient != 1) {
         // a plan for FEWER control sets than the engine holds is legal (a rank that holds several shards of a planned batch keeps
         // bit-identity with them) but can cost a factor: say so once when it changes what AUTO would have picked for the resident batch
         const AutoPlan own = plan_for(B);
@@ -889,6 +904,13 @@ static int create_engine(const qoc_config* cfg, const double* Hs, const double* 
         ALLOC(e->seed_scratch, (size_t)B * (2 * nn + 2 * nm));
     } else if (path == QOC_PATH_GENERIC) {
         ALLOC(e->seed_scratch, (size_t)B * (nn + 3 * nm));
+    }
+    if (cfg->gradient == 1) {
+        if (const char* why = qoc_exact_plan(e->xg, d)) return bail(fail(QOC_ERR_INVALID, "qoc_create: %s (T=%d s=%d)", why, d.T, d.s));
+        ALLOC(e->xg.Lam, (size_t)B * steps * nm);
+        ALLOC(e->xg.scratch, (size_t)e->xg.grid * e->xg.per_wg);
+        if (qoc_exact_lds_opt_in(e->xg) != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create: cannot reserve %zu bytes of LDS for the exact gradient kernel",
+            e->xg.lds_bytes));
     }
     if (ens) {
         // the group view: the caller's G control sets of k controls -- variable, Adam slots, stop rule, pulse regularisers, the tail's arrays
@@ -1344,10 +1366,10 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 // sweeps=<downup|split|row_tile_gradient|latency|latency_sources|one_wave>
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
-// and on every path tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
+// on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
-    char tmp[256];
+    char tmp[384];
     if (e->path == QOC_PATH_MFMA) {
         const QocMfma& mf = e->mf;
         const bool split = (mf.NT > 2 || (mf.NT == 2 && e->d.k >= 6)) && mf.variant != 1;
@@ -1388,6 +1410,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     // ensemble engines only (the plain engines' line stays as it was)
     if (e->ens_E) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " members=%d perturbations=%d", e->ens_E, e->en.q); }
     if (e->shaped) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " samples=%d band=%d", e->sh.P, e->sh.band); }
+    { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " gradient=%s", e->xg.on ? "exact" : "first_order"); }
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }

@@ -20,6 +20,9 @@ class Convergence(object):
         self.time_unit = time_unit
         for key, default in DEFAULTS:
             setattr(self, key, convergence[key] if key in convergence else default)
+        # extension, L-BFGS-B only: scipy's relative-reduction stop (absent: scipy's own default, as the reference); 0 switches it off, so that
+        # only conv_target, min_grad and max_iterations end the run
+        self.ftol = convergence['ftol'] if 'ftol' in convergence else None
         self.reset_convergence()
 
     def reset_convergence(self):

@@ -26,7 +26,8 @@ class QocConfig(C.Structure):
                 ('c_d2wdt2', C.c_double), ('c_speed_up', C.c_double), ('c_bandpass', C.c_double),
                 ('band_lo', C.c_int32), ('band_hi', C.c_int32), ('n_forbidden', C.c_int32),
                 ('forbid_dressed', C.c_int32), ('device', C.c_int32), ('path', C.c_int32), ('chunks', C.c_int32),
-                ('variant', C.c_int32), ('plan_seeds', C.c_int32), ('time_shards', C.c_int32), ('time_rank', C.c_int32), ('reserved', C.c_int32 * 3)]
+                ('variant', C.c_int32), ('plan_seeds', C.c_int32), ('time_shards', C.c_int32), ('time_rank', C.c_int32), ('gradient', C.c_int32),
+                ('reserved', C.c_int32 * 2)]
 
 
 class QocEnsemble(C.Structure):
@@ -293,11 +294,15 @@ class HipEngine(object):
 
     transfer (transfer-function GRAPE, include/qoc.h qoc_create_shaped): a real steps x P response matrix.  The variable, the gradient and
     get_uks are then (n_seeds, k, P) -- the AWG's samples --, get_pulse() gives the (n_seeds, k, steps) pulse the trajectories ran on, and the
-    pulse regularisers act on the samples.  Composes with ensemble."""
+    pulse regularisers act on the samples.  Composes with ensemble.
+
+    exact_gradient (include/qoc.h qoc_config.gradient): False = the reference's first-order GRAPE gradient; True = the derivative of the slice
+    propagators the engine computes (truncated Taylor series and squarings), so that loss and gradient belong to one function.  Generic path
+    only (AUTO resolves to it; any other explicit path and time sharding raise QocError).  Composes with ensemble and transfer."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
-                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None):
+                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False):
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
@@ -329,6 +334,8 @@ class HipEngine(object):
         cfg.forbid_dressed = int(use_vs)
         cfg.device, cfg.path, cfg.chunks, cfg.variant = int(device), int(path), int(chunks), int(variant)
         cfg.time_shards, cfg.time_rank = int(time_shards), int(time_rank)     # one trajectory sharded along the time axis (csrc/qoc_gemm_ts.h); -1: emulated in this engine
+        cfg.gradient = int(bool(exact_gradient))
+        self.exact_gradient = bool(exact_gradient)
         cfg.plan_seeds = int(plan_seeds)       # 0: plan for n_seeds; > 0: the batch AUTO plans for (sharded restarts: see plan_seeds_for)
         omg = None
         if one_minus_gauss is not None:
@@ -365,8 +372,8 @@ class HipEngine(object):
             self.members = int(ens.members)
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
-        buf = C.create_string_buffer(256)
-        _check(lib.qoc_plan_describe(self._h, buf, 256))
+        buf = C.create_string_buffer(512)
+        _check(lib.qoc_plan_describe(self._h, buf, 512))
         self.plan = dict(kv.split('=', 1) for kv in buf.value.decode().split())
         if time_comm is not None:
             _check(lib.qoc_set_time_comm(self._h, time_comm._h))

@@ -199,6 +199,8 @@ class run_session(object):
         x0 = np.reshape(self.sys_para.ops_weight_base, -1)
         if method == 'L-BFGS-B':
             options = {'maxfun': self.conv.max_iterations, 'gtol': self.conv.min_grad, 'disp': False, 'maxls': 40}
+            if getattr(self.conv, 'ftol', None) is not None:
+                options['ftol'] = float(self.conv.ftol)
         else:
             options = {'gtol': self.conv.min_grad, 'disp': False, 'maxiter': self.conv.max_iterations}
         res = minimize(self.minimize_opt_fun, x0, method=method, jac=jac, options=options)

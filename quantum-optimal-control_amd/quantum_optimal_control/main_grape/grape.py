@@ -52,7 +52,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, _first_seed=0, _device=0, _return_session=False):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, _first_seed=0, _device=0, _return_session=False):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -65,9 +65,16 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``transfer`` (transfer-function GRAPE): a helper_functions.transfer.Transfer (or a steps x P matrix): the variable is then the k x P
     samples an AWG plays, and the pulse the Hamiltonian sees is their response ``samples @ T.T``.  ``initial_guess`` is k x P sample
     amplitudes; the returned uks is the k x steps pulse, ``transfer.samples`` the k x P samples behind it.  The pulse regularisers
-    (amplitude, dwdt, d2wdt2, bandpass) act on the samples; ``envelope`` is rejected.  Composes with ``robust``."""
+    (amplitude, dwdt, d2wdt2, bandpass) act on the samples; ``envelope`` is rejected.  Composes with ``robust``.
+
+    ``exact_gradient`` (default False: the reference's first-order GRAPE gradient): True differentiates the slice propagators the engine
+    computes -- truncated Taylor series and squarings included -- so that the loss and the gradient a driver sees belong to one function.
+    It pays for few, long slices and for the scipy drivers, whose line searches assume exactly that; it costs more per evaluation
+    (DESIGN.md).  Works with every ``method``, with ``restarts``, ``robust``, ``transfer`` and GrapeSharded; not with ``time_comm``."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
+    if exact_gradient and time_comm is not None:
+        raise ValueError('Grape: the exact gradient cannot be time-sharded (time_comm)')
     if robust is not None:
         from quantum_optimal_control.helper_functions import robust as _robust
         if time_comm is not None:
@@ -104,6 +111,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
                 hf.add('transfer_matrix', data=transfer.matrix)
+        if exact_gradient:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                hf.add('exact_gradient', data=np.array(1))
 
     if U0 is None:
         U0 = np.identity(len(H0))
@@ -152,7 +163,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         sys_para.raw_shape = np.shape(sample_base)
     tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
                    plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust,
-                   transfer=None if transfer is None else transfer.matrix)   # constants -> HBM
+                   transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient))   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
