@@ -13,7 +13,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "qoc_common.h"
@@ -44,12 +46,14 @@ static int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail(QOC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                              \
+#define HIP_TRY(expr)                                                                                                               \
+    do {                                                                                                                            \
+        hipError_t e_ = (expr);                                                                                                     \
+        if (e_ != hipSuccess) return fail(QOC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);  \
     } while (0)
+
+#define HIP_TRY_MSG(expr, ...) do { if ((expr) != hipSuccess) return fail(QOC_ERR_HIP, __VA_ARGS__); } while (0)
+#define TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 struct qoc_engine {
     qoc_config cfg;
@@ -101,6 +105,11 @@ struct qoc_engine {
 
 // the view that holds the control sets: the engine itself, or the group view of an ensemble engine
 static inline QocDev& sets(qoc_engine* e) { return e->ens_E ? e->g : e->d; }
+static inline const QocDev& sets(const qoc_engine* e) { return e->ens_E ? e->g : e->d; }
+// a grid of one workgroup per `per_block` items, at most `cap` workgroups (the kernels stride over the rest)
+static inline unsigned grid_for(size_t items, unsigned per_block, unsigned cap) {
+    return (unsigned)std::min<size_t>((items + per_block - 1) / per_block, cap);
+}
 
 template <typename T>
 static int dev_alloc(qoc_engine* e, T** p, size_t count) {
@@ -122,21 +131,21 @@ static int dev_alloc(qoc_engine* e, T** p, size_t count) {
     return QOC_OK;
 }
 
+// ... cleared (`who`: the entry point that the message names)
+template <typename T>
+static int dev_zalloc(qoc_engine* e, T** p, size_t count, const char* who) {
+    TRY(dev_alloc(e, p, count));
+    HIP_TRY_MSG(hipMemset(*p, 0, count * sizeof(T)), "%s: clearing the state buffers failed", who);
+    return QOC_OK;
+}
 template <typename T>
 static int dev_upload(qoc_engine* e, const T** p, const T* host, size_t count) {
     T* q = nullptr;
-    int rc = dev_alloc(e, &q, count);
-    if (rc) return rc;
+    TRY(dev_alloc(e, &q, count));
     HIP_TRY(hipMemcpy(q, host, count * sizeof(T), hipMemcpyHostToDevice));
     *p = q;
     return QOC_OK;
 }
-
-#define TRY(expr)          \
-    do {                   \
-        int rc_ = (expr);  \
-        if (rc_) return rc_; \
-    } while (0)
 
 static int prof_begin(qoc_engine* e) {
     if (!e->profiling) return QOC_OK;
@@ -245,16 +254,14 @@ __global__ void __launch_bounds__(256) k_band_gradient(QocDev d) {
 
 // k_loss, preceded by what it needs per time point: the dressed-basis amplitudes of the forbidden levels, the overlaps of speed_up
 static inline void launch_loss(const QocDev& d, hipStream_t s) {
-    if (d.n_forb > 0) {
-        const size_t total = (size_t)d.B * (d.steps + 1) * d.n_forb * d.m;
-        size_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(k_dress_amplitudes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d);
-    }
-    if (d.has_speed) {
-        const size_t g = ((size_t)d.B * (d.steps + 1) + 3) / 4;
-        hipLaunchKernelGGL(k_time_overlaps, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d);
-    }
+    if (d.n_forb > 0)
+        hipLaunchKernelGGL(k_dress_amplitudes, dim3(grid_for((size_t)d.B * (d.steps + 1) * d.n_forb * d.m, 256, 4096)), dim3(256), 0, s, d);
+    if (d.has_speed) hipLaunchKernelGGL(k_time_overlaps, dim3(grid_for((size_t)d.B * (d.steps + 1), 4, 4096)), dim3(256), 0, s, d);
     hipLaunchKernelGGL(k_loss, dim3(d.B), dim3(QOC_BLOCK), 0, s, d);
+}
+// u / w = maxA sin(base) of every control set of the view
+static inline void launch_controls(const QocDev& v, hipStream_t s) {
+    hipLaunchKernelGGL(k_controls, dim3(grid_for((size_t)v.B * v.k * v.steps, QOC_BLOCK, 2048)), dim3(QOC_BLOCK), 0, s, v);
 }
 
 // workgroup-resident path: ONE launch runs `iters` loop iterations (or one evaluation / explicit step)
@@ -286,7 +293,7 @@ enum TailKind {
 };
 
 static TailKind tail_kind(const qoc_engine* e) {
-    const QocDev& d = e->ens_E ? e->g : e->d;
+    const QocDev& d = sets(e);
     const int ks = d.k * d.steps;
     // an ensemble runs the stand-alone tails on its group view: never on one of the paths with a tail of their own, and its gradient is a
     // plain array (k_ens_reduce), never the persistent chains' partials
@@ -299,50 +306,27 @@ static TailKind tail_kind(const qoc_engine* e) {
     return ks <= 8 * 1024 && ks > 4 * 1024 ? TAIL_FINISH8 : TAIL_FINISH4;
 }
 
-static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
-    if (e->path == QOC_PATH_SMALL) return enqueue_small(e, ap, 1);
-    const TailKind tail = tail_kind(e);
-    // the slice kernel of the n <= 32 latency mode forms its own controls; everybody else reads u / w: from k_controls, or -- when the Adam
-    // tail of the previous iteration (or qoc_get_uks) has left them in u2 / w2 -- by swapping the two pairs (one launch less per iteration)
-    const bool own_controls = e->path == QOC_PATH_MFMA && e->mf.latency && e->mf.NT == 2;
-    const bool swap_in = e->controls_ready && !own_controls && !(e->skip_mask & 1);
-    const bool ens = e->ens_E > 0;
-    QocDev& cv = sets(e);                    // (an ensemble: the group view holds the controls of the control sets)
-    if (swap_in) { std::swap(cv.u, cv.u2); std::swap(cv.w, cv.w2); }
-    e->controls_ready = false;
-    QocDev d = e->d;
-    if (own_controls) { d.u2 = nullptr; d.w2 = nullptr; }
-    d.skip_done = ap.mode == 1 ? 1 : 0;      // qoc_eval / explicit steps always evaluate every seed
-    QocDev gd = e->g;
-    gd.skip_done = d.skip_done;
-    d.uscale_in_loss = (e->path == QOC_PATH_MFMA && !e->mf.latency && !e->mf.updown) ? 1 : 0;
-    const int total = d.B * d.k * d.steps;
-    int cgrid = (total + QOC_BLOCK - 1) / QOC_BLOCK;
-    if (cgrid > 2048) cgrid = 2048;
-    const int skip = e->skip_mask;
-    const QocDev& td = ens ? gd : d;        // the view the tail runs on
-    const bool plain = !(td.has_amp || td.has_env || td.has_dwdt || td.has_d2wdt2 || td.has_band);
-    // latency mode: the tail of the iteration runs in the last workgroup of the gradient kernel
-    // (with the local pulse regularisers too -- amplitude, envelope, dwdt, d2wdt2; the bandpass DFT keeps its own launch)
-    const bool fused_tail = tail == TAIL_LATENCY_FUSED;
-    // (latency mode of the MFMA path: the slice kernel of the exponentials forms its own controls)
-    if (ens) {
+// ---- the four stages of enqueue_iteration, in launch order, on this iteration's copies d (trajectories) and gd (groups of an ensemble)
+// 1. controls.  All read u / w: from k_controls, or -- swap_in: the Adam tail of the previous iteration (or qoc_get_uks) left them in
+// u2 / w2 -- from no launch at all: enqueue_iteration has swapped the two pairs (in the engine's own views, so before it took the copies d
+// and gd that the stages share).  own_controls: the slice kernel of the n <= 32 latency mode forms its own
+static void enqueue_controls(const qoc_engine* e, const QocDev& d, const QocDev& gd, bool own_controls, bool swap_in) {
+    const dim3 eg(grid_for((size_t)gd.B * d.k * d.steps, QOC_BLOCK, 2048));        // (ensembles: a thread per member's control)
+    if (e->skip_mask & 1) return;
+    if (!e->ens_E) {
+        if (!own_controls && !swap_in) launch_controls(d, e->stream);
+    } else if (!e->shaped) {
         // every member's controls from its group's (formed from the variable unless the last tail left them), and the done flags
-        const size_t items = (size_t)gd.B * d.k * d.steps;
-        size_t eg = (items + QOC_BLOCK - 1) / QOC_BLOCK;
-        if (eg > 2048) eg = 2048;
-        if (!(skip & 1) && !e->shaped) hipLaunchKernelGGL(k_ens_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
-        else if (!(skip & 1)) {
-            // a pulse response: the samples w_s / u_s from the variable (unless the last tail left them), then the pulse through the response
-            if (!swap_in) {
-                const size_t sitems = (size_t)gd.B * gd.k * gd.steps;
-                size_t sg = (sitems + QOC_BLOCK - 1) / QOC_BLOCK;
-                if (sg > 2048) sg = 2048;
-                hipLaunchKernelGGL(k_controls, dim3((unsigned)sg), dim3(QOC_BLOCK), 0, e->stream, gd);
-            }
-            hipLaunchKernelGGL(k_shape_expand, dim3((unsigned)eg), dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
-        }
-    } else if (!(skip & 1) && !own_controls && !swap_in) hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, d);
+        hipLaunchKernelGGL(k_ens_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+    } else {
+        // a pulse response: the samples w_s / u_s from the variable (unless the last tail left them), then the pulse through the response
+        if (!swap_in) launch_controls(gd, e->stream);
+        hipLaunchKernelGGL(k_shape_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
+    }
+}
+// 2. trajectories: exponentials, forward, loss, backward of the engine's path; qoc_profile_read's hipEvent bracket around the dominant one
+static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev& ap, bool fused_tail) {
+    const int skip = e->skip_mask;
     if (e->path == QOC_PATH_MFMA) {
         TRY(prof_begin(e));
         if (!(skip & 2)) qoc_mfma_launch_expm(e->mf, d, e->stream);
@@ -356,16 +340,14 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
             if (fused_tail) qoc_mfma_latency_gradient(e->mf, d, &ap, e->stream);
             else qoc_mfma_launch_backward(e->mf, d, e->stream);
         }
+    } else if (e->path == QOC_PATH_GEMM && e->gm.ts_G > 0) {            // one trajectory sharded along the time axis (qoc_gemm_ts.h)
+        const int rc = qoc_gemm_ts_evaluate(e->gm, d, e->stream, [&]() { launch_loss(d, e->stream); }, [&]() { return prof_begin(e); },
+            [&]() { return prof_end(e); });
+        if (rc == 1) return fail(QOC_ERR_HIP, "time-sharded iteration: clearing the gradient array failed");
+        if (rc) return rc;                                              // (the message is the collective's / the profiler's)
     } else if (e->path == QOC_PATH_GEMM) {
-        if (e->gm.ts_G > 0) {                                           // one trajectory sharded along the time axis (qoc_gemm_ts.h)
-            const int rc = qoc_gemm_ts_evaluate(e->gm, d, e->stream, [&]() { launch_loss(d, e->stream); }, [&]() { return prof_begin(e); },
-                [&]() { return prof_end(e); });
-            if (rc == 1) return fail(QOC_ERR_HIP, "time-sharded iteration: clearing the gradient array failed");
-            if (rc) return rc;                                          // (the message is the collective's / the profiler's)
-        } else {
-        // the hipEvent bracket of qoc_profile_read: the exponentials -- or, on the direct state-transfer route (no exponentials: the
-        // assembly of the generators is all qoc_gemm_expm does there), the backward half of the iteration, which the backward Taylor chain
-        // dominates
+        // the bracket: the exponentials -- or, on the direct state-transfer route (no exponentials: the assembly of the generators is all
+        // qoc_gemm_expm does there), the backward half of the iteration, which the backward Taylor chain dominates
         const bool bracket_bwd = e->gm.direct;
         if (!bracket_bwd) TRY(prof_begin(e));
         qoc_gemm_expm(e->gm, d, e->stream);
@@ -375,66 +357,87 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
         if (bracket_bwd) TRY(prof_begin(e));
         qoc_gemm_backward(e->gm, d, e->stream);
         if (bracket_bwd) TRY(prof_end(e));
-        }
-    } else if (!d.state_transfer) {
-        TRY(prof_begin(e));
-        hipLaunchKernelGGL(k_expm_generic, dim3(e->expm_grid), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->expm_scratch);
-        TRY(prof_end(e));
-        hipLaunchKernelGGL(k_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
-        launch_loss(d, e->stream);
-        if (e->xg.on) qoc_exact_backward(e->xg, d, e->K, nullptr, e->stream);
-        else hipLaunchKernelGGL(k_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
     } else if (e->path == QOC_PATH_ST_FUSED) {
         TRY(prof_begin(e));
         st_fused_launch(d, e->stream, true);
         TRY(prof_end(e));
         launch_loss(d, e->stream);
         st_fused_launch(d, e->stream, false);
-    } else {
+    } else {                                            // the any-size kernels; state transfer: no propagators, one sweep each way
+        const bool st = d.state_transfer;
         TRY(prof_begin(e));
-        hipLaunchKernelGGL(k_st_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
+        if (st) hipLaunchKernelGGL(k_st_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
+        else hipLaunchKernelGGL(k_expm_generic, dim3(e->expm_grid), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->expm_scratch);
         TRY(prof_end(e));
+        if (!st) hipLaunchKernelGGL(k_fwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
         launch_loss(d, e->stream);
-        if (e->xg.on) qoc_exact_backward(e->xg, d, nullptr, e->seed_scratch, e->stream);
-        else hipLaunchKernelGGL(k_st_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
+        if (e->xg.on) qoc_exact_backward(e->xg, d, st ? nullptr : e->K, st ? e->seed_scratch : nullptr, e->stream);
+        else if (st) hipLaunchKernelGGL(k_st_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->seed_scratch);
+        else hipLaunchKernelGGL(k_bwd_generic, dim3(d.B), dim3(QOC_BLOCK), 0, e->stream, d, e->K, e->seed_scratch);
     }
-    // an ensemble: the members' gradients and losses, weighted, into the group view
-    if (ens && !(skip & 32)) {
-        const int ks = gd.k * gd.steps;
-        if (!e->shaped) hipLaunchKernelGGL(k_ens_reduce, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en);
-        else if (e->sh.col_band <= QOC_SHAPE_WAVE_FROM)
-            hipLaunchKernelGGL(k_shape_reduce<1>, dim3((unsigned)((ks + 255) / 256), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en, e->sh);
-        else hipLaunchKernelGGL(k_shape_reduce<64>, dim3((unsigned)((ks + 3) / 4), (unsigned)gd.B), dim3(256), 0, e->stream, d, gd, e->en, e->sh);
+    return QOC_OK;
+}
+// 3. an ensemble: the members' gradients and losses, weighted, into the group view
+static void enqueue_ens_reduce(const qoc_engine* e, const QocDev& d, const QocDev& gd) {
+    const int ks = gd.k * gd.steps;
+    const dim3 per_thread((unsigned)((ks + 255) / 256), (unsigned)gd.B), per_wave((unsigned)((ks + 3) / 4), (unsigned)gd.B);
+    if (!e->shaped) hipLaunchKernelGGL(k_ens_reduce, per_thread, dim3(256), 0, e->stream, d, gd, e->en);
+    else if (e->sh.col_band <= QOC_SHAPE_WAVE_FROM)
+        hipLaunchKernelGGL(k_shape_reduce<1>, per_thread, dim3(256), 0, e->stream, d, gd, e->en, e->sh);
+    else hipLaunchKernelGGL(k_shape_reduce<64>, per_wave, dim3(256), 0, e->stream, d, gd, e->en, e->sh);
+}
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument of what f launches
+template <typename F>
+static inline void with_flag(bool flag, F&& f) { flag ? f(std::true_type{}) : f(std::false_type{}); }
+// 4. the tail on the view td that holds the control sets (the latency mode's fused tail runs in the last workgroup of its gradient kernel
+// instead, with the local pulse regularisers too -- amplitude, envelope, dwdt, d2wdt2; the bandpass DFT keeps its own launches)
+static void enqueue_tail(const qoc_engine* e, const QocDev& td, const QocAdamDev& ap, TailKind tail) {
+    if (td.has_band) {
+        const size_t items = (size_t)td.B * td.k * td.steps;
+        hipLaunchKernelGGL(k_band_spectrum, dim3(grid_for(items, 4, 8192)), dim3(256), 0, e->stream, td);
+        hipLaunchKernelGGL(k_band_gradient, dim3(grid_for(items, 256, 8192)), dim3(256), 0, e->stream, td);
     }
-    if (!(skip & 32) && !fused_tail) {
-        const dim3 fb(td.k * td.steps >= 2048 ? 1024 : QOC_BLOCK);
-        if (td.has_band) {
-            const size_t items = (size_t)td.B * td.k * td.steps, g1 = (items + 3) / 4, g2 = (items + 255) / 256;
-            hipLaunchKernelGGL(k_band_spectrum, dim3((unsigned)(g1 > 8192 ? 8192 : g1)), dim3(256), 0, e->stream, td);
-            hipLaunchKernelGGL(k_band_gradient, dim3((unsigned)(g2 > 8192 ? 8192 : g2)), dim3(256), 0, e->stream, td);
-        }
-        // seeds of 4097 .. 8192 (k, t) elements (C3: 6 x 1000) keep their Adam slots in registers too: eight elements per thread
-        // ... or, since round 6, spread over fin_S workgroups in two launches: one control set of 6000 elements is bound by the fp64 sin / cos / sqrt / divide of the
-        // ONE compute unit k_finish_t runs it on (C3, one trajectory: 32.5 us; profiles/r06_kernel_stats_c3_single_trajectory.txt)
-        const bool wide = tail == TAIL_FINISH8;
+    const bool plain = !(td.has_amp || td.has_env || td.has_dwdt || td.has_d2wdt2 || td.has_band);
+    with_flag(plain, [&](auto plain_c) {
+        constexpr bool PLAIN = decltype(plain_c)::value;
+        // control sets of 4097 .. 8192 (k, t) elements (C3: 6 x 1000) over fin_S workgroups in two launches: one set of 6000 elements
+        // is bound by the fp64 sin / cos / sqrt / divide of the ONE compute unit k_finish_t runs it on (C3, one trajectory: 32.5 us;
+        // profiles/r06_kernel_stats_c3_single_trajectory.txt)
         if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS) {
             const dim3 sg((unsigned)e->fin_S, (unsigned)td.B);
-            // (GEMM path, persistent chains: the wide gradient product left per-tile partial dots -- qoc_gemm_backward skipped its reduce launch, part A sums them)
+            // (GEMM path, persistent chains: the wide gradient product left per-tile partial dots -- qoc_gemm_backward skipped its reduce
+            // launch, part A sums them)
             QocGradPartial gp{nullptr, 0, 0, 0};
             if (tail == TAIL_SPLIT_PARTIALS) gp = QocGradPartial{e->gm.partial, e->gm.N / 32, e->gm.ldW, e->gm.MV};
-            if (plain) {
-                hipLaunchKernelGGL(k_finish_split_a<true>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part, gp);
-                hipLaunchKernelGGL(k_finish_split_b<true>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part);
-            } else {
-                hipLaunchKernelGGL(k_finish_split_a<false>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part, gp);
-                hipLaunchKernelGGL(k_finish_split_b<false>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part);
-            }
-        }
-        else if (plain && wide) hipLaunchKernelGGL((k_finish_t<true, 8>), dim3(td.B), fb, 0, e->stream, td, ap);
-        else if (plain) hipLaunchKernelGGL(k_finish_t<true>, dim3(td.B), fb, 0, e->stream, td, ap);
-        else if (wide) hipLaunchKernelGGL((k_finish_t<false, 8>), dim3(td.B), fb, 0, e->stream, td, ap);
-        else hipLaunchKernelGGL(k_finish_t<false>, dim3(td.B), fb, 0, e->stream, td, ap);
-    }
+            hipLaunchKernelGGL(k_finish_split_a<PLAIN>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part, gp);
+            hipLaunchKernelGGL(k_finish_split_b<PLAIN>, sg, dim3(256), 0, e->stream, td, ap, e->fin_part);
+        } else with_flag(tail == TAIL_FINISH8, [&](auto wide_c) {   // ... or their Adam slots in registers too: eight elements per thread
+            const dim3 fb(td.k * td.steps >= 2048 ? 1024 : QOC_BLOCK);
+            hipLaunchKernelGGL((k_finish_t<PLAIN, decltype(wide_c)::value ? 8 : QF_E>), dim3(td.B), fb, 0, e->stream, td, ap);
+        });
+    });
+}
+
+static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
+    if (e->path == QOC_PATH_SMALL) return enqueue_small(e, ap, 1);
+    const TailKind tail = tail_kind(e);
+    const int skip = e->skip_mask;
+    const bool own_controls = e->path == QOC_PATH_MFMA && e->mf.latency && e->mf.NT == 2;
+    const bool swap_in = e->controls_ready && !own_controls && !(skip & 1);
+    QocDev& cv = sets(e);                    // (an ensemble: the group view holds the controls of the control sets)
+    if (swap_in) { std::swap(cv.u, cv.u2); std::swap(cv.w, cv.w2); }
+    e->controls_ready = false;
+    QocDev d = e->d;
+    if (own_controls) { d.u2 = nullptr; d.w2 = nullptr; }
+    d.skip_done = ap.mode == 1 ? 1 : 0;      // qoc_eval / explicit steps always evaluate every seed
+    d.uscale_in_loss = (e->path == QOC_PATH_MFMA && !e->mf.latency && !e->mf.updown) ? 1 : 0;
+    QocDev gd = e->g;
+    gd.skip_done = d.skip_done;
+    const bool fused_tail = tail == TAIL_LATENCY_FUSED;
+    enqueue_controls(e, d, gd, own_controls, swap_in);
+    TRY(enqueue_trajectories(e, d, ap, fused_tail));
+    if (e->ens_E && !(skip & 32)) enqueue_ens_reduce(e, d, gd);
+    if (!fused_tail && !(skip & 32)) enqueue_tail(e, e->ens_E ? gd : d, ap, tail);
     HIP_TRY(hipGetLastError());
     e->evaluated = true;
     // the Adam tail ran: u2 / w2 belong to the moved variable
@@ -508,6 +511,441 @@ static QocAdamDev loop_params(const qoc_adam_params* p) {
     return ap;
 }
 
+// the response matrix of qoc_create_shaped as the host prepared it: the transposed copy and the nonzero window of every row and column
+struct ShapeHost {
+    int P, band, col_band;
+    std::vector<double> Tt;          // [P][steps]: T transposed (what the kernels read)
+    std::vector<int2> row_win, col_win;
+};
+
+// what qoc_create_ensemble adds to the trajectory engine it creates: the caller's own configuration (k controls, n_seeds control sets, the
+// pulse regularisers) for the group view, and the member description
+struct EnsArgs {
+    const qoc_config* user;
+    const double* maxA;              // [k]
+    const double* one_minus_gauss;   // [k][steps] or null
+    const qoc_ensemble* ens;
+    const ShapeHost* shape;          // qoc_create_shaped: the response matrix and its windows, else null
+};
+
+// the caller's arrays of qoc_create (include/qoc.h), passed on together
+struct Problem {
+    const double *Hs, *U0, *V, *W, *maxA, *one_minus_gauss; const int32_t* forbidden_states; const double *forbidden_coeffs, *Vs;
+};
+
+static int check_create_args(const qoc_config* cfg, const Problem& p, qoc_handle* out) {
+    if (!cfg || !p.Hs || !p.V || !p.W || !p.maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create: null argument");
+    if (cfg->plan_seeds < 0)
+        return fail(QOC_ERR_INVALID, "qoc_create: plan_seeds = %d (0 = plan for n_seeds, > 0 = the batch AUTO plans for)", cfg->plan_seeds);
+    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->m < 1 || cfg->n_seeds < 1)
+        return fail(QOC_ERR_INVALID, "qoc_create: n, k, steps, m, n_seeds must be >= 1");
+    if (cfg->taylor_terms < 1 || cfg->scaling < 0 || cfg->scaling > 30)
+        return fail(QOC_ERR_INVALID, "qoc_create: bad taylor_terms/scaling (%d, %d)", cfg->taylor_terms, cfg->scaling);
+    if (!cfg->state_transfer && !p.U0) return fail(QOC_ERR_INVALID, "qoc_create: U0 required in unitary mode");
+    if (cfg->n_forbidden < 0) return fail(QOC_ERR_INVALID, "qoc_create: n_forbidden must be >= 0");
+    if (cfg->n_forbidden > 0 && (!p.forbidden_states || !p.forbidden_coeffs))
+        return fail(QOC_ERR_INVALID, "qoc_create: forbidden lists missing");
+    if (cfg->forbid_dressed && cfg->n_forbidden > 0 && !p.Vs) return fail(QOC_ERR_INVALID, "qoc_create: forbid_dressed needs Vs");
+    if (cfg->has_envelope && !p.one_minus_gauss) return fail(QOC_ERR_INVALID, "qoc_create: envelope constant missing");
+    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "qoc_create: d2wdt2 needs dwdt (reference: NameError new_weights)");
+    for (int f = 0; f < cfg->n_forbidden; ++f)
+        if (p.forbidden_states[f] < 0 || p.forbidden_states[f] >= cfg->n)
+            return fail(QOC_ERR_INVALID, "qoc_create: forbidden state %d out of range", p.forbidden_states[f]);
+    if (cfg->gradient != 0 && cfg->gradient != 1)
+        return fail(QOC_ERR_INVALID, "qoc_create: gradient = %d (0 = first-order, the reference's; 1 = exact gradient)", cfg->gradient);
+    if (cfg->gradient == 1) {
+        // the exact gradient runs behind the generic path's forward (csrc/qoc_exact_grad.h); the other paths keep K_t in layouts of their own
+        if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_GENERIC)
+            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient runs on the generic path (QOC_PATH_GENERIC or AUTO), not on path %d", cfg->path);
+        if (cfg->time_shards > 0)
+            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+    }
+    int ndev = 0;
+    const hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || ndev == 0)
+        return fail(QOC_ERR_HIP, "qoc_create: no HIP device visible (%s) -- this engine has no CPU fallback",
+                    de == hipSuccess ? "count = 0" : hipGetErrorString(de));
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(QOC_ERR_INVALID, "qoc_create: device %d of %d", cfg->device, ndev);
+    return QOC_OK;
+}
+
+// the pulse regularisers of a view that holds control sets, per slice (a sample view: per sample) of that view
+static void fill_pulse_regularisers(QocDev& v, const qoc_config& c) {
+    const double inv_steps = 1.0 / (double)v.steps;
+    v.has_amp = c.has_amplitude; v.a_amp = c.c_amplitude * inv_steps;
+    v.has_env = c.has_envelope; v.a_env = c.c_envelope * inv_steps;
+    v.has_dwdt = c.has_dwdt; v.a_dwdt = c.c_dwdt * inv_steps;
+    v.has_d2wdt2 = c.has_d2wdt2; v.a_d2wdt2 = c.c_d2wdt2 * inv_steps;
+    v.has_band = c.has_bandpass; v.a_band = c.c_bandpass * inv_steps;
+    v.band_lo = c.band_lo; v.band_hi = c.band_hi;
+}
+// U0 V (state transfer: V itself): the start vectors of the thin forward recursion
+static std::vector<double> start_vectors(const qoc_config& c, const double* U0, const double* V) {
+    const int n = c.n, m = c.m;
+    std::vector<double> psi0(V, V + 2 * (size_t)n * m);
+    if (c.state_transfer) return psi0;
+    for (int a = 0; a < n; ++a)
+        for (int j = 0; j < m; ++j) {
+            double re = 0, im = 0;
+            for (int l = 0; l < n; ++l) {
+                const double ur = U0[2 * (a * n + l)], ui = U0[2 * (a * n + l) + 1];
+                const double vr = V[2 * (l * m + j)], vi = V[2 * (l * m + j) + 1];
+                re += ur * vr - ui * vi;
+                im += ur * vi + ui * vr;
+            }
+            psi0[2 * (a * m + j)] = re; psi0[2 * (a * m + j) + 1] = im;
+        }
+    return psi0;
+}
+
+// ---- the state of a view that holds control sets: e->d of a plain engine, e->g of an ensemble engine (whose e->d keeps its own, unused by
+// the tail).  Three helpers because a plain engine allocates its trajectory buffers between them, and the arena is a bump allocator whose
+// layout the measurements were taken on.  `who`: the entry point that builds the view.  First the variable, Adam slots, stop rule, controls
+// and gradients, and -- tail_here: the tail runs on this view -- above 4096 (k, t) elements the partials of the split tail over fin_S
+// workgroups per control set (k_finish_split_a / _b; the switch: A/B runs)
+static int alloc_set_arrays(qoc_engine* e, QocDev& v, const char* who, bool tail_here) {
+    const size_t B = (size_t)v.B, ks = (size_t)v.k * v.steps, all = B * ks;
+    for (double** p : {&v.base, &v.adam_m, &v.adam_v}) TRY(dev_zalloc(e, p, all, who));
+    for (int** p : {&v.adam_t, &v.iters, &v.done}) TRY(dev_zalloc(e, p, B, who));
+    for (double** p : {&v.w, &v.u, &v.w2, &v.u2, &v.dLdu, &v.grad}) TRY(dev_alloc(e, p, all));
+    if (!tail_here || ks <= 4 * 1024 || qoc_exp_is("QOC_FINISH_SPLIT", 0)) return QOC_OK;
+    e->fin_S = (int)grid_for(ks, 256, 64);                         // (longer pulses: several elements per thread)
+    return dev_alloc(e, &e->fin_part, B * (e->fin_S + 2) * 2);
+}
+// the scalars of every control set and the arrays of the bandpass regulariser with its phase table (no_table: the message without one)
+static int alloc_set_scalars(qoc_engine* e, QocDev& v, const char* who, const char* no_table) {
+    const size_t B = (size_t)v.B, all = B * v.k * v.steps;
+    for (double** p : {&v.loss, &v.reg_state, &v.reg_loss, &v.g2}) TRY(dev_alloc(e, p, B));
+    TRY(dev_zalloc(e, &v.uscale, B, who));
+    if (!v.has_band) return QOC_OK;
+    TRY(dev_alloc(e, &v.band_ph, all)); TRY(dev_alloc(e, &v.band_tw, (size_t)v.steps));
+    TRY(dev_alloc(e, &v.band_mag, all)); TRY(dev_alloc(e, &v.band_dR, all));
+    hipLaunchKernelGGL(k_band_twiddles, dim3((v.steps + 255) / 256), dim3(256), 0, 0, v.band_tw, v.steps);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fail(QOC_ERR_HIP, "%s", no_table);
+    return QOC_OK;
+}
+static int build_trajectory_view(qoc_engine* e, const Problem& p) {
+    const qoc_config& c = e->cfg;
+    QocDev& d = e->d;
+    const size_t B = (size_t)d.B, pts = B * (d.steps + 1), nn = (size_t)d.n * d.n, nm = (size_t)d.n * d.m;
+    const std::vector<double> psi0 = start_vectors(c, p.U0, p.V);
+    std::vector<double> ident(p.U0 ? 0 : 2 * nn, 0.0);             // (state transfer without a start unitary)
+    if (!p.U0) for (int a = 0; a < c.n; ++a) ident[2 * (a * c.n + a)] = 1.0;
+    TRY(dev_upload(e, &d.Hs, (const cplx*)p.Hs, (size_t)(c.k + 1) * nn));
+    TRY(dev_upload(e, &d.U0, (const cplx*)(p.U0 ? p.U0 : ident.data()), nn));
+    TRY(dev_upload(e, &d.V, (const cplx*)p.V, nm)); TRY(dev_upload(e, &d.W, (const cplx*)p.W, nm));
+    TRY(dev_upload(e, &d.Psi0, (const cplx*)psi0.data(), nm));
+    if (d.forbid_dressed) TRY(dev_upload(e, &d.Vs, (const cplx*)p.Vs, nn));
+    TRY(dev_upload(e, &d.maxA, p.maxA, (size_t)c.k));
+    if (p.one_minus_gauss) TRY(dev_upload(e, &d.omg, p.one_minus_gauss, (size_t)c.k * c.steps));
+    if (c.n_forbidden > 0) {
+        std::vector<double> fa(c.n_forbidden);
+        for (int f = 0; f < c.n_forbidden; ++f) fa[f] = p.forbidden_coeffs[f] * (1.0 / (double)c.steps);
+        TRY(dev_upload(e, &d.forb_state, (const int*)p.forbidden_states, (size_t)c.n_forbidden));
+        TRY(dev_upload(e, &d.forb_a, (const double*)fa.data(), (size_t)c.n_forbidden));
+    }
+    TRY(alloc_set_arrays(e, d, "qoc_create", !e->ens_E));         // (an ensemble runs the tail on its group view)
+    TRY(dev_alloc(e, &d.inter, pts * nm)); TRY(dev_zalloc(e, &d.Xfinal, B * nn, "qoc_create")); TRY(dev_alloc(e, &d.ztau, pts));
+    if (d.n_forb > 0) TRY(dev_alloc(e, &d.Fpop, pts * d.n_forb * d.m));
+    if (d.forbid_dressed && d.n_forb > 0) TRY(dev_alloc(e, &d.Fd, pts * d.n_forb * d.m));
+    TRY(dev_alloc(e, &d.zfin, B)); TRY(dev_zalloc(e, &d.su_resid, B, "qoc_create"));
+    TRY(alloc_set_scalars(e, d, "qoc_create", "qoc_create: the phase table of the bandpass regulariser could not be formed"));
+    return dev_alloc(e, &e->step_lr, B);
+}
+
+struct AutoPlan { int path; bool latency, gemm_direct, mfma_ok, st_ok, gemm_ok; };     // (.._ok: the path can run the problem at all)
+
+// The batch-size-dependent part of AUTO as a function of the batch Bp it plans for (tests/test_auto_plan.py restates this table row by row)
+// Every batch-size-dependent choice is taken for Bp = qoc_config.plan_seeds (else the local batch): a shard of a restart batch then runs
+// the same path, kernels and chunking as the whole batch would.
+//
+// Measured with tools/path_sweep.py (profiles/r01_path_sweep.txt):
+//  * unitary, n <= 32: the register-resident MFMA chain kernels win on throughput (1.8 vs 2.3 ms per iteration of 64 C2 seeds), the GEMM
+//    path (fused LDS-resident exponential + product tree + persistent thin chains) on latency (0.19 vs 0.47 ms for one C2 trajectory; level
+//    at 12 seeds, 0.56 vs 0.49 ms at 16 since the batch kernels split the pulse into up to 64 chunks: profiles/r02_latency_sweep.txt); 32 <
+//    n <= 48 (NT = 3: exponentials by three waves per item on v_mfma_f64_4x4x4, costate sweep + slice-parallel gradient kernel): the MFMA
+//    path wins from 8 seeds on (1.11 vs 1.50 ms at 8, 1.70 vs 2.72 at 16, 5.27 vs 9.88 ms at 64 seeds of n = 48; the GEMM path pads to N =
+//    64), ties at 4 (1.00 vs 0.95) and loses below (0.96 vs 0.62 ms at 2); 48 < n <= 64 (NT = 4; tools/n64_batch_sweep.py): with k <= 4
+//    controls the MFMA path is ahead from 32 seeds on (4.96 vs 5.14 ms at 32, 9.16 vs 10.05 at 64, 17.4 vs 19.8 at 128 seeds of n = 64 x
+//    500 slices, since the row-tile gradient kernel); with more controls the GEMM path up to 64 seeds, the MFMA path beyond (since
+//    k_mfma_expm_rows lost its scratch: k = 6 x 200 slices 4.33 vs 4.35 ms at 64 seeds, 7.86 vs 8.47 at 128; k = 8 x 1000 slices 20.05 vs
+//    20.54 at 64, 38.7 vs 40.7 at 128; at 32 seeds the GEMM path: 2.31 vs 2.59, 10.4 vs 10.7).
+//  * a handful of control sets of an n <= 32 unitary problem (the reference's own use is ONE per Grape() call): the latency mode of the
+//    MFMA path. It spends a workgroup per time slice, so what decides is seeds x slices (profiles/r02_latency_sweep.txt,
+//    r02_small_n_sweep.txt): C2 (500 slices) 0.083 ms against 0.189 (GEMM route) and 0.56 (batch kernels) for one seed, still ahead at 12
+//    seeds, level at 16; n <= 16 is padded to 32 and competes with the cheap NT = 1 batch kernels: ahead up to 4 seeds (n = 16 x 500
+//    slices: 0.081 against 0.203 ms for one seed, 0.163 against 0.213 for four) (with k_mfma_expm_slice2 on the active strips: ahead up to
+//    6 control sets with or without a state regulariser -- n = 16 x 500 slices x 6: 0.180 against 0.213 ms, with a forbidden level 0.250
+//    against 0.280; x 8: 0.229 / 0.213 and 0.308 / 0.280; n = 9 x 300 x 6: 0.106 / 0.140; profiles/r04_small_n_latency.txt) 32 < n <= 48
+//    (NT = 3 kernels: k_mfma_expm_rows per slice, the same chains, sweeps and gradient): one trajectory of n = 48 x 500 slices 0.165 ms
+//    against 0.454 (GEMM route) and 0.84 (batch kernels); ahead up to 8 seeds (profiles/r02_mid_n_sweep.txt). With a state regulariser
+//    (forbidden levels, speed_up: lat_src) the backward half is the affine recursion of the batch kernels on the latency mode's chunks,
+//    with two-level boundaries (QocMfma::lat_sources): one C2 trajectory with dwdt + forbidden levels 0.189 ms against 0.290 (GEMM route)
+//    and 0.72 (batch kernels); ahead up to ~4096 seed-slices (tools/c2_forbidden_single.py).
+//  * n > 32 with ONE state vector (dpp_shape): the direct route runs k_gemm_taylor_chain_dpp (0.31 against 0.46 us per dependent mat-vec)
+//    and wins earlier -- C3 (n = 64, k = 6, 1000 slices), propagator / direct route in ms: x 24 6.03 / 6.20, x 32 8.00 / 6.34; without
+//    forbidden levels (both chains side by side) x 12 2.81 / 3.12, x 16 3.74 / 3.18 (profiles/r04_c3_route_sweep.txt); n = 40, 48 with k =
+//    4 x 500 slices, MFMA batch kernels / direct: x 24 1.48 / 1.64, x 32 1.84 / 1.70; with forbidden levels x 32 2.14 / 3.20, x 48 3.89 /
+//    3.32 (profiles/r04_st_direct_sweep.txt). Three-multiplication form of the DPP chain, profiles/r04_c3_route_sweep_gauss.txt: with
+//    forbidden levels x 20 5.05 / 5.43, x 22 5.56 / 5.45, x 24 6.02 / 5.49; without x 11 2.63 / 2.77, x 12 2.84 / 2.79, x 13 3.11 / 2.81 --
+//    the limits (ST_DIRECT_FROM) moved from 28 / 14 to 22 / 12.
+//  * state transfer on the MFMA path (tools/st_path_sweep.py -> profiles/r04_state_transfer_paths.txt; m = 1, T = 10, 500 slices, ms per
+//    iteration, GEMM path / MFMA batch kernels / latency mode): n = 32 x 1: 0.125 / 0.300 / 0.073, x 4: 0.159 / 0.304 / 0.143, x 16: 0.388
+//    / 0.324, x 64: 1.30 / 0.99, x 256: 2.00 (direct Taylor chains) / 3.78; n = 16 x 1: 0.126 / 0.192 / 0.063, x 8: 0.219 / 0.209 / 0.203,
+//    x 64: 1.28 / 0.34, x 256: 1.94 / 1.16; n = 48 x 1: 0.245 / 0.72 / 0.120, x 8: 1.02 / 0.77 / 0.58, x 16: 1.87 / 1.11, x 64: 2.60 / 3.31
+//    (with forbidden levels 4.85 / 4.00); n = 64 (C3: k = 6, 1000 slices) x 1: 0.417 / 3.0 / 0.449, x 64: 9.73 / 18.1 -- so (mfma_auto):
+//    the unitary table for n <= 32 and for 32 < n <= 48 with k <= 4 (NT = 3), the latency mode of n <= 16 up to 8 control sets and from 25
+//    levels on up to 4, the GEMM route for up to 8 control sets from 25 levels on, and the direct Taylor chains of the GEMM path for the
+//    large batches they win (n <= 32: from 112 control sets of more than 20 levels, 28 with a state regulariser; n > 32: from 48, 112).
+static AutoPlan plan_for(const qoc_config& cfg, const QocDev& d, bool antiherm, bool ensemble, int Bp) {
+    const int n = cfg.n, k = cfg.k, steps = cfg.steps, m = cfg.m;
+    const bool st = cfg.state_transfer != 0;
+    // (state transfer: the propagator's adjoint is the reference's gradient only with anti-Hermitian generators)
+    const bool mfma_ok = qoc_mfma_supported(d) && antiherm, gemm_ok = qoc_gemm_supported(d, antiherm);
+    const bool st_ok = st_fused_supported(d), direct_ok = qoc_gemm_direct_supported(d);
+    const bool lat_src = d.n_forb > 0 || d.has_speed;
+    const bool dpp_shape = n > 32 && m == 1;
+    const int ST_DIRECT_FROM = n <= 32 ? QOC_PLAN_ST_DIRECT_N32 : (dpp_shape ? (lat_src ? QOC_PLAN_ST_DIRECT_DPP_SRC
+        : QOC_PLAN_ST_DIRECT_DPP) : QOC_PLAN_ST_DIRECT_N64);
+    const bool mfma_auto = mfma_ok && (!st || n <= 32 || (n <= 48 && k <= 4));
+    const bool nt4_batch = n > 48 && ((k <= 4 && Bp >= QOC_PLAN_NT4_MIN_SETS_K4) || Bp >= QOC_PLAN_NT4_MIN_SETS);
+    // 16 < n <= 32 below the latency mode's reach (long pulses): the GEMM route up to a few control sets, fewer the smaller the active part
+    // of the padded matrices is (500 slices, GEMM route / MFMA batch kernels in ms: n = 32 x 6 0.290 / 0.315, x 8 0.340 / 0.318; n = 27 x 4
+    // 0.251 / 0.270, x 6 0.288 / 0.271; n = 20 x 2 0.185 / 0.196, x 4 0.249 / 0.196; with a forbidden level n = 32 x 8 0.436 / 0.473, n =
+    // 27 x 8 level, n = 20 x 6 0.373 / 0.360)
+    const int qa_g = (n + 3) / 4;
+    const int gemm_small = (st && qa_g >= 7) ? QOC_PLAN_GEMM_SMALL_ST_WIDE
+                           : lat_src ? (qa_g <= 5 ? QOC_PLAN_GEMM_SMALL_SRC_Q5 : qa_g == 6 ? QOC_PLAN_GEMM_SMALL_SRC_Q6
+                               : QOC_PLAN_GEMM_SMALL_SRC_Q78)
+                                     : (qa_g <= 5 ? QOC_PLAN_GEMM_SMALL_Q5 : qa_g == 6 ? QOC_PLAN_GEMM_SMALL_Q6 : qa_g == 7
+                                         ? QOC_PLAN_GEMM_SMALL_Q7 : QOC_PLAN_GEMM_SMALL_Q8);
+    const bool st_big = st && direct_ok && cfg.chunks <= 1 &&
+                        (n <= 32 ? (Bp >= QOC_PLAN_ST_BIG_N32
+                            && n > (lat_src ? QOC_PLAN_ST_BIG_N32_MIN_LEVELS_SRC : QOC_PLAN_ST_BIG_N32_MIN_LEVELS))
+                                 : Bp >= (dpp_shape ? (lat_src ? QOC_PLAN_ST_BIG_DPP_SRC : QOC_PLAN_ST_BIG_DPP) : (lat_src
+                                     ? QOC_PLAN_ST_BIG_N64_SRC : QOC_PLAN_ST_BIG_N64)));
+    const bool prefer_gemm = gemm_ok && ((n > 48 && !nt4_batch) || (n > 32 && Bp < QOC_PLAN_NT3_MIN_SETS) ||
+                                         (n > 16 && n <= 32 && Bp <= gemm_small && m <= 8 && steps >= QOC_PLAN_GEMM_SMALL_MIN_SLICES)
+                                             || st_big);
+    const long long lat_work = (long long)Bp * steps;
+    // 16 < n <= 32: the batch kernels work on the ACTIVE 4-row strips qa = ceil(n / 4) of the padded matrices and take over earlier the
+    // smaller n is (tools/padded_latency_sweep.py, 500 slices: n = 20 / 24 / 27 / 32 level at ~5 / 6 / 7 / 8.5 control sets; with a
+    // forbidden level the latency mode stays ahead up to 8, at n = 20 up to 7): seeds x slices <= 512 qa, with a state regulariser
+    // min(4096, 768 qa)
+    const int qa = (n + 3) / 4 < 5 ? 5 : (n + 3) / 4;
+    const long long lat_limit = n <= 16 ? (lat_src ? QOC_PLAN_LAT_WORK_SRC : QOC_PLAN_LAT_WORK)
+                                        : (lat_src ? std::min<long long>(QOC_PLAN_LAT_WORK_SRC,
+                                            (long long)QOC_PLAN_LAT_WORK_PER_STRIP_SRC * qa)
+                                                   : (long long)QOC_PLAN_LAT_WORK_PER_STRIP * qa);
+    // NT = 4 (also 32 < n <= 48 with k > 4, padded): 0.268 against 0.458 ms (GEMM route) for one seed of 500 slices, level at 8; NT = 3:
+    // the competitors are slower (tools/mid_n_sweep.py); state transfer from 25 levels on: 5 .. 8 control sets go to the GEMM route -- n =
+    // 32 x 8: 0.220 against 0.261 ms, with forbidden levels 0.272 / 0.316
+    const int lat_sets = n > 16 ? ((st && qa_g >= 7) ? QOC_PLAN_LAT_SETS_N32_ST_WIDE : QOC_PLAN_LAT_SETS_N32) : (st
+        ? QOC_PLAN_LAT_SETS_N16_ST : QOC_PLAN_LAT_SETS_N16);
+    const bool latency = !ensemble && cfg.path == QOC_PATH_AUTO && cfg.variant == 0 && mfma_auto && qoc_mfma_latency_ok(d)
+        && steps >= QOC_PLAN_LAT_MIN_SLICES &&
+                          (((n > 48 || (n > 32 && k > 4)) ? (lat_work <= QOC_PLAN_LAT_WORK_NT4 && Bp <= QOC_PLAN_LAT_SETS_NT4)
+                            : n > 32 ? (lat_work <= QOC_PLAN_LAT_WORK_NT3 && Bp <= QOC_PLAN_LAT_SETS_NT3)
+                                     : (lat_work <= lat_limit && Bp <= lat_sets)) ||
+                           (Bp == 1 && steps <= QOC_PLAN_LAT_SINGLE_MAX_SLICES));
+    AutoPlan p;
+    p.mfma_ok = mfma_ok; p.st_ok = st_ok; p.gemm_ok = gemm_ok;
+    p.latency = latency;
+    p.gemm_direct = direct_ok && (!antiherm || cfg.chunks == 1 || (cfg.chunks == 0 && Bp >= ST_DIRECT_FROM));
+    p.path = cfg.path != QOC_PATH_AUTO ? cfg.path
+             : latency ? QOC_PATH_MFMA : (mfma_auto
+                 && !prefer_gemm) ? QOC_PATH_MFMA : (gemm_ok ? QOC_PATH_GEMM : (st_ok ? QOC_PATH_ST_FUSED : QOC_PATH_GENERIC));
+    return p;
+}
+
+// the plan of this engine: plan_for its planned batch, then what overrides the table, then whether the path can run the problem at all
+static int choose_path(const qoc_config& cfg, const QocDev& d, bool antiherm, bool ensemble, AutoPlan& plan) {
+    const int n = cfg.n, k = cfg.k, m = cfg.m, B = cfg.n_seeds;
+    if (cfg.state_transfer && cfg.path == QOC_PATH_GEMM && cfg.chunks > 1 && !antiherm)
+        return fail(QOC_ERR_INVALID,
+            "qoc_create: the propagator route of the GEMM path (chunks > 1) needs exactly anti-Hermitian generators");
+    plan = plan_for(cfg, d, antiherm, ensemble, d.Bplan);
+    if (d.Bplan < B && cfg.gradient != 1) {
+        // a plan for FEWER control sets than the engine holds is legal (a rank that holds several shards of a planned batch keeps
+        // bit-identity with them) but can cost a factor: say so once when it changes what AUTO would have picked for the resident batch
+        const AutoPlan own = plan_for(cfg, d, antiherm, ensemble, B);
+        if (own.path != plan.path || own.latency != plan.latency || own.gemm_direct != plan.gemm_direct)
+            fprintf(stderr, "libqoc_hip: note: plan_seeds = %d < n_seeds = %d changes the AUTO plan (path %d%s instead of %d%s): kernels "
+                "tuned for the smaller batch run on the larger one\n",
+                    d.Bplan, B, plan.path, plan.latency ? " latency mode" : "", own.path, own.latency ? " latency mode" : "");
+    }
+    // n <= 12, one or a few control sets (the reference's own use) and small batches: the workgroup-resident iteration (csrc/qoc_small.h) --
+    // 5-20 us per iteration where the paths above pay 42-57 us of launches and dependent round trips whatever n (profiles/r06_small_n_latency.txt)
+    // (QOC_EXPERIMENTAL=1 QOC_SMALL_AUTO=0: AUTO without it, for A/B runs -- tools/small_n_latency.py)
+    if (!ensemble && cfg.path == QOC_PATH_AUTO && cfg.variant == 0 && cfg.chunks == 0 && cfg.time_shards < 1
+        && !qoc_exp_is("QOC_SMALL_AUTO", 0) && qoc_small_auto(d, antiherm))
+        plan.path = QOC_PATH_SMALL;
+    if (cfg.gradient == 1) plan.path = QOC_PATH_GENERIC;             // (whatever AUTO's table says: the exact gradient has one home)
+    if (cfg.time_shards >= 1) {
+        if (cfg.time_rank < -1 || cfg.time_rank >= cfg.time_shards)
+            return fail(QOC_ERR_INVALID, "qoc_create: time_rank %d of %d time shards", cfg.time_rank, cfg.time_shards);
+        if (cfg.path != QOC_PATH_AUTO && cfg.path != QOC_PATH_GEMM)
+            return fail(QOC_ERR_INVALID, "qoc_create: time sharding runs on the GEMM path");
+        plan.path = QOC_PATH_GEMM;
+    }
+    if (plan.path == QOC_PATH_MFMA && !plan.mfma_ok)
+        return fail(QOC_ERR_INVALID, "qoc_create: MFMA path needs n <= 64, m <= 16, k <= 8, a Taylor degree of 1 .. 22 and, in state "
+            "transfer, exactly anti-Hermitian generators (n=%d m=%d k=%d T=%d)", n, m, k, d.T);
+    if (plan.path == QOC_PATH_ST_FUSED && !plan.st_ok)
+        return fail(QOC_ERR_INVALID,
+            "qoc_create: fused state-transfer path needs state_transfer, n <= 64, m <= 4, k <= 8 (n=%d m=%d k=%d)", n, m, k);
+    if (plan.path == QOC_PATH_GEMM && !plan.gemm_ok)
+        return fail(QOC_ERR_INVALID,
+            "qoc_create: GEMM path needs m <= 32 and, in state transfer, exactly anti-Hermitian generators or n <= 64, m <= 8 (m=%d)", m);
+    if (plan.path < QOC_PATH_GENERIC || plan.path > QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "qoc_create: unknown path %d", plan.path);
+    return QOC_OK;
+}
+
+// the any-size kernels' buffers: the generic path's own, and the workgroup-resident path's for its read-backs
+static int alloc_generic_scratch(qoc_engine* e) {
+    const QocDev& d = e->d;
+    const size_t B = (size_t)d.B, nn = (size_t)d.n * d.n, nm = (size_t)d.n * d.m;
+    if (d.state_transfer) return dev_alloc(e, &e->seed_scratch, B * (nn + 3 * nm));
+    TRY(dev_alloc(e, &e->K, B * d.steps * nn));
+    e->expm_grid = (int)grid_for(B * d.steps, 1, 4096);
+    TRY(dev_alloc(e, &e->expm_scratch, (size_t)e->expm_grid * 3 * nn));
+    return dev_alloc(e, &e->seed_scratch, B * (2 * nn + 2 * nm));
+}
+// what the engine's path keeps beside the views (the fused state-transfer kernels: nothing)
+static int setup_path(qoc_engine* e, const double* Hs, bool antiherm, const AutoPlan& plan) {
+    const qoc_config& c = e->cfg;
+    QocDev& d = e->d;
+    std::string msg;
+    int rc = QOC_OK;
+    switch (e->path) {
+    case QOC_PATH_MFMA:
+        e->mf.variant = plan.latency ? 5 : c.variant;
+        if (c.variant == 5 && !qoc_mfma_latency_ok(d))
+            return fail(QOC_ERR_INVALID, "qoc_create: the latency mode of the MFMA path (variant 5) needs n <= 32 with k <= 8 (or, "
+                "with at most 4 dressed forbidden levels, n <= 64), "
+                                              "a Taylor degree >= 2 (n=%d k=%d T=%d)", c.n, c.k, d.T);
+        // state transfer: sum_{j < T} A^j / j! is the polynomial of degree T - 1 (no squarings: d.s = 0)
+        d.T = qoc_mfma_degree(d);
+        rc = qoc_mfma_setup(e->mf, d, c.chunks, (const cplx*)Hs, e->allocs, msg);
+        if (rc) return fail(rc, "qoc_create: %s", msg.c_str());
+        e->chunks = e->mf.C;
+        break;
+    case QOC_PATH_GEMM:
+        if (c.time_shards >= 1) { e->gm.ts_G = c.time_shards; e->gm.ts_rank = c.time_rank; }
+        e->gm.antiherm = antiherm;
+        e->gm.direct_variant = c.path == QOC_PATH_GEMM ? c.variant : 0;
+        rc = qoc_gemm_setup(e->gm, d, (const cplx*)Hs, plan.gemm_direct, e->allocs, msg);
+        if (rc) return fail(rc, "qoc_create: %s", msg.c_str());
+        if (!qoc_gemm_lds_opt_in()) return fail(QOC_ERR_HIP, "qoc_create: cannot reserve LDS for the GEMM-path kernels");
+        e->chunks = e->gm.NC;
+        // the split tail sums the gradient partials: one launch less (an ensemble reduces the members' gradients first)
+        e->gm.reduce_in_tail = !e->ens_E && tail_kind(e) == TAIL_SPLIT_PARTIALS;
+        if (e->gm.ts_G > 0) {
+            std::string why;
+            if (!qoc_gemm_ts_supported(e->gm, d, e->gm.ts_G, why))
+                return fail(QOC_ERR_INVALID, "qoc_create: time_shards = %d needs %s (n=%d m=%d chunks=%d)", e->gm.ts_G, why.c_str(), c.n,
+                    c.m, e->gm.NC);
+            qoc_gemm_ts_ranges(e->gm, e->gm.ts_G);
+        }
+        break;
+    case QOC_PATH_SMALL:
+        rc = qoc_small_setup(e->sm, d, antiherm, c.chunks, c.variant, e->allocs, msg);
+        if (rc) return fail(rc == -1 ? QOC_ERR_INVALID : (rc == -3 ? QOC_ERR_NOMEM : QOC_ERR_HIP),
+            "qoc_create: %s (n=%d m=%d k=%d T=%d steps=%d seeds=%d)", msg.c_str(), c.n, c.m, c.k, d.T, c.steps, c.n_seeds);
+        e->chunks = e->sm.G;
+        [[fallthrough]];          // read-back (inter_vecs, final_state, unitary_scale) runs the any-size kernels on the last controls
+    case QOC_PATH_GENERIC: return alloc_generic_scratch(e);
+    }
+    return QOC_OK;
+}
+static int setup_exact_gradient(qoc_engine* e) {
+    const QocDev& d = e->d;
+    if (const char* why = qoc_exact_plan(e->xg, d)) return fail(QOC_ERR_INVALID, "qoc_create: %s (T=%d s=%d)", why, d.T, d.s);
+    TRY(dev_alloc(e, &e->xg.Lam, (size_t)d.B * d.steps * d.n * d.m));
+    TRY(dev_alloc(e, &e->xg.scratch, (size_t)e->xg.grid * e->xg.per_wg));
+    HIP_TRY_MSG(qoc_exact_lds_opt_in(e->xg), "qoc_create: cannot reserve %zu bytes of LDS for the exact gradient kernel", e->xg.lds_bytes);
+    return QOC_OK;
+}
+
+// the group view of an ensemble engine: the caller's G control sets of k controls -- variable, Adam slots, stop rule, pulse regularisers,
+// the tail's arrays -- beside the members' description and, for a pulse response, the response matrix
+static int setup_group_view(qoc_engine* e, const EnsArgs& a) {
+    const qoc_config& uc = *a.user;
+    const qoc_ensemble& en = *a.ens;
+    const int kg = uc.k, G = uc.n_seeds, E = en.members, q = en.n_perturb, steps = e->d.steps;
+    QocDev& gv = e->g;
+    gv = e->d;
+    gv.k = kg; gv.B = G; gv.Bplan = G;
+    // a pulse response: the group view is the SAMPLE view -- P samples of total_time / P each stand where the time slices stood, so the
+    // pulse regularisers act on the samples with their coefficients divided by P
+    if (a.shape) { gv.steps = a.shape->P; gv.dt = uc.total_time / (double)gv.steps; }
+    fill_pulse_regularisers(gv, uc);
+    // (the trajectories' buffers are not the groups'; omg and the bandpass arrays are null already: no trajectory has a pulse regulariser)
+    gv.inter = nullptr; gv.Xfinal = nullptr; gv.ztau = nullptr; gv.Fpop = nullptr; gv.Fd = nullptr; gv.zfin = nullptr;
+    gv.su_resid = nullptr;
+    TRY(dev_upload(e, &gv.maxA, a.maxA, (size_t)kg));
+    if (a.one_minus_gauss) TRY(dev_upload(e, &gv.omg, a.one_minus_gauss, (size_t)kg * gv.steps));
+    TRY(alloc_set_arrays(e, gv, "qoc_create_ensemble", true));
+    TRY(alloc_set_scalars(e, gv, "qoc_create_ensemble", "qoc_create_ensemble: the bandpass phase table could not be formed"));
+    const double* da = nullptr; const double* dd = nullptr; const double* dw = nullptr;
+    TRY(dev_upload(e, &da, en.amp_scales, (size_t)E * kg));
+    if (q > 0) TRY(dev_upload(e, &dd, en.offsets, (size_t)E * q));
+    TRY(dev_upload(e, &dw, en.weights, (size_t)E));
+    e->en = QocEns{E, q, da, dd, dw};
+    e->ens_wt.assign(en.weights, en.weights + E);
+    if (const ShapeHost* shp = a.shape) {
+        QocShape& sh = e->sh;
+        sh.P = shp->P; sh.band = shp->band; sh.col_band = shp->col_band;
+        TRY(dev_upload(e, &sh.Tt, shp->Tt.data(), (size_t)steps * shp->P));
+        TRY(dev_upload(e, &sh.row_win, shp->row_win.data(), (size_t)steps));
+        TRY(dev_upload(e, &sh.col_win, shp->col_win.data(), (size_t)shp->P));
+        TRY(dev_alloc(e, &sh.uf, (size_t)G * kg * steps));
+        e->shaped = true;
+    }
+    return QOC_OK;
+}
+
+static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out) {
+    TRY(check_create_args(cfg, p, out));
+    HIP_TRY(hipSetDevice(cfg->device));
+    // the half-built engine owns itself: every early return below destroys it (fail() has set the message by then)
+    std::unique_ptr<qoc_engine, int (*)(qoc_handle)> guard(new qoc_engine(), qoc_destroy);
+    qoc_engine* e = guard.get();
+    e->cfg = *cfg;
+    if (ens) e->ens_E = ens->ens->members;
+    // the trajectory view: the shape, the state regularisers and (a plain engine: its control sets are the trajectories) the pulse's
+    QocDev& d = e->d;
+    memset(&d, 0, sizeof d);
+    d.n = cfg->n; d.k = cfg->k; d.steps = cfg->steps; d.m = cfg->m; d.T = cfg->taylor_terms; d.s = cfg->state_transfer ? 0 : cfg->scaling;
+    d.B = cfg->n_seeds; d.state_transfer = cfg->state_transfer; d.dt = cfg->dt;
+    d.Bplan = cfg->plan_seeds > 0 ? cfg->plan_seeds : cfg->n_seeds;
+    fill_pulse_regularisers(d, *cfg);
+    d.has_speed = cfg->has_speed_up; d.a_speed = cfg->c_speed_up * (1.0 / (double)cfg->steps);
+    d.n_forb = cfg->n_forbidden; d.forbid_dressed = cfg->forbid_dressed && cfg->n_forbidden > 0;
+    HIP_TRY_MSG(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate failed");
+    HIP_TRY_MSG(hipEventCreate(&e->t0), "hipEventCreate failed");
+    HIP_TRY_MSG(hipEventCreate(&e->t1), "hipEventCreate failed");
+    TRY(build_trajectory_view(e, p));
+    const bool antiherm = cfg->state_transfer ? qoc_all_antihermitian((const cplx*)p.Hs, cfg->n, cfg->k + 1) : true;
+    AutoPlan plan;
+    TRY(choose_path(*cfg, d, antiherm, ens != nullptr, plan));
+    e->path = plan.path; e->chunks = 1;
+#ifdef QOC_DEBUG     // timing experiments only (tools/skip_timing.py builds its own library with -DQOC_DEBUG): never in the product library
+    if (const char* sk = getenv("QOC_DEBUG_SKIP")) {             // wall-clock attribution of one kernel group
+        e->skip_mask = atoi(sk);
+        if (e->skip_mask) fprintf(stderr, "libqoc_hip: WARNING: QOC_DEBUG_SKIP=%d is set -- kernel groups are skipped or repeated, every "
+            "result of this engine is garbage (timing experiments only)\n", e->skip_mask);
+    }
+#endif
+    TRY(setup_path(e, p.Hs, antiherm, plan));
+    if (cfg->gradient == 1) TRY(setup_exact_gradient(e));
+    if (ens) TRY(setup_group_view(e, *ens));
+    const hipError_t se = hipDeviceSynchronize();
+    HIP_TRY_MSG(se, "qoc_create: %s", hipGetErrorString(se));
+    *out = guard.release();
+    return QOC_OK;
+}
+
 extern "C" {
 
 const char* qoc_last_error(void) { return g_err.c_str(); }
@@ -539,459 +977,16 @@ int qoc_device_peer_access(int32_t device, int32_t peer, int32_t* can_access) {
     return QOC_OK;
 }
 
-// what qoc_create_ensemble adds to the trajectory engine it creates: the caller's own configuration (k controls, n_seeds control sets, the
-// pulse regularisers) for the group view, and the member description
-struct EnsArgs {
-    const qoc_config* user;
-    const double* maxA;              // [k]
-    const double* one_minus_gauss;   // [k][steps] or null
-    const qoc_ensemble* ens;
-    const struct ShapeHost* shape;   // qoc_create_shaped: the response matrix and its windows, else null
-};
-
-// the response matrix of qoc_create_shaped as the host prepared it: the transposed copy and the nonzero window of every row and column
-struct ShapeHost {
-    int P, band, col_band;
-    std::vector<double> Tt;          // [P][steps]: T transposed (what the kernels read)
-    std::vector<int2> row_win, col_win;
-};
-
-static int create_engine(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
-                         const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                         const double* forbidden_coeffs, const double* Vs, const EnsArgs* ens, qoc_handle* out) {
-    if (!cfg || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create: null argument");
-    if (cfg->plan_seeds < 0) return fail(QOC_ERR_INVALID,
-        "qoc_create: plan_seeds = %d (0 = plan for n_seeds, > 0 = the batch AUTO plans for)", cfg->plan_seeds);
-    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->m < 1 || cfg->n_seeds < 1)
-        return fail(QOC_ERR_INVALID, "qoc_create: n, k, steps, m, n_seeds must be >= 1");
-    if (cfg->taylor_terms < 1 || cfg->scaling < 0 || cfg->scaling > 30)
-        return fail(QOC_ERR_INVALID, "qoc_create: bad taylor_terms/scaling (%d, %d)", cfg->taylor_terms, cfg->scaling);
-    if (!cfg->state_transfer && !U0) return fail(QOC_ERR_INVALID, "qoc_create: U0 required in unitary mode");
-    if (cfg->n_forbidden < 0) return fail(QOC_ERR_INVALID, "qoc_create: n_forbidden must be >= 0");
-    if (cfg->n_forbidden > 0 && (!forbidden_states || !forbidden_coeffs))
-        return fail(QOC_ERR_INVALID, "qoc_create: forbidden lists missing");
-    if (cfg->forbid_dressed && cfg->n_forbidden > 0 && !Vs)
-        return fail(QOC_ERR_INVALID, "qoc_create: forbid_dressed needs Vs");
-    if (cfg->has_envelope && !one_minus_gauss) return fail(QOC_ERR_INVALID, "qoc_create: envelope constant missing");
-    if (cfg->has_d2wdt2 && !cfg->has_dwdt)
-        return fail(QOC_ERR_INVALID, "qoc_create: d2wdt2 needs dwdt (reference: NameError new_weights)");
-    for (int f = 0; f < cfg->n_forbidden; ++f)
-        if (forbidden_states[f] < 0 || forbidden_states[f] >= cfg->n)
-            return fail(QOC_ERR_INVALID, "qoc_create: forbidden state %d out of range", forbidden_states[f]);
-    if (cfg->gradient != 0 && cfg->gradient != 1)
-        return fail(QOC_ERR_INVALID, "qoc_create: gradient = %d (0 = first-order, the reference's; 1 = exact gradient)", cfg->gradient);
-    if (cfg->gradient == 1) {
-        // the exact gradient runs behind the generic path's forward (csrc/qoc_exact_grad.h); the other paths keep K_t in layouts of their own
-        if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_GENERIC)
-            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient runs on the generic path (QOC_PATH_GENERIC or AUTO), not on path %d", cfg->path);
-        if (cfg->time_shards > 0)
-            return fail(QOC_ERR_INVALID, "qoc_create: the exact gradient cannot be time-sharded (time_shards = %d)", cfg->time_shards);
-    }
-    int ndev = 0;
-    hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0)
-        return fail(QOC_ERR_HIP, "qoc_create: no HIP device visible (%s) -- this engine has no CPU fallback",
-                    de == hipSuccess ? "count = 0" : hipGetErrorString(de));
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(QOC_ERR_INVALID, "qoc_create: device %d of %d", cfg->device, ndev);
-    HIP_TRY(hipSetDevice(cfg->device));
-
-    qoc_engine* e = new qoc_engine();
-    e->cfg = *cfg;
-    if (ens) e->ens_E = ens->ens->members;
-    QocDev& d = e->d;
-    memset(&d, 0, sizeof d);
-    const int n = cfg->n, k = cfg->k, steps = cfg->steps, m = cfg->m, B = cfg->n_seeds;
-    d.n = n; d.k = k; d.steps = steps; d.m = m; d.T = cfg->taylor_terms; d.s = cfg->state_transfer ? 0 : cfg->scaling;
-    d.B = B; d.state_transfer = cfg->state_transfer; d.dt = cfg->dt;
-    d.Bplan = cfg->plan_seeds > 0 ? cfg->plan_seeds : B;
-    const double inv_steps = 1.0 / (double)steps;
-    d.has_amp = cfg->has_amplitude; d.a_amp = cfg->c_amplitude * inv_steps;
-    d.has_env = cfg->has_envelope; d.a_env = cfg->c_envelope * inv_steps;
-    d.has_dwdt = cfg->has_dwdt; d.a_dwdt = cfg->c_dwdt * inv_steps;
-    d.has_d2wdt2 = cfg->has_d2wdt2; d.a_d2wdt2 = cfg->c_d2wdt2 * inv_steps;
-    d.has_speed = cfg->has_speed_up; d.a_speed = cfg->c_speed_up * inv_steps;
-    d.has_band = cfg->has_bandpass; d.a_band = cfg->c_bandpass * inv_steps;
-    d.band_lo = cfg->band_lo; d.band_hi = cfg->band_hi;
-    d.n_forb = cfg->n_forbidden; d.forbid_dressed = cfg->forbid_dressed && cfg->n_forbidden > 0;
-    int rc = QOC_OK;
-    auto bail = [&](int code) { qoc_destroy(e); return code; };
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(QOC_ERR_HIP, "hipStreamCreate failed"));
-    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) return bail(fail(QOC_ERR_HIP,
-        "hipEventCreate failed"));
-
-    const size_t nn = (size_t)n * n, nm = (size_t)n * m, ks = (size_t)k * steps;
-    // U0*V on the host (tiny): start vector of the thin forward recursion
-    std::vector<double> psi0(2 * nm);
-    for (int a = 0; a < n; ++a)
-        for (int j = 0; j < m; ++j) {
-            double re = 0, im = 0;
-            if (cfg->state_transfer) {
-                re = V[2 * (a * m + j)]; im = V[2 * (a * m + j) + 1];
-            } else {
-                for (int c = 0; c < n; ++c) {
-                    const double ur = U0[2 * (a * n + c)], ui = U0[2 * (a * n + c) + 1];
-                    const double vr = V[2 * (c * m + j)], vi = V[2 * (c * m + j) + 1];
-                    re += ur * vr - ui * vi;
-                    im += ur * vi + ui * vr;
-                }
-            }
-            psi0[2 * (a * m + j)] = re; psi0[2 * (a * m + j) + 1] = im;
-        }
-    std::vector<double> ident;
-    if (!U0) {
-        ident.assign(2 * nn, 0.0);
-        for (int a = 0; a < n; ++a) ident[2 * (a * n + a)] = 1.0;
-        U0 = ident.data();
-    }
-    if ((rc = dev_upload(e, &d.Hs, (const cplx*)Hs, (size_t)(k + 1) * nn))) return bail(rc);
-    if ((rc = dev_upload(e, &d.U0, (const cplx*)U0, nn))) return bail(rc);
-    if ((rc = dev_upload(e, &d.V, (const cplx*)V, nm))) return bail(rc);
-    if ((rc = dev_upload(e, &d.W, (const cplx*)W, nm))) return bail(rc);
-    if ((rc = dev_upload(e, &d.Psi0, (const cplx*)psi0.data(), nm))) return bail(rc);
-    if (d.forbid_dressed && (rc = dev_upload(e, &d.Vs, (const cplx*)Vs, nn))) return bail(rc);
-    if ((rc = dev_upload(e, &d.maxA, maxA, (size_t)k))) return bail(rc);
-    if (one_minus_gauss && (rc = dev_upload(e, &d.omg, one_minus_gauss, ks))) return bail(rc);
-    if (cfg->n_forbidden > 0) {
-        std::vector<double> fa(cfg->n_forbidden);
-        for (int f = 0; f < cfg->n_forbidden; ++f) fa[f] = forbidden_coeffs[f] * inv_steps;
-        if ((rc = dev_upload(e, &d.forb_state, (const int*)forbidden_states, (size_t)cfg->n_forbidden))) return bail(rc);
-        if ((rc = dev_upload(e, &d.forb_a, (const double*)fa.data(), (size_t)cfg->n_forbidden))) return bail(rc);
-    }
-
-#define ALLOC(ptr, count) if ((rc = dev_alloc(e, &(ptr), (count)))) return bail(rc)
-    ALLOC(d.base, B * ks); ALLOC(d.adam_m, B * ks); ALLOC(d.adam_v, B * ks);
-    ALLOC(d.adam_t, (size_t)B); ALLOC(d.iters, (size_t)B); ALLOC(d.done, (size_t)B);
-    ALLOC(d.w, B * ks); ALLOC(d.u, B * ks); ALLOC(d.w2, B * ks); ALLOC(d.u2, B * ks); ALLOC(d.dLdu, B * ks); ALLOC(d.grad, B * ks);
-    if (!ens && ks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {      // (the tail of such control sets runs over fin_S workgroups each; the switch: A/B runs)
-        e->fin_S = (int)((ks + 255) / 256);
-        if (e->fin_S > 64) e->fin_S = 64;                          // (longer pulses: several elements per thread)
-        ALLOC(e->fin_part, (size_t)B * (e->fin_S + 2) * 2);
-    }
-    ALLOC(d.inter, (size_t)B * (steps + 1) * nm);
-    ALLOC(d.Xfinal, (size_t)B * nn);
-    ALLOC(d.ztau, (size_t)B * (steps + 1));
-    if (d.n_forb > 0) ALLOC(d.Fpop, (size_t)B * (steps + 1) * d.n_forb * m);
-    if (d.forbid_dressed && d.n_forb > 0) ALLOC(d.Fd, (size_t)B * (steps + 1) * d.n_forb * m);
-    ALLOC(d.zfin, (size_t)B); ALLOC(d.su_resid, (size_t)B);
-    ALLOC(d.loss, (size_t)B); ALLOC(d.reg_state, (size_t)B); ALLOC(d.reg_loss, (size_t)B);
-    ALLOC(d.g2, (size_t)B); ALLOC(d.uscale, (size_t)B);
-    if (d.has_band) { ALLOC(d.band_ph, B * ks); ALLOC(d.band_tw, (size_t)steps); ALLOC(d.band_mag, B * ks); ALLOC(d.band_dR, B * ks); }
-    ALLOC(e->step_lr, (size_t)B);
-    if (hipMemset(d.base, 0, B * ks * sizeof(double)) != hipSuccess ||
-        hipMemset(d.adam_m, 0, B * ks * sizeof(double)) != hipSuccess ||
-        hipMemset(d.adam_v, 0, B * ks * sizeof(double)) != hipSuccess ||
-        hipMemset(d.adam_t, 0, B * sizeof(int)) != hipSuccess ||
-        hipMemset(d.iters, 0, B * sizeof(int)) != hipSuccess ||
-        hipMemset(d.done, 0, B * sizeof(int)) != hipSuccess ||
-        hipMemset(d.su_resid, 0, B * sizeof(double)) != hipSuccess ||
-        hipMemset(d.uscale, 0, B * sizeof(double)) != hipSuccess ||
-        hipMemset(d.Xfinal, 0, (size_t)B * nn * sizeof(cplx)) != hipSuccess)
-        return bail(fail(QOC_ERR_HIP, "qoc_create: clearing the state buffers failed"));
-    if (d.has_band) {
-        hipLaunchKernelGGL(k_band_twiddles, dim3((steps + 255) / 256), dim3(256), 0, 0, d.band_tw, steps);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-            return bail(fail(QOC_ERR_HIP, "qoc_create: the phase table of the bandpass regulariser could not be formed"));
-    }
-
-    // ---- path selection -----------------------------------------------------------------------------------------
-    int path = cfg->path;
-    const bool antiherm = cfg->state_transfer ? qoc_all_antihermitian((const cplx*)Hs, n, k + 1) : true;
-    // (state transfer: the propagator's adjoint is the reference's gradient only then)
-    const bool mfma_ok = qoc_mfma_supported(d) && antiherm;
-    const bool st_ok = st_fused_supported(d);
-    const bool gemm_ok = qoc_gemm_supported(d, antiherm);
-    // Measured with tools/path_sweep.py (profiles/r01_path_sweep.txt):
-    //  * unitary, n <= 32: the register-resident MFMA chain kernels win on throughput (1.8 vs 2.3 ms per iteration of 64
-    //    C2 seeds), the GEMM path (fused LDS-resident exponential + product tree + persistent thin chains) on latency
-    //    (0.19 vs 0.47 ms for one C2 trajectory; level at 12 seeds, 0.56 vs 0.49 ms at 16 since the batch kernels split the pulse into
-    //    up to 64 chunks: profiles/r02_latency_sweep.txt); 32 < n <= 48 (NT = 3: exponentials by
-    //    three waves per item on v_mfma_f64_4x4x4, costate sweep + slice-parallel gradient kernel): the MFMA path wins from 8 seeds
-    //    on (1.11 vs 1.50 ms at 8, 1.70 vs 2.72 at 16, 5.27 vs 9.88 ms at 64 seeds of n = 48; the GEMM path pads to N = 64), ties at
-    //    4 (1.00 vs 0.95) and loses below (0.96 vs 0.62 ms at 2); 48 < n <= 64 (NT = 4; tools/n64_batch_sweep.py): with k <= 4 controls
-    //    the MFMA path is ahead from 32 seeds on (4.96 vs 5.14 ms at 32, 9.16 vs 10.05 at 64, 17.4 vs 19.8 at 128 seeds of n = 64 x 500
-    //    slices, since the row-tile gradient kernel); with more controls the GEMM path up to 64 seeds, the MFMA path beyond (round 3, after
-    // k_mfma_expm_rows lost its scratch: k = 6 x 200 slices 4.33 vs 4.35 ms at 64 seeds, 7.86 vs 8.47 at 128; k = 8 x 1000 slices 20.05 vs
-    //    20.54 at 64, 38.7 vs 40.7 at 128; at 32 seeds the GEMM path: 2.31 vs 2.59, 10.4 vs 10.7).
-    // every batch-size-dependent choice below is taken for Bp = qoc_config.plan_seeds (else the local batch): a shard of a restart
-    // batch then runs the same path, kernels and chunking as the whole batch would
-    const bool direct_ok = qoc_gemm_direct_supported(d);
-    if (cfg->state_transfer && cfg->path == QOC_PATH_GEMM && cfg->chunks > 1 && !antiherm)
-        return bail(fail(QOC_ERR_INVALID,
-            "qoc_create: the propagator route of the GEMM path (chunks > 1) needs exactly anti-Hermitian generators"));
-    // a handful of control sets of an n <= 32 unitary problem (the reference's own use is ONE per Grape() call): the latency mode of
-    // the MFMA path.  It spends a workgroup per time slice, so what decides is seeds x slices
-    // (profiles/r02_latency_sweep.txt, r02_small_n_sweep.txt): C2 (500 slices) 0.083 ms against 0.189 (GEMM route) and 0.56 (batch
-    // kernels) for one seed, still ahead at 12 seeds, level at 16; n <= 16 is padded to 32 and competes with the cheap NT = 1 batch
-    // kernels: ahead up to 4 seeds (n = 16 x 500 slices: 0.081 against 0.203 ms for one seed, 0.163 against 0.213 for four)
-    // (round 4, with k_mfma_expm_slice2 on the active strips: ahead up to 6 control sets with or without a state regulariser -- n = 16 x
-    // 500 slices x 6: 0.180 against 0.213 ms, with a forbidden level 0.250 against 0.280; x 8: 0.229 / 0.213 and 0.308 / 0.280; n = 9 x 300
-    // x 6: 0.106 / 0.140; profiles/r04_small_n_latency.txt) 32 < n <= 48 (NT = 3 kernels: k_mfma_expm_rows per slice, the same chains,
-    // sweeps and gradient): one trajectory of n = 48 x 500 slices 0.165 ms against 0.454 (GEMM route) and 0.84 (batch kernels); ahead up to
-    // 8 seeds (profiles/r02_mid_n_sweep.txt). With a state regulariser (forbidden levels, speed_up) the backward half is the affine
-    // recursion of the batch kernels on the latency mode's chunks, with two-level boundaries (QocMfma::lat_sources): one C2 trajectory with
-    // dwdt + forbidden levels 0.189 ms against 0.290 (GEMM route) and 0.72 (batch kernels); ahead up to ~4096 seed-slices
-    // (tools/c2_forbidden_single.py).
-    const bool lat_src = d.n_forb > 0 || d.has_speed;
-    // n > 32 with ONE state vector: the direct route runs k_gemm_taylor_chain_dpp (round 4: 0.31 against 0.46 us per dependent mat-vec) and
-    // wins earlier -- C3 (n = 64, k = 6, 1000 slices), propagator / direct route in ms: x 24 6.03 / 6.20, x 32 8.00 / 6.34; without
-    // forbidden levels (both chains side by side) x 12 2.81 / 3.12, x 16 3.74 / 3.18 (profiles/r04_c3_route_sweep.txt); n = 40, 48 with k =
-    // 4 x 500 slices, MFMA batch kernels / direct: x 24 1.48 / 1.64, x 32 1.84 / 1.70; with forbidden levels x 32 2.14 / 3.20, x 48 3.89 /
-    // 3.32 (profiles/r04_st_direct_sweep.txt)
-    const bool dpp_shape = n > 32 && m == 1;
-    // (three-multiplication form of the DPP chain, profiles/r04_c3_route_sweep_gauss.txt: with forbidden levels x 20 5.05 / 5.43, x 22 5.56
-    // / 5.45, x 24 6.02 / 5.49; without x 11 2.63 / 2.77, x 12 2.84 / 2.79, x 13 3.11 / 2.81 -- the limits moved from 28 / 14 to 22 / 12)
-    const int ST_DIRECT_FROM = n <= 32 ? QOC_PLAN_ST_DIRECT_N32 : (dpp_shape ? (lat_src ? QOC_PLAN_ST_DIRECT_DPP_SRC
-        : QOC_PLAN_ST_DIRECT_DPP) : QOC_PLAN_ST_DIRECT_N64);
-    struct AutoPlan { int path; bool latency; bool gemm_direct; };
-    // the batch-size-dependent part of AUTO as a function of the batch it plans for (tests/test_auto_plan.py restates this table row by
-    // row) State transfer on the MFMA path (round 4, tools/st_path_sweep.py -> profiles/r04_state_transfer_paths.txt; m = 1, T = 10, 500
-    // slices, ms per iteration, GEMM path / MFMA batch kernels / latency mode): n = 32 x 1: 0.125 / 0.300 / 0.073, x 4: 0.159 / 0.304 /
-    // 0.143, x 16: 0.388 / 0.324, x 64: 1.30 / 0.99, x 256: 2.00 (direct Taylor chains) / 3.78; n = 16 x 1: 0.126 / 0.192 / 0.063, x 8:
-    // 0.219 / 0.209 / 0.203, x 64: 1.28 / 0.34, x 256: 1.94 / 1.16; n = 48 x 1: 0.245 / 0.72 / 0.120, x 8: 1.02 / 0.77 / 0.58, x 16: 1.87 /
-    // 1.11, x 64: 2.60 / 3.31 (with forbidden levels 4.85 / 4.00); n = 64 (C3: k = 6, 1000 slices) x 1: 0.417 / 3.0 / 0.449, x 64: 9.73 /
-    // 18.1 -- so: the unitary table for n <= 32 and for 32 < n <= 48 with k <= 4 (NT = 3), the latency mode of n <= 16 up to 8 control sets
-    // and from 25 levels on up to 4, the GEMM route for up to 8 control sets from 25 levels on, and the direct Taylor chains of the GEMM
-    // path for the large batches they win (n <= 32: from 112 control sets of more than 20 levels, 28 with a state regulariser;
-    // n > 32: from 48, 112).
-    const bool st = cfg->state_transfer != 0;
-    const bool mfma_auto = mfma_ok && (!st || n <= 32 || (n <= 48 && k <= 4));
-    auto plan_for = [&](int Bp) -> AutoPlan {
-        const bool nt4_batch = n > 48 && ((k <= 4 && Bp >= QOC_PLAN_NT4_MIN_SETS_K4) || Bp >= QOC_PLAN_NT4_MIN_SETS);
-        // 16 < n <= 32 below the latency mode's reach (long pulses): the GEMM route up to a few control sets, fewer the smaller the active
-        // part of the padded matrices is (500 slices, GEMM route / MFMA batch kernels in ms: n = 32 x 6 0.290 / 0.315, x 8 0.340 / 0.318; n
-        // = 27 x 4 0.251 / 0.270, x 6 0.288 / 0.271; n = 20 x 2 0.185 / 0.196, x 4 0.249 / 0.196; with a forbidden level n = 32 x 8 0.436 /
-        // 0.473, n = 27 x 8 level, n = 20 x 6 0.373 / 0.360)
-        const int qa_g = (n + 3) / 4;
-        const int gemm_small = (st && qa_g >= 7) ? QOC_PLAN_GEMM_SMALL_ST_WIDE
-                               : lat_src ? (qa_g <= 5 ? QOC_PLAN_GEMM_SMALL_SRC_Q5 : qa_g == 6 ? QOC_PLAN_GEMM_SMALL_SRC_Q6
-                                   : QOC_PLAN_GEMM_SMALL_SRC_Q78)
-                                         : (qa_g <= 5 ? QOC_PLAN_GEMM_SMALL_Q5 : qa_g == 6 ? QOC_PLAN_GEMM_SMALL_Q6 : qa_g == 7
-                                             ? QOC_PLAN_GEMM_SMALL_Q7 : QOC_PLAN_GEMM_SMALL_Q8);
-        const bool st_big = st && direct_ok && cfg->chunks <= 1 &&
-                            (n <= 32 ? (Bp >= QOC_PLAN_ST_BIG_N32
-                                && n > (lat_src ? QOC_PLAN_ST_BIG_N32_MIN_LEVELS_SRC : QOC_PLAN_ST_BIG_N32_MIN_LEVELS))
-                                     : Bp >= (dpp_shape ? (lat_src ? QOC_PLAN_ST_BIG_DPP_SRC : QOC_PLAN_ST_BIG_DPP) : (lat_src
-                                         ? QOC_PLAN_ST_BIG_N64_SRC : QOC_PLAN_ST_BIG_N64)));
-        const bool prefer_gemm = gemm_ok && ((n > 48 && !nt4_batch) || (n > 32 && Bp < QOC_PLAN_NT3_MIN_SETS) ||
-                                             (n > 16 && n <= 32 && Bp <= gemm_small && m <= 8 && steps >= QOC_PLAN_GEMM_SMALL_MIN_SLICES)
-                                                 || st_big);
-        const long long lat_work = (long long)Bp * steps;
-        // 16 < n <= 32: the batch kernels work on the ACTIVE 4-row strips qa = ceil(n / 4) of the padded matrices since round 4 and take
-        // over earlier the smaller n is (tools/padded_latency_sweep.py, 500 slices: n = 20 / 24 / 27 / 32 level at ~5 / 6 / 7 / 8.5 control
-        // sets; with a forbidden level the latency mode stays ahead up to 8, at n = 20 up to 7): seeds x slices <= 512 qa, with a state
-        // regulariser min(4096, 768 qa)
-        const int qa = (n + 3) / 4 < 5 ? 5 : (n + 3) / 4;
-        const long long lat_limit = n <= 16 ? (lat_src ? QOC_PLAN_LAT_WORK_SRC : QOC_PLAN_LAT_WORK)
-                                            : (lat_src ? std::min<long long>(QOC_PLAN_LAT_WORK_SRC,
-                                                (long long)QOC_PLAN_LAT_WORK_PER_STRIP_SRC * qa)
-                                                       : (long long)QOC_PLAN_LAT_WORK_PER_STRIP * qa);
-        // NT = 4 (also 32 < n <= 48 with k > 4, padded): 0.268 against 0.458 ms (GEMM route) for one seed of 500 slices, level at 8; NT =
-        // 3: the competitors are slower (tools/mid_n_sweep.py); state transfer from 25 levels on: 5 .. 8 control sets go to the GEMM route
-        // -- n = 32 x 8: 0.220 against 0.261 ms, with forbidden levels 0.272 / 0.316
-        const int lat_sets = n > 16 ? ((st && qa_g >= 7) ? QOC_PLAN_LAT_SETS_N32_ST_WIDE : QOC_PLAN_LAT_SETS_N32) : (st
-            ? QOC_PLAN_LAT_SETS_N16_ST : QOC_PLAN_LAT_SETS_N16);
-        const bool latency = !ens && cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && mfma_auto && qoc_mfma_latency_ok(d)
-            && steps >= QOC_PLAN_LAT_MIN_SLICES &&
-                              (((n > 48 || (n > 32 && k > 4)) ? (lat_work <= QOC_PLAN_LAT_WORK_NT4 && Bp <= QOC_PLAN_LAT_SETS_NT4)
-                                : n > 32 ? (lat_work <= QOC_PLAN_LAT_WORK_NT3 && Bp <= QOC_PLAN_LAT_SETS_NT3)
-                                         : (lat_work <= lat_limit && Bp <= lat_sets)) ||
-                               (Bp == 1 && steps <= QOC_PLAN_LAT_SINGLE_MAX_SLICES));
-        AutoPlan p;
-        p.latency = latency;
-        p.gemm_direct = direct_ok && (!antiherm || cfg->chunks == 1 || (cfg->chunks == 0 && Bp >= ST_DIRECT_FROM));
-        p.path = cfg->path != QOC_PATH_AUTO ? cfg->path
-                 : latency ? QOC_PATH_MFMA : (mfma_auto
-                     && !prefer_gemm) ? QOC_PATH_MFMA : (gemm_ok ? QOC_PATH_GEMM : (st_ok ? QOC_PATH_ST_FUSED : QOC_PATH_GENERIC));
-        return p;
-    };
-    const AutoPlan plan = plan_for(d.Bplan);
-    const bool latency_auto = plan.latency, gemm_direct = plan.gemm_direct;
-    path = plan.path;
-    // n <= 12, one or a few control sets (the reference's own use) and small batches: the workgroup-resident iteration (csrc/qoc_small.h) --
-    // 5-20 us per iteration where the paths above pay 42-57 us of launches and dependent round trips whatever n (profiles/r06_small_n_latency.txt)
-    // (QOC_EXPERIMENTAL=1 QOC_SMALL_AUTO=0: AUTO as it was before round 6, for A/B runs -- tools/small_n_latency.py)
-    if (!ens && cfg->path == QOC_PATH_AUTO && cfg->variant == 0 && cfg->chunks == 0 && cfg->time_shards < 1 && !qoc_exp_is("QOC_SMALL_AUTO", 0) && qoc_small_auto(d, antiherm))
-        path = QOC_PATH_SMALL;
-    if (cfg->gradient == 1) path = QOC_PATH_GENERIC;             // (whatever AUTO's table says: the exact gradient has one home)
-    if (d.Bplan < B && cfg->gradient != 1) {
-        // a plan for FEWER control sets than the engine holds is legal (a rank that holds several shards of a planned batch keeps
-        // bit-identity with them) but can cost a factor: say so once when it changes what AUTO would have picked for the resident batch
-        const AutoPlan own = plan_for(B);
-        if (own.path != plan.path || own.latency != plan.latency || own.gemm_direct != plan.gemm_direct)
-            fprintf(stderr, "libqoc_hip: note: plan_seeds = %d < n_seeds = %d changes the AUTO plan (path %d%s instead of %d%s): kernels "
-                "tuned for the smaller batch run on the larger one\n",
-                    d.Bplan, B, plan.path, plan.latency ? " latency mode" : "", own.path, own.latency ? " latency mode" : "");
-    }
-    if (cfg->time_shards >= 1) {
-        if (cfg->time_rank < -1 || cfg->time_rank >= cfg->time_shards) return bail(fail(QOC_ERR_INVALID,
-            "qoc_create: time_rank %d of %d time shards", cfg->time_rank, cfg->time_shards));
-        if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_GEMM) return bail(fail(QOC_ERR_INVALID,
-            "qoc_create: time sharding runs on the GEMM path"));
-        path = QOC_PATH_GEMM;
-    }
-    if (path == QOC_PATH_MFMA && !mfma_ok)
-        return bail(fail(QOC_ERR_INVALID, "qoc_create: MFMA path needs n <= 64, m <= 16, k <= 8, a Taylor degree of 1 .. 22 and, in state "
-            "transfer, exactly anti-Hermitian generators (n=%d m=%d k=%d T=%d)", n, m, k, d.T));
-    if (path == QOC_PATH_ST_FUSED && !st_ok)
-        return bail(fail(QOC_ERR_INVALID,
-            "qoc_create: fused state-transfer path needs state_transfer, n <= 64, m <= 4, k <= 8 (n=%d m=%d k=%d)", n, m, k));
-    if (path == QOC_PATH_GEMM && !gemm_ok)
-        return bail(fail(QOC_ERR_INVALID,
-            "qoc_create: GEMM path needs m <= 32 and, in state transfer, exactly anti-Hermitian generators or n <= 64, m <= 8 (m=%d)", m));
-    if (path < QOC_PATH_GENERIC || path > QOC_PATH_SMALL) return bail(fail(QOC_ERR_INVALID, "qoc_create: unknown path %d", path));
-    e->path = path;
-    e->chunks = 1;
-#ifdef QOC_DEBUG     // timing experiments only (tools/skip_timing.py builds its own library with -DQOC_DEBUG): never in the product library
-    // wall-clock attribution of one kernel group (results are garbage)
-    if (const char* sk = getenv("QOC_DEBUG_SKIP")) {
-        e->skip_mask = atoi(sk);
-        if (e->skip_mask) fprintf(stderr, "libqoc_hip: WARNING: QOC_DEBUG_SKIP=%d is set -- kernel groups are skipped or repeated, every "
-            "result of this engine is garbage (timing experiments only)\n", e->skip_mask);
-    }
-#endif
-    if (path == QOC_PATH_MFMA) {
-        std::string msg;
-        e->mf.variant = latency_auto ? 5 : cfg->variant;
-        if (cfg->variant == 5 && !qoc_mfma_latency_ok(d))
-            return bail(fail(QOC_ERR_INVALID, "qoc_create: the latency mode of the MFMA path (variant 5) needs n <= 32 with k <= 8 (or, "
-                "with at most 4 dressed forbidden levels, n <= 64), "
-                                              "a Taylor degree >= 2 (n=%d k=%d T=%d)", n, k, d.T));
-        // state transfer: sum_{j < T} A^j / j! is the polynomial of degree T - 1 (no squarings: d.s = 0)
-        d.T = qoc_mfma_degree(d);
-        rc = qoc_mfma_setup(e->mf, d, cfg->chunks, (const cplx*)Hs, e->allocs, msg);
-        if (rc) return bail(fail(rc, "qoc_create: %s", msg.c_str()));
-        e->chunks = e->mf.C;
-    } else if (path == QOC_PATH_GEMM) {
-        std::string msg;
-        if (cfg->time_shards >= 1) { e->gm.ts_G = cfg->time_shards; e->gm.ts_rank = cfg->time_rank; }
-        e->gm.antiherm = antiherm;
-        e->gm.direct_variant = cfg->path == QOC_PATH_GEMM ? cfg->variant : 0;
-        rc = qoc_gemm_setup(e->gm, d, (const cplx*)Hs, gemm_direct, e->allocs, msg);
-        if (rc) return bail(fail(rc, "qoc_create: %s", msg.c_str()));
-        if (!qoc_gemm_lds_opt_in()) return bail(fail(QOC_ERR_HIP, "qoc_create: cannot reserve LDS for the GEMM-path kernels"));
-        e->chunks = e->gm.NC;
-        e->gm.reduce_in_tail = !ens && tail_kind(e) == TAIL_SPLIT_PARTIALS;   // (an ensemble reduces the members' gradients first)      // (the split tail sums the gradient partials: one launch less)
-        if (e->gm.ts_G > 0) {
-            std::string why;
-            if (!qoc_gemm_ts_supported(e->gm, d, e->gm.ts_G, why))
-                return bail(fail(QOC_ERR_INVALID, "qoc_create: time_shards = %d needs %s (n=%d m=%d chunks=%d)", e->gm.ts_G, why.c_str(), n,
-                    m, e->gm.NC));
-            qoc_gemm_ts_ranges(e->gm, e->gm.ts_G);
-        }
-    } else if (path == QOC_PATH_SMALL) {
-        std::string msg;
-        rc = qoc_small_setup(e->sm, d, antiherm, cfg->chunks, cfg->variant, e->allocs, msg);
-        if (rc) return bail(fail(rc == -1 ? QOC_ERR_INVALID : (rc == -3 ? QOC_ERR_NOMEM : QOC_ERR_HIP), "qoc_create: %s (n=%d m=%d k=%d T=%d steps=%d seeds=%d)",
-            msg.c_str(), n, m, k, d.T, steps, B));
-        e->chunks = e->sm.G;
-        // read-back (inter_vecs, final_state, unitary_scale) runs the any-size kernels on the controls of the last evaluation
-        if (!cfg->state_transfer) {
-            ALLOC(e->K, (size_t)B * steps * nn);
-            int grid = B * steps;
-            if (grid > 4096) grid = 4096;
-            e->expm_grid = grid;
-            ALLOC(e->expm_scratch, (size_t)grid * 3 * nn);
-            ALLOC(e->seed_scratch, (size_t)B * (2 * nn + 2 * nm));
-        } else {
-            ALLOC(e->seed_scratch, (size_t)B * (nn + 3 * nm));
-        }
-    } else if (!cfg->state_transfer) {
-        ALLOC(e->K, (size_t)B * steps * nn);
-        int grid = B * steps;
-        if (grid > 4096) grid = 4096;
-        e->expm_grid = grid;
-        ALLOC(e->expm_scratch, (size_t)grid * 3 * nn);
-        ALLOC(e->seed_scratch, (size_t)B * (2 * nn + 2 * nm));
-    } else if (path == QOC_PATH_GENERIC) {
-        ALLOC(e->seed_scratch, (size_t)B * (nn + 3 * nm));
-    }
-    if (cfg->gradient == 1) {
-        if (const char* why = qoc_exact_plan(e->xg, d)) return bail(fail(QOC_ERR_INVALID, "qoc_create: %s (T=%d s=%d)", why, d.T, d.s));
-        ALLOC(e->xg.Lam, (size_t)B * steps * nm);
-        ALLOC(e->xg.scratch, (size_t)e->xg.grid * e->xg.per_wg);
-        if (qoc_exact_lds_opt_in(e->xg) != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create: cannot reserve %zu bytes of LDS for the exact gradient kernel",
-            e->xg.lds_bytes));
-    }
-    if (ens) {
-        // the group view: the caller's G control sets of k controls -- variable, Adam slots, stop rule, pulse regularisers, the tail's arrays
-        const qoc_config* uc = ens->user;
-        const qoc_ensemble* en = ens->ens;
-        QocDev& gv = e->g;
-        gv = d;
-        const int kg = uc->k, G = uc->n_seeds, E = en->members, q = en->n_perturb;
-        // (a pulse response: the group view is the sample view -- P samples of total_time / P each stand where the time slices stood, so the
-        // pulse regularisers act on the samples with their coefficients divided by P)
-        const ShapeHost* shp = ens->shape;
-        const int gsteps = shp ? shp->P : steps;
-        const double inv_gsteps = shp ? 1.0 / (double)gsteps : inv_steps;
-        const size_t gks = (size_t)kg * gsteps;
-        gv.k = kg; gv.B = G; gv.Bplan = G;
-        if (shp) { gv.steps = gsteps; gv.dt = uc->total_time / (double)gsteps; }
-        gv.has_amp = uc->has_amplitude; gv.a_amp = uc->c_amplitude * inv_gsteps;
-        gv.has_env = uc->has_envelope; gv.a_env = uc->c_envelope * inv_gsteps;
-        gv.has_dwdt = uc->has_dwdt; gv.a_dwdt = uc->c_dwdt * inv_gsteps;
-        gv.has_d2wdt2 = uc->has_d2wdt2; gv.a_d2wdt2 = uc->c_d2wdt2 * inv_gsteps;
-        gv.has_band = uc->has_bandpass; gv.a_band = uc->c_bandpass * inv_gsteps;
-        gv.band_lo = uc->band_lo; gv.band_hi = uc->band_hi;
-        gv.inter = nullptr; gv.Xfinal = nullptr; gv.ztau = nullptr; gv.Fpop = nullptr; gv.Fd = nullptr; gv.zfin = nullptr; gv.su_resid = nullptr;
-        gv.omg = nullptr; gv.band_ph = nullptr; gv.band_tw = nullptr; gv.band_mag = nullptr; gv.band_dR = nullptr;
-        if ((rc = dev_upload(e, &gv.maxA, ens->maxA, (size_t)kg))) return bail(rc);
-        if (ens->one_minus_gauss && (rc = dev_upload(e, &gv.omg, ens->one_minus_gauss, gks))) return bail(rc);
-        ALLOC(gv.base, G * gks); ALLOC(gv.adam_m, G * gks); ALLOC(gv.adam_v, G * gks);
-        ALLOC(gv.adam_t, (size_t)G); ALLOC(gv.iters, (size_t)G); ALLOC(gv.done, (size_t)G);
-        ALLOC(gv.w, G * gks); ALLOC(gv.u, G * gks); ALLOC(gv.w2, G * gks); ALLOC(gv.u2, G * gks); ALLOC(gv.dLdu, G * gks); ALLOC(gv.grad, G * gks);
-        ALLOC(gv.loss, (size_t)G); ALLOC(gv.reg_state, (size_t)G); ALLOC(gv.reg_loss, (size_t)G); ALLOC(gv.g2, (size_t)G); ALLOC(gv.uscale, (size_t)G);
-        if (gv.has_band) { ALLOC(gv.band_ph, G * gks); ALLOC(gv.band_tw, (size_t)gsteps); ALLOC(gv.band_mag, G * gks); ALLOC(gv.band_dR, G * gks); }
-        if (gks > 4 * 1024 && !qoc_exp_is("QOC_FINISH_SPLIT", 0)) {
-            e->fin_S = (int)((gks + 255) / 256);
-            if (e->fin_S > 64) e->fin_S = 64;
-            ALLOC(e->fin_part, (size_t)G * (e->fin_S + 2) * 2);
-        }
-        const double* da = nullptr; const double* dd = nullptr; const double* dw = nullptr;
-        if ((rc = dev_upload(e, &da, en->amp_scales, (size_t)E * kg))) return bail(rc);
-        if (q > 0 && (rc = dev_upload(e, &dd, en->offsets, (size_t)E * q))) return bail(rc);
-        if ((rc = dev_upload(e, &dw, en->weights, (size_t)E))) return bail(rc);
-        e->en = QocEns{E, q, da, dd, dw};
-        e->ens_wt.assign(en->weights, en->weights + E);
-        if (hipMemset(gv.base, 0, G * gks * sizeof(double)) != hipSuccess || hipMemset(gv.adam_m, 0, G * gks * sizeof(double)) != hipSuccess ||
-            hipMemset(gv.adam_v, 0, G * gks * sizeof(double)) != hipSuccess || hipMemset(gv.adam_t, 0, G * sizeof(int)) != hipSuccess ||
-            hipMemset(gv.iters, 0, G * sizeof(int)) != hipSuccess || hipMemset(gv.done, 0, G * sizeof(int)) != hipSuccess ||
-            hipMemset(gv.uscale, 0, G * sizeof(double)) != hipSuccess)
-            return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: clearing the state buffers failed"));
-        if (gv.has_band) {
-            hipLaunchKernelGGL(k_band_twiddles, dim3((gsteps + 255) / 256), dim3(256), 0, 0, gv.band_tw, gsteps);
-            if (hipGetLastError() != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create_ensemble: the bandpass phase table could not be formed"));
-        }
-        if (shp) {
-            QocShape& sh = e->sh;
-            sh.P = shp->P; sh.band = shp->band; sh.col_band = shp->col_band;
-            if ((rc = dev_upload(e, &sh.Tt, shp->Tt.data(), (size_t)steps * gsteps))) return bail(rc);
-            if ((rc = dev_upload(e, &sh.row_win, shp->row_win.data(), (size_t)steps))) return bail(rc);
-            if ((rc = dev_upload(e, &sh.col_win, shp->col_win.data(), (size_t)gsteps))) return bail(rc);
-            ALLOC(sh.uf, (size_t)G * kg * steps);
-            e->shaped = true;
-        }
-    }
-#undef ALLOC
-    {
-        const hipError_t se = hipDeviceSynchronize();
-        if (se != hipSuccess) return bail(fail(QOC_ERR_HIP, "qoc_create: %s", hipGetErrorString(se)));
-    }
-    *out = e;
-    return QOC_OK;
-}
-
 int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const double* V, const double* W,
                const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
                const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    return create_engine(cfg, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, nullptr, out);
+    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, nullptr, out);
 }
 
 // qoc_create_ensemble and qoc_create_shaped (`who` names the caller in the messages; shape: the prepared response of the latter, else null)
-static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0,
-                          const double* V, const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                          const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    if (!cfg || !ens || !Hs || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, Problem p,
+                          qoc_handle* out) {
+    if (!cfg || !ens || !p.Hs || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int E = ens->members, q = ens->n_perturb;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
     if (!ens->amp_scales || !ens->weights || (q > 0 && (!ens->P || !ens->offsets)))
@@ -999,7 +994,7 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
     if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
         return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
     if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "%s: %d x %d trajectories", who, cfg->n_seeds, E);
-    if (cfg->has_envelope && !one_minus_gauss) return fail(QOC_ERR_INVALID, "%s: envelope constant missing", who);
+    if (cfg->has_envelope && !p.one_minus_gauss) return fail(QOC_ERR_INVALID, "%s: envelope constant missing", who);
     if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "%s: d2wdt2 needs dwdt (reference: NameError new_weights)", who);
     for (int i = 0; i < E; ++i)
         if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "%s: weight %d is %g", who, i, ens->weights[i]);
@@ -1022,18 +1017,20 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
     tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
     tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
     std::vector<double> Hst(2 * nn * (size_t)(k + q + 1));
-    memcpy(Hst.data(), Hs, 2 * nn * (size_t)(k + 1) * sizeof(double));
+    memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(k + 1) * sizeof(double));
     if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(k + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
-    std::vector<double> maxAt(maxA, maxA + k);
+    std::vector<double> maxAt(p.maxA, p.maxA + k);
     maxAt.resize((size_t)(k + q), 1.0);
-    const EnsArgs ea{cfg, maxA, cfg->has_envelope ? one_minus_gauss : nullptr, ens, shape};
-    return create_engine(&tc, Hst.data(), U0, V, W, maxAt.data(), nullptr, forbidden_states, forbidden_coeffs, Vs, &ea, out);
+    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape};
+    p.Hs = Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
+    return create_engine(&tc, p, &ea, out);
 }
 
 int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
                         const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
                         const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    return create_members("qoc_create_ensemble", nullptr, cfg, ens, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, out);
+    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
+    return create_members("qoc_create_ensemble", nullptr, cfg, ens, p, out);
 }
 
 int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
@@ -1046,11 +1043,8 @@ int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
     if (!tr->T) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the response matrix is missing");
     if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the envelope regulariser is defined per time slice, not per sample");
     // the response: finite, every sample reaches the pulse; the nonzero window of every row and column and the transposed copy
-    ShapeHost sh;
-    sh.P = P; sh.band = 0; sh.col_band = 0;
-    sh.Tt.resize((size_t)P * steps);
-    sh.row_win.assign((size_t)steps, make_int2(0, 0));
-    sh.col_win.assign((size_t)P, make_int2(0, 0));
+    ShapeHost sh{P, 0, 0, std::vector<double>((size_t)P * steps), std::vector<int2>((size_t)steps, make_int2(0, 0)),
+                 std::vector<int2>((size_t)P, make_int2(0, 0))};
     for (int t = 0; t < steps; ++t)
         for (int p = 0; p < P; ++p) {
             const double v = tr->T[(size_t)t * P + p];
@@ -1073,7 +1067,8 @@ int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
     // no ensemble: one nominal member
     const std::vector<double> ones((size_t)k + 1, 1.0);
     const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    return create_members("qoc_create_shaped", &sh, cfg, ens ? ens : &nominal, Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs, out);
+    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
+    return create_members("qoc_create_shaped", &sh, cfg, ens ? ens : &nominal, p, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1227,13 +1222,11 @@ int qoc_get_uks(qoc_handle e, double* uks) {
     const QocDev& d = sets(e);
     // uks = maxA[k] * sin(base) of the CURRENT variable (run_session.py:112-117), evaluated on the device
     const int total = d.B * d.k * d.steps;
-    int cgrid = (total + QOC_BLOCK - 1) / QOC_BLOCK;
-    if (cgrid > 2048) cgrid = 2048;
     // (into u2 / w2: u / w keep the controls of the last evaluation for qoc_get_uks_evaluated and the regularisers' read-backs)
     if (!e->controls_ready) {
         QocDev dd = d;
         dd.u = d.u2; dd.w = d.w2;
-        hipLaunchKernelGGL(k_controls, dim3(cgrid), dim3(QOC_BLOCK), 0, e->stream, dd);
+        launch_controls(dd, e->stream);
         HIP_TRY(hipGetLastError());
         e->controls_ready = true;
     }
@@ -1329,17 +1322,17 @@ int qoc_profile_enable(qoc_handle e, int32_t on) {
 int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, double* total_ms) {
     CHECK_H(e);
     TRY(prof_collect(e));
+    // the MFMA path's kernel of the exponentials by its variant 2 .. 8 (else k_mfma_expm_chunk; 5 with NT = 3: k_mfma_expm_rows per slice)
+    static const char* const expm[] = {"k_mfma_expm_chunk4", "k_mfma_expm_chunk4w", "k_mfma_expm_chunk4s",
+        "k_mfma_expm_slice2 + k_mfma_chain_rows", "k_mfma_expm_pair", "k_mfma_expm_rows", "k_mfma_expm_inplace"};
+    const int v = e->path == QOC_PATH_MFMA ? qoc_mfma_expm_variant(e->mf, e->d) : 0;
     if (kernel_name)
-        *kernel_name = e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)" : e->path == QOC_PATH_GEMM ? (e->gm.direct ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
-                                                 : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched "
-                                                     "matexp sequence)")
-                       : e->path == QOC_PATH_MFMA ? (qoc_mfma_expm_variant(e->mf, e->d) == 7 ? "k_mfma_expm_rows"
-                           : qoc_mfma_expm_variant(e->mf, e->d) == 6 ? "k_mfma_expm_pair" : qoc_mfma_expm_variant(e->mf, e->d) == 5
-                           ? (e->mf.NT == 3 ? "k_mfma_expm_rows (per slice) + k_mfma_chain_rows" : "k_mfma_expm_slice2 + "
-                           "k_mfma_chain_rows") : qoc_mfma_expm_variant(e->mf, e->d) == 8 ? "k_mfma_expm_inplace"
-                           : qoc_mfma_expm_variant(e->mf, e->d) == 4 ? "k_mfma_expm_chunk4s" : qoc_mfma_expm_variant(e->mf, e->d) == 3
-                           ? "k_mfma_expm_chunk4w" : qoc_mfma_expm_variant(e->mf, e->d) == 2 ? "k_mfma_expm_chunk4" : "k_mfma_expm_chunk")
-                       : (e->path == QOC_PATH_ST_FUSED ? "k_st_fwd_fused" : (e->d.state_transfer ? "k_st_fwd_generic" : "k_expm_generic"));
+        *kernel_name = e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
+                       : e->path == QOC_PATH_GEMM ? (e->gm.direct ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
+                           : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
+                       : e->path == QOC_PATH_MFMA ? (v == 5 && e->mf.NT == 3 ? "k_mfma_expm_rows (per slice) + k_mfma_chain_rows"
+                           : v >= 2 && v <= 8 ? expm[v - 2] : "k_mfma_expm_chunk")
+                       : e->path == QOC_PATH_ST_FUSED ? "k_st_fwd_fused" : (e->d.state_transfer ? "k_st_fwd_generic" : "k_expm_generic");
     if (launches) *launches = e->prof_launches;
     if (total_ms) *total_ms = e->prof_ms;
     return QOC_OK;
@@ -1396,21 +1389,21 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
         snprintf(tmp, sizeof tmp, "path=%s", e->path == QOC_PATH_ST_FUSED ? "st_fused" : "generic");
     }
     // the kernel of the Adam tail (tail_kind) and where its elements live: registers while ks <= QFE x threads (finish_body's in_regs)
-    const int ks = sets(e).k * sets(e).steps, w = (int)strlen(tmp);
+    auto add = [&tmp](const char* fmt, auto... a) { const size_t w = strlen(tmp); snprintf(tmp + w, sizeof tmp - w, fmt, a...); };
+    const int ks = sets(e).k * sets(e).steps;
     const TailKind tail = tail_kind(e);
-    if (tail == TAIL_IN_LAUNCH) snprintf(tmp + w, sizeof tmp - w, " tail=in_launch");
-    else if (tail == TAIL_SPLIT || tail == TAIL_SPLIT_PARTIALS)
-        snprintf(tmp + w, sizeof tmp - w, " tail=split%d%s", e->fin_S, tail == TAIL_SPLIT_PARTIALS ? "_partials" : "");
-    else if (tail == TAIL_LATENCY_FUSED)
-        snprintf(tmp + w, sizeof tmp - w, " tail=latency_fused_%s", ks <= QF_E * 64 * (16 / e->mf.NT) * e->mf.NT ? "regs" : "memory");
+    if (tail == TAIL_IN_LAUNCH) add(" tail=%s", "in_launch");
+    else if (tail == TAIL_SPLIT) add(" tail=split%d", e->fin_S);
+    else if (tail == TAIL_SPLIT_PARTIALS) add(" tail=split%d_partials", e->fin_S);
+    else if (tail == TAIL_LATENCY_FUSED) add(" tail=latency_fused_%s", ks <= QF_E * 64 * (16 / e->mf.NT) * e->mf.NT ? "regs" : "memory");
     else {
         const int threads = ks >= 2048 ? 1024 : QOC_BLOCK, qfe = tail == TAIL_FINISH8 ? 8 : QF_E;
-        snprintf(tmp + w, sizeof tmp - w, " tail=finish%d_%s", threads, tail == TAIL_FINISH8 ? "regs8" : (ks <= qfe * threads ? "regs" : "memory"));
+        add(" tail=finish%d_%s", threads, tail == TAIL_FINISH8 ? "regs8" : (ks <= qfe * threads ? "regs" : "memory"));
     }
     // ensemble engines only (the plain engines' line stays as it was)
-    if (e->ens_E) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " members=%d perturbations=%d", e->ens_E, e->en.q); }
-    if (e->shaped) { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " samples=%d band=%d", e->sh.P, e->sh.band); }
-    { const int w2 = (int)strlen(tmp); snprintf(tmp + w2, sizeof tmp - w2, " gradient=%s", e->xg.on ? "exact" : "first_order"); }
+    if (e->ens_E) add(" members=%d perturbations=%d", e->ens_E, e->en.q);
+    if (e->shaped) add(" samples=%d band=%d", e->sh.P, e->sh.band);
+    add(" gradient=%s", e->xg.on ? "exact" : "first_order");
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }
