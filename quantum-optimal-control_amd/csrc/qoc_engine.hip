@@ -1360,6 +1360,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
+// exact engines add exact_variant=<lds|global> exact_lds=<bytes of dynamic LDS, 0 in the global variant> exact_grid=<workgroups of k_exact_grad>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
     char tmp[384];
@@ -1404,6 +1405,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (e->ens_E) add(" members=%d perturbations=%d", e->ens_E, e->en.q);
     if (e->shaped) add(" samples=%d band=%d", e->sh.P, e->sh.band);
     add(" gradient=%s", e->xg.on ? "exact" : "first_order");
+    // exact engines only: where k_exact_grad keeps its generator and vector blocks, its dynamic LDS and its grid (qoc_exact_plan)
+    if (e->xg.on) add(" exact_variant=%s exact_lds=%zu exact_grid=%d", e->xg.lds ? "lds" : "global", e->xg.lds_bytes, e->xg.grid);
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }
