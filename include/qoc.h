@@ -41,6 +41,8 @@ extern "C" {
                                 * inside one launch -- a row of 16 lanes per time slice, matrices column-per-lane in registers, plain complex-fp64 FMAs
                                 * (v_fmac_f64_dpp), product tree in LDS, several workgroups per control set for long pulses (csrc/qoc_small.h); AUTO for
                                 * one or a few control sets of the sizes the reference is used at (qubits, qutrits, two / three transmons) */
+#define QOC_PATH_LINDBLAD 6    /* engines made by qoc_create_open only: n <= 32, density operators of the pairs of states of interest resident in LDS,
+                                * plain complex-fp64 FMAs (csrc/qoc_lindblad.h) */
 
 typedef struct qoc_engine* qoc_handle;
 
@@ -187,6 +189,37 @@ int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
 /* u_f of the last evaluation, [n_seeds][k][steps] (the nominal pulse, before any member's amplitude scale).  QOC_ERR_STATE on an engine
  * not made by qoc_create_shaped. */
 int qoc_get_pulse(qoc_handle h, double* u);
+
+/* ---- open-system GRAPE: the pulse is scored and optimised under a Lindblad master equation (no counterpart in the reference, whose graph
+ * propagates state vectors) ----------------------------------------------------------------------------------------------------------------
+ * Collapse operators C_j are n x n and carry the square root of their rates; the caller passes D_j = sqrt(dt) C_j.  With H' = -i dt H as in Hs:
+ *   A_t = H0' + sum_k u_k[t] H_k' - 1/2 sum_j D_j^dagger D_j,   L_t(X) = A_t X + X A_t^dagger + sum_j D_j X D_j^dagger
+ * Slice map: N = 2^scaling sub-steps, each X <- sum_{j = 0 .. taylor_terms} (L_t / N)^j X / j! (terms as a chain, summed in ascending j).  The
+ * convention is the SAME in unitary and state-transfer mode: degree taylor_terms and 2^scaling sub-steps in both -- not the closed engine's degree
+ * taylor_terms - 1 without squarings in state transfer.
+ * The operators rho_ij(0) = psi_i psi_j^dagger of the m start vectors (U0 V in unitary mode, V in state transfer) are propagated and scored against
+ * sigma_ij = w_i w_j^dagger (columns of W):
+ *   loss          = 1 - (1 / m^2) sum_ij Re Tr(sigma_ij^dagger rho_ij(T))   (with n_collapse = 0: the closed engine's loss exactly; the relative
+ *                                                                            phases of a gate are scored without a process-tomography basis)
+ *   unitary_scale = (1 / m) sum_i Re Tr rho_ii(T)                           (1 for a trace-preserving map);  the state regulariser is 0
+ *   grad          : first order as the reference's -- Lambda_ij(T) = -sigma_ij / m^2 carried back by the adjoint slice map,
+ *                   dL/du[k, t] = sum_ij Re <Lambda_ij(t+1), H_k' rho_ij(t+1) + rho_ij(t+1) H_k'^dagger>; pulse regularisers, chain rule, Adam tail and
+ *                   stop rule as on every engine, so qoc_eval, qoc_adam_step, qoc_iterate, qoc_run_adam, qoc_get_scalars, qoc_get_uks* and
+ *                   qoc_set_base / qoc_get_base work as they are
+ * Accepted: n_collapse = 0 (the closed limit), cfg.path AUTO or QOC_PATH_LINDBLAD, both modes, any n_seeds.  QOC_ERR_INVALID, before any device is
+ * touched: forbidden levels, speed_up, forbid_dressed; gradient = 1; time_shards > 0; any other explicit path; n > 32, n_collapse > 8, m > n or
+ * (n_collapse + 4) n (n | 1) 16 bytes > 159 KiB of LDS; taylor_terms < 1 or > 60; scaling > 12.  qoc_get_final_unitary, qoc_get_inter_vecs and the
+ * member and pulse read-backs return QOC_ERR_STATE on such an engine; the two read-backs below return it on every other engine. */
+typedef struct qoc_open {
+    int32_t n_collapse;         /* c >= 0 */
+    const double* C;            /* [c][n][n] complex: sqrt(dt) C_j; NULL when c = 0 */
+} qoc_open;
+int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* Hs, const double* U0, const double* V, const double* W,
+                    const double* maxA, const double* one_minus_gauss, qoc_handle* out);
+/* rho_ij(T) of the last evaluation, [n_seeds][m][m][n][n] complex: the pairs i > j mirrored from rho_ji (rho_ij = rho_ji^dagger) */
+int qoc_get_final_density(qoc_handle h, double* rho);
+/* Re rho_ii(tau)[l][l] of the last evaluation, [n_seeds][steps+1][n][m] (tau = 0 is the start): the populations a closed run derives from inter_vecs */
+int qoc_get_populations(qoc_handle h, double* pop);
 
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).

@@ -29,6 +29,7 @@
 #include "qoc_ensemble.h"
 #include "qoc_transfer.h"
 #include "qoc_exact_grad.h"
+#include "qoc_lindblad.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
 // (QOC_PLAN_LAT_WORK = 4608 seeds x time slices: since the batch sweeps take their chunk boundaries and final_state from k_mfma_bnd_scan
@@ -101,6 +102,8 @@ struct qoc_engine {
     QocShape sh{};
     // exact gradient (qoc_config.gradient = 1, csrc/qoc_exact_grad.h): the generic path's forward, a costate-storing sweep and k_exact_grad
     QocExact xg{};
+    // open-system GRAPE (qoc_create_open, csrc/qoc_lindblad.h): density operators of the pairs of states of interest under a Lindblad master equation
+    QocLb lb{};
 };
 
 // the view that holds the control sets: the engine itself, or the group view of an ensemble engine
@@ -357,6 +360,11 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
         if (bracket_bwd) TRY(prof_begin(e));
         qoc_gemm_backward(e->gm, d, e->stream);
         if (bracket_bwd) TRY(prof_end(e));
+    } else if (e->path == QOC_PATH_LINDBLAD) {                          // open system: forward, backward, reduce (csrc/qoc_lindblad.h)
+        TRY(prof_begin(e));
+        qoc_lb_forward(e->lb, d, e->stream);
+        TRY(prof_end(e));
+        qoc_lb_backward(e->lb, d, e->stream);
     } else if (e->path == QOC_PATH_ST_FUSED) {
         TRY(prof_begin(e));
         st_fused_launch(d, e->stream, true);
@@ -905,7 +913,37 @@ static int setup_group_view(qoc_engine* e, const EnsArgs& a) {
     return QOC_OK;
 }
 
-static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out) {
+// the buffers of an open engine: collapse operators, the drift with -1/2 sum_j D_j^dagger D_j folded in, history, partials, populations
+static int setup_lindblad(qoc_engine* e, const Problem& p, const qoc_open* op) {
+    const QocDev& d = e->d;
+    QocLb& L = e->lb;
+    const int n = d.n, c = op->n_collapse;
+    const size_t nn = (size_t)n * n, B = (size_t)d.B;
+    L.on = 1; L.c = c; L.R = d.m * (d.m + 1) / 2; L.S = qoc_lb_stride(n); L.lds_bytes = qoc_lb_lds_bytes(n, c);
+    std::vector<double> h0(p.Hs, p.Hs + 2 * nn);
+    for (int j = 0; j < c; ++j) {
+        const double* D = op->C + 2 * nn * (size_t)j;
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) {
+                double re = 0.0, im = 0.0;                       // (D^dagger D)[a][b] = sum_l conj(D[l][a]) D[l][b]
+                for (int l = 0; l < n; ++l) {
+                    const double xr = D[2 * (l * n + a)], xi = D[2 * (l * n + a) + 1], yr = D[2 * (l * n + b)], yi = D[2 * (l * n + b) + 1];
+                    re += xr * yr + xi * yi;
+                    im += xr * yi - xi * yr;
+                }
+                h0[2 * (a * n + b)] -= 0.5 * re; h0[2 * (a * n + b) + 1] -= 0.5 * im;
+            }
+    }
+    TRY(dev_upload(e, &L.H0, (const cplx*)h0.data(), nn));
+    if (c > 0) TRY(dev_upload(e, &L.D, (const cplx*)op->C, (size_t)c * nn));
+    TRY(dev_alloc(e, &L.hist, B * L.R * d.steps * nn));
+    TRY(dev_alloc(e, &L.partial, B * L.R * d.k * d.steps));
+    TRY(dev_alloc(e, &L.pop, B * (d.steps + 1) * n * d.m));
+    HIP_TRY_MSG(qoc_lb_lds_opt_in(L), "qoc_create_open: cannot reserve %zu bytes of LDS for the open-system kernels", L.lds_bytes);
+    return QOC_OK;
+}
+
+static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out, const qoc_open* open = nullptr) {
     TRY(check_create_args(cfg, p, out));
     HIP_TRY(hipSetDevice(cfg->device));
     // the half-built engine owns itself: every early return below destroys it (fail() has set the message by then)
@@ -918,6 +956,7 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
     memset(&d, 0, sizeof d);
     d.n = cfg->n; d.k = cfg->k; d.steps = cfg->steps; d.m = cfg->m; d.T = cfg->taylor_terms; d.s = cfg->state_transfer ? 0 : cfg->scaling;
     d.B = cfg->n_seeds; d.state_transfer = cfg->state_transfer; d.dt = cfg->dt;
+    if (open) d.s = cfg->scaling;                                // (an open engine takes sub-steps in both modes)
     d.Bplan = cfg->plan_seeds > 0 ? cfg->plan_seeds : cfg->n_seeds;
     fill_pulse_regularisers(d, *cfg);
     d.has_speed = cfg->has_speed_up; d.a_speed = cfg->c_speed_up * (1.0 / (double)cfg->steps);
@@ -927,8 +966,11 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
     HIP_TRY_MSG(hipEventCreate(&e->t1), "hipEventCreate failed");
     TRY(build_trajectory_view(e, p));
     const bool antiherm = cfg->state_transfer ? qoc_all_antihermitian((const cplx*)p.Hs, cfg->n, cfg->k + 1) : true;
-    AutoPlan plan;
-    TRY(choose_path(*cfg, d, antiherm, ens != nullptr, plan));
+    AutoPlan plan{};
+    // (an open engine has been through build_trajectory_view like every engine: d.inter, d.Xfinal, d.ztau and zfin are allocated there and never
+    // touched by the open path -- (steps + 1) n m + n^2 numbers per control set, small beside its history; left so as not to fork that helper)
+    if (open) plan.path = QOC_PATH_LINDBLAD;                     // (one home, as the exact gradient has: no table to consult)
+    else TRY(choose_path(*cfg, d, antiherm, ens != nullptr, plan));
     e->path = plan.path; e->chunks = 1;
 #ifdef QOC_DEBUG     // timing experiments only (tools/skip_timing.py builds its own library with -DQOC_DEBUG): never in the product library
     if (const char* sk = getenv("QOC_DEBUG_SKIP")) {             // wall-clock attribution of one kernel group
@@ -937,7 +979,8 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
             "result of this engine is garbage (timing experiments only)\n", e->skip_mask);
     }
 #endif
-    TRY(setup_path(e, p.Hs, antiherm, plan));
+    if (open) TRY(setup_lindblad(e, p, open));
+    else TRY(setup_path(e, p.Hs, antiherm, plan));
     if (cfg->gradient == 1) TRY(setup_exact_gradient(e));
     if (ens) TRY(setup_group_view(e, *ens));
     const hipError_t se = hipDeviceSynchronize();
@@ -981,6 +1024,32 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
                const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
                const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
     return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, nullptr, out);
+}
+
+int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* Hs, const double* U0, const double* V, const double* W,
+                    const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
+    if (!cfg || !open || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_open: null argument");
+    const int n = cfg->n, c = open->n_collapse;
+    if (cfg->n_forbidden > 0) return fail(QOC_ERR_INVALID, "qoc_create_open: forbidden levels are not available under a master equation (n_forbidden = %d)", cfg->n_forbidden);
+    if (cfg->has_speed_up) return fail(QOC_ERR_INVALID, "qoc_create_open: the speed_up regulariser is not available under a master equation");
+    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "qoc_create_open: forbid_dressed is not available under a master equation");
+    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "qoc_create_open: the exact gradient is not available under a master equation (gradient = %d)", cfg->gradient);
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_open: an open system cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_LINDBLAD)
+        return fail(QOC_ERR_INVALID, "qoc_create_open: an open system runs on QOC_PATH_LINDBLAD (or AUTO), not on path %d", cfg->path);
+    if (c < 0 || (c > 0 && !open->C)) return fail(QOC_ERR_INVALID, "qoc_create_open: n_collapse = %d (>= 0) with its operators", c);
+    if (n < 1 || n > QOC_LB_MAX_N) return fail(QOC_ERR_INVALID, "qoc_create_open: n = %d (1 .. %d levels)", n, QOC_LB_MAX_N);
+    if (c > QOC_LB_MAX_C) return fail(QOC_ERR_INVALID, "qoc_create_open: n_collapse = %d (at most %d collapse operators)", c, QOC_LB_MAX_C);
+    if (cfg->m < 1 || cfg->m > n) return fail(QOC_ERR_INVALID, "qoc_create_open: m = %d states of interest (1 .. n = %d)", cfg->m, n);
+    if (qoc_lb_lds_bytes(n, c) > QOC_LB_LDS_LIMIT)
+        return fail(QOC_ERR_INVALID, "qoc_create_open: n = %d with %d collapse operators needs %zu bytes of LDS (limit %zu)", n, c, qoc_lb_lds_bytes(n, c),
+                    QOC_LB_LDS_LIMIT);
+    if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_LB_MAX_T)
+        return fail(QOC_ERR_INVALID, "qoc_create_open: taylor_terms = %d (1 .. %d)", cfg->taylor_terms, QOC_LB_MAX_T);
+    if (cfg->scaling < 0 || cfg->scaling > QOC_LB_MAX_S) return fail(QOC_ERR_INVALID, "qoc_create_open: scaling = %d (0 .. %d)", cfg->scaling, QOC_LB_MAX_S);
+    for (size_t i = 0; i < 2 * (size_t)c * n * n; ++i)
+        if (!std::isfinite(open->C[i])) return fail(QOC_ERR_INVALID, "qoc_create_open: a collapse operator is not finite");
+    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, open);
 }
 
 // qoc_create_ensemble and qoc_create_shaped (`who` names the caller in the messages; shape: the prepared response of the latter, else null)
@@ -1259,6 +1328,7 @@ int qoc_get_pulse(qoc_handle e, double* u) {
 
 int qoc_get_final_unitary(qoc_handle e, double* Uf) {
     CHECK_H(e);
+    if (e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_final_unitary: an open engine has no final unitary (qoc_get_final_density)");
     if (e->d.state_transfer) return fail(QOC_ERR_STATE, "qoc_get_final_unitary: state-transfer mode has no final unitary");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_final_unitary: nothing evaluated yet");
     TRY(refresh_final(e));
@@ -1271,6 +1341,7 @@ int qoc_get_final_unitary(qoc_handle e, double* Uf) {
 
 int qoc_get_inter_vecs(qoc_handle e, double* inter) {
     CHECK_H(e);
+    if (e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_inter_vecs: an open engine propagates no state vectors (qoc_get_populations)");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_inter_vecs: nothing evaluated yet");
     // one rank of a time-sharded run: its own slices, summed over the ranks (a collective)
     if (e->path == QOC_PATH_GEMM) TRY(qoc_gemm_ts_gather_inter(e->gm, e->d, e->stream));
@@ -1284,6 +1355,46 @@ int qoc_get_inter_vecs(qoc_handle e, double* inter) {
     const size_t row = (size_t)(e->d.steps + 1) * e->d.n * e->d.m * sizeof(cplx);
     if (e->ens_E) HIP_TRY(hipMemcpy2D(inter, row, e->d.inter, row * e->ens_E, row, (size_t)e->g.B, hipMemcpyDeviceToHost));   // member 0 of each group
     else HIP_TRY(hipMemcpy(inter, e->d.inter, (size_t)e->d.B * row, hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+int qoc_get_final_density(qoc_handle e, double* rho) {
+    CHECK_H(e);
+    if (!e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_final_density: not an open engine (qoc_create_open)");
+    if (!rho) return fail(QOC_ERR_INVALID, "qoc_get_final_density: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_final_density: nothing evaluated yet");
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const QocDev& d = e->d;
+    const int n = d.n, m = d.m, R = e->lb.R;
+    const size_t nn = (size_t)n * n;
+    std::vector<cplx> blk(nn);
+    for (int b = 0; b < d.B; ++b)
+        for (int i = 0, r = 0; i < m; ++i)
+            for (int j = i; j < m; ++j, ++r) {
+                HIP_TRY(hipMemcpy(blk.data(), e->lb.hist + (((size_t)b * R + r) * d.steps + (d.steps - 1)) * nn, nn * sizeof(cplx), hipMemcpyDeviceToHost));
+                double* up = rho + 2 * ((((size_t)b * m + i) * m + j) * nn);
+                double* lo = rho + 2 * ((((size_t)b * m + j) * m + i) * nn);
+                for (int a = 0; a < n; ++a)
+                    for (int c = 0; c < n; ++c) {
+                        const cplx v = blk[(size_t)a * n + c];
+                        up[2 * (a * n + c)] = v.x; up[2 * (a * n + c) + 1] = v.y;
+                        if (i != j) { lo[2 * (c * n + a)] = v.x; lo[2 * (c * n + a) + 1] = -v.y; }   // rho_ji = rho_ij^dagger
+                    }
+            }
+    return QOC_OK;
+}
+
+int qoc_get_populations(qoc_handle e, double* pop) {
+    CHECK_H(e);
+    if (!e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_populations: not an open engine (qoc_create_open)");
+    if (!pop) return fail(QOC_ERR_INVALID, "qoc_get_populations: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_populations: nothing evaluated yet");
+    const QocDev& d = e->d;
+    const size_t total = (size_t)d.B * (d.steps + 1) * d.n * d.m;
+    hipLaunchKernelGGL(k_lb_populations, dim3(grid_for(total, QOC_BLOCK, 2048)), dim3(QOC_BLOCK), 0, e->stream, d, e->lb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(pop, e->lb.pop, total * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1327,7 +1438,7 @@ int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, 
         "k_mfma_expm_slice2 + k_mfma_chain_rows", "k_mfma_expm_pair", "k_mfma_expm_rows", "k_mfma_expm_inplace"};
     const int v = e->path == QOC_PATH_MFMA ? qoc_mfma_expm_variant(e->mf, e->d) : 0;
     if (kernel_name)
-        *kernel_name = e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
+        *kernel_name = e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
                        : e->path == QOC_PATH_GEMM ? (e->gm.direct ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
                            : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
                        : e->path == QOC_PATH_MFMA ? (v == 5 && e->mf.NT == 3 ? "k_mfma_expm_rows (per slice) + k_mfma_chain_rows"
@@ -1359,6 +1470,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 // sweeps=<downup|split|row_tile_gradient|latency|latency_sources|one_wave>
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
+//   open engines (qoc_create_open): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
 // exact engines add exact_variant=<lds|global> exact_lds=<bytes of dynamic LDS, 0 in the global variant> exact_grid=<workgroups of k_exact_grad>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
@@ -1383,6 +1495,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
             g.sq_chain ? "squared" : g.dpp_packed ? "packed"
             : g.dpp_chain ? (g.dpp_cw == 10 ? "columns40" : g.dpp_cw == 12 ? "columns48" : g.dpp_cw == 14 ? "columns56" : "full")
                 : "butterfly");
+    } else if (e->path == QOC_PATH_LINDBLAD) {
+        snprintf(tmp, sizeof tmp, "path=lindblad collapse=%d pairs=%d lds=%zu", e->lb.c, e->lb.R, e->lb.lds_bytes);
     } else if (e->path == QOC_PATH_SMALL) {
         snprintf(tmp, sizeof tmp, "path=small n_pad=%d rows=%d slices_per_row=%d workgroups=%d state_sources=%d lds_kb=%d", e->sm.N, e->sm.R, e->sm.L, e->sm.G,
             e->sm.src ? 1 : 0, (int)((e->sm.lds_bytes + 1023) / 1024));

@@ -30,6 +30,14 @@ class Analysis(object):
 
     def get_final_state(self, save=True):
         """Final evolved unitary, n x n complex (analysis.py:26-35)."""
+        if getattr(self.engine, 'open_system', False):
+            # open-system GRAPE: the final density operators rho_ij(T), (m, m, n, n), logged as they are (real and imaginary part)
+            rho = np.array(self.engine.get_final_density()[self.seed])
+            if self.sys_para.save and save:
+                with self._log() as hf:
+                    hf.append('final_density_real', np.array(rho.real))
+                    hf.append('final_density_imag', np.array(rho.imag))
+            return rho
         CMat = np.array(self.engine.get_final_unitary()[self.seed])
         if self.sys_para.save and save:
             with self._log() as hf:
@@ -50,6 +58,13 @@ class Analysis(object):
         sp = self.sys_para
         if not sp.use_inter_vecs:
             return None
+        if getattr(self.engine, 'open_system', False):
+            # open-system GRAPE: the diagonals of rho_ii(tau) are the populations themselves
+            pops = np.ascontiguousarray(np.transpose(np.array(self.engine.get_populations()[self.seed]), (2, 1, 0)))   # (m, n, steps+1)
+            if sp.save:
+                with self._log() as hf:
+                    hf.append('populations', np.array(pops))
+            return list(pops)
         raw = np.array(self.engine.get_inter_vecs()[self.seed])        # (steps+1, n, m)
         raw = np.ascontiguousarray(np.transpose(raw, (2, 1, 0)))       # (m, n, steps+1) like tf.stack(inter_vecs)
         if sp.save:

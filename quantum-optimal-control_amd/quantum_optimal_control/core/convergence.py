@@ -36,7 +36,11 @@ class Convergence(object):
     def save_evol(self, anly):
         """Snapshot of the propagation at this point of the run (convergence.py:62-66); with save=True the Analysis
         calls append final_state / inter_vecs_* to the run log."""
-        if not self.sys_para.state_transfer:
+        if getattr(getattr(anly, 'engine', None), 'open_system', False):
+            # open-system GRAPE: the final density operators (m, m, n, n); the figure shows the one the first state ends in
+            self.final_density = anly.get_final_state()
+            self.final_state = self.final_density[0, 0]
+        elif not self.sys_para.state_transfer:
             self.final_state = anly.get_final_state()
         self.inter_vecs = anly.get_inter_vecs()
 

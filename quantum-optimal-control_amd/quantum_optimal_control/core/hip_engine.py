@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('QOC_HIP_LIBRARY') or os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libqoc_hip.so'))   # override: A/B builds
 
 PATH_AUTO, PATH_GENERIC, PATH_MFMA, PATH_ST_FUSED, PATH_GEMM, PATH_SMALL = 0, 1, 2, 3, 4, 5
+PATH_LINDBLAD = 6          # open engines only (HipEngine(collapse_ops=...))
 
 
 class QocConfig(C.Structure):
@@ -39,6 +40,10 @@ class QocTransfer(C.Structure):
     _fields_ = [('n_samples', C.c_int32), ('T', C.POINTER(C.c_double))]
 
 
+class QocOpen(C.Structure):
+    _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double))]
+
+
 class QocAdamParams(C.Structure):
     _fields_ = [('rate', C.c_double), ('learning_rate_decay', C.c_double), ('conv_target', C.c_double),
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
@@ -54,6 +59,9 @@ _SIGNATURES = {
                                       C.POINTER(C.c_void_p)]),
     'qoc_create_shaped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP,
                                     _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_open': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocOpen), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_get_populations': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_pulse': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_member_scalars': (C.c_int, [C.c_void_p, _DP, _DP]),
     'qoc_get_member_final_unitary': (C.c_int, [C.c_void_p, _DP]),
@@ -298,11 +306,24 @@ class HipEngine(object):
 
     exact_gradient (include/qoc.h qoc_config.gradient): False = the reference's first-order GRAPE gradient; True = the derivative of the slice
     propagators the engine computes (truncated Taylor series and squarings), so that loss and gradient belong to one function.  Generic path
-    only (AUTO resolves to it; any other explicit path and time sharding raise QocError).  Composes with ensemble and transfer."""
+    only (AUTO resolves to it; any other explicit path and time sharding raise QocError).  Composes with ensemble and transfer.
+
+    collapse_ops (open-system GRAPE, include/qoc.h qoc_create_open): a list of n x n collapse operators that carry the square root of their
+    rates (helper_functions/open_system.py builds the usual ones; an empty list is the closed limit).  The engine then propagates the operators
+    psi_i psi_j^dagger of the states of interest under the Lindblad master equation, with degree taylor_terms and 2^scaling sub-steps per slice in
+    both modes; loss, gradient and the optimiser entry points keep their shapes, get_final_density() and get_populations() take the place of
+    get_final_unitary() and get_inter_vecs().  Combines with none of ensemble, transfer, exact_gradient or time sharding (ValueError)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
-                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False):
+                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None):
+        if collapse_ops is not None:
+            for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
+                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
+                if given:
+                    raise ValueError('HipEngine: collapse_ops (open-system GRAPE) does not combine with %s' % name)
+            from quantum_optimal_control.helper_functions import open_system
+            collapse_ops = open_system.validate(collapse_ops, np.shape(Hs)[1])
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
@@ -346,6 +367,7 @@ class HipEngine(object):
                 _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
                 C.byref(self._h))
         self.members = 0
+        self.open_system = collapse_ops is not None
         self.samples = None                           # transfer-function GRAPE: P, the length of the variable's rows
         ens = None
         if ensemble is not None:
@@ -356,7 +378,13 @@ class HipEngine(object):
             ens.offsets = _dp(off) if P.shape[0] else None
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
-        if transfer is not None:
+        if collapse_ops is not None:
+            # D_j = sqrt(dt) C_j; the state regularisers and Vs stay behind (the library refuses them by name)
+            D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
+            op = QocOpen()
+            op.n_collapse, op.C = len(collapse_ops), (_dp(D.view(np.float64)) if len(collapse_ops) else None)
+            _check(lib.qoc_create_open(C.byref(cfg), C.byref(op), *(args[:6] + args[-1:])))
+        elif transfer is not None:
             T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
             if T.ndim != 2 or T.shape[0] != int(steps):
                 raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
@@ -466,6 +494,18 @@ class HipEngine(object):
     def get_final_unitary(self):
         out = np.empty((self.n_seeds, self.n, self.n), dtype=np.complex128)
         _check(self._lib.qoc_get_final_unitary(self._h, _dp(out.view(np.float64))))
+        return out
+
+    def get_final_density(self):
+        """Open engines: rho_ij(T) of the last evaluation, (n_seeds, m, m, n, n); [g, i, i] is the density matrix state i ends in."""
+        out = np.empty((self.n_seeds, self.m, self.m, self.n, self.n), dtype=np.complex128)
+        _check(self._lib.qoc_get_final_density(self._h, _dp(out.view(np.float64))))
+        return out
+
+    def get_populations(self):
+        """Open engines: Re rho_ii(tau)[l, l] of the last evaluation, (n_seeds, steps + 1, n, m); tau = 0 is the start."""
+        out = np.empty((self.n_seeds, self.steps + 1, self.n, self.m))
+        _check(self._lib.qoc_get_populations(self._h, _dp(out)))
         return out
 
     def member_scalars(self):

@@ -110,7 +110,9 @@ class run_session(object):
         self.display()
         self.conv.save_evol(self.anly)                    # final_state / inter_vecs_* rows of the run log (:100-101)
         self.uks = self.Get_uks()
-        if not self.sys_para.state_transfer:
+        if getattr(self.engine, 'open_system', False):
+            self.Uf = self.anly.get_final_state(save=False)     # (m, m, n, n): the final density operators, in both modes
+        elif not self.sys_para.state_transfer:
             self.Uf = self.anly.get_final_state(save=False)
         else:
             self.Uf = []

@@ -1,0 +1,82 @@
+"""Open-system GRAPE: collapse operators for Grape(collapse_ops=...) / HipEngine(collapse_ops=...) and the Taylor rule of the Lindblad slice map.
+
+A collapse operator C_j is n x n and carries the square root of its rate, so that the master equation reads
+    d rho / dt = -i [H, rho] + sum_j (C_j rho C_j^dagger - 1/2 {C_j^dagger C_j, rho}).
+The reference has no counterpart (it propagates state vectors only).
+"""
+import math
+
+import numpy as np
+
+
+def validate(collapse_ops, n):
+    """The list as the engine takes it: complex n x n arrays.  ValueError on anything else (an empty list is the closed limit)."""
+    if not isinstance(collapse_ops, (list, tuple)):
+        raise ValueError('collapse_ops: a list of %d x %d collapse operators is expected, got %s' % (n, n, type(collapse_ops).__name__))
+    out = []
+    for j, op in enumerate(collapse_ops):
+        a = np.asarray(op)
+        if a.shape != (n, n):
+            raise ValueError('collapse_ops[%d] has shape %s, expected (%d, %d)' % (j, a.shape, n, n))
+        try:
+            a = a.astype(np.complex128)
+        except (TypeError, ValueError):
+            raise ValueError('collapse_ops[%d] is not numeric' % j)
+        if not np.all(np.isfinite(a)):
+            raise ValueError('collapse_ops[%d] is not finite' % j)
+        if not np.any(a):
+            raise ValueError('collapse_ops[%d] is all zero (leave it out)' % j)
+        out.append(np.ascontiguousarray(a))
+    return out
+
+
+def _lowering(n):
+    return np.diag(np.sqrt(np.arange(1, n)), 1).astype(np.complex128)
+
+
+def relaxation(n, t1):
+    """Energy relaxation of an n-level oscillator with lifetime t1: sqrt(1 / t1) a."""
+    if not (t1 > 0 and np.isfinite(t1)):
+        raise ValueError('relaxation: t1 = %r (a positive time)' % (t1,))
+    return math.sqrt(1.0 / float(t1)) * _lowering(n)
+
+
+def dephasing(n, tphi):
+    """Pure dephasing of an n-level oscillator with dephasing time tphi: sqrt(2 / tphi) a^dagger a."""
+    if not (tphi > 0 and np.isfinite(tphi)):
+        raise ValueError('dephasing: tphi = %r (a positive time)' % (tphi,))
+    a = _lowering(n)
+    return math.sqrt(2.0 / float(tphi)) * (a.conj().T @ a)
+
+
+def lindblad_bound(H0, Hops, maxA, collapse_ops, dt):
+    """x = 2 dt (|H0|_2 + sum_k maxA_k |H_k|_2 + sum_j |C_j|_2^2) >= |dt L| for every admissible pulse."""
+    x = np.linalg.norm(np.asarray(H0, dtype=np.complex128), 2)
+    for a, h in zip(np.asarray(maxA, dtype=np.float64), Hops):
+        x += abs(float(a)) * np.linalg.norm(np.asarray(h, dtype=np.complex128), 2)
+    for c in collapse_ops:
+        x += np.linalg.norm(np.asarray(c, dtype=np.complex128), 2) ** 2
+    return 2.0 * float(dt) * float(x)
+
+
+def taylor_remainder(y, T, steps, s):
+    """steps 2^s 2 y^(T+1) / (T+1)!: the Taylor remainder with e^y <= 2, summed over all sub-steps of a contractive map."""
+    return steps * (2.0 ** s) * 2.0 * y ** (T + 1) / math.factorial(T + 1)
+
+
+def choose_taylor(H0, Hops, maxA, collapse_ops, dt, steps, unitary_error):
+    """(T, s) of the Lindblad slice map (degree T, 2^s sub-steps): s the smallest value with y = x / 2^s <= 0.5, T the smallest value >= 2 with
+    taylor_remainder(y, T, steps, s) <= unitary_error.  ValueError past T = 60 or s = 12 (the engine's limits)."""
+    x = lindblad_bound(H0, Hops, maxA, collapse_ops, dt)
+    s = 0
+    while x / 2.0 ** s > 0.5:
+        s += 1
+        if s > 12:
+            raise ValueError('choose_taylor: |dt L| <= %.3g needs more than 2^12 sub-steps per slice; use more time slices' % x)
+    y = x / 2.0 ** s
+    T = 2
+    while taylor_remainder(y, T, steps, s) > unitary_error:
+        T += 1
+        if T > 60:
+            raise ValueError('choose_taylor: unitary_error = %g is not reached with 60 Taylor terms' % unitary_error)
+    return T, s

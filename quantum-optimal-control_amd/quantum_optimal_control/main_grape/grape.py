@@ -52,7 +52,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, _first_seed=0, _device=0, _return_session=False):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, _first_seed=0, _device=0, _return_session=False):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -70,9 +70,31 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``exact_gradient`` (default False: the reference's first-order GRAPE gradient): True differentiates the slice propagators the engine
     computes -- truncated Taylor series and squarings included -- so that the loss and the gradient a driver sees belong to one function.
     It pays for few, long slices and for the scipy drivers, whose line searches assume exactly that; it costs more per evaluation
-    (DESIGN.md).  Works with every ``method``, with ``restarts``, ``robust``, ``transfer`` and GrapeSharded; not with ``time_comm``."""
+    (DESIGN.md).  Works with every ``method``, with ``restarts``, ``robust``, ``transfer`` and GrapeSharded; not with ``time_comm``.
+
+    ``collapse_ops`` (open-system GRAPE): a list of n x n collapse operators that carry the square root of their rates, e.g. from
+    helper_functions.open_system (``relaxation``, ``dephasing``).  The pulse is then scored and optimised under the Lindblad master equation
+    d rho/dt = -i [H, rho] + sum_j (C_j rho C_j^dagger - 1/2 {C_j^dagger C_j, rho}): the loss is 1 - (1/m^2) sum_ij Re Tr(sigma_ij^dagger rho_ij(T)) over
+    the operators rho_ij(0) = psi_i psi_j^dagger of the states of interest and sigma_ij = w_i w_j^dagger of their targets -- the closed loss when the
+    list is empty.  Returns ``(uks, rho_final)`` with ``rho_final`` of shape (m, m, n, n): ``rho_final[i, i]`` is the density matrix that state i
+    ends in, ``rho_final[i, j]`` the propagated coherence psi_i psi_j^dagger.  Taylor order and sub-steps come from
+    open_system.choose_taylor unless ``Taylor_terms=(T, s)`` is given (degree T, 2^s sub-steps per slice, in both modes).  Works with every
+    ``method`` (``'EVOLVE'`` with ``initial_guess=uks`` scores an existing pulse under decay) and with ``restarts``; not with ``robust``,
+    ``transfer``, ``exact_gradient``, ``time_comm``, forbidden-level / ``speed_up`` regularisers, ``dressed_info`` or the sharded entry points."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
+    if collapse_ops is not None:
+        from quantum_optimal_control.helper_functions import open_system as _open
+        for name, given in (('robust', robust is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
+                            ('time_comm', time_comm is not None), ('dressed_info', dressed_info is not None),
+                            ('the forbidden-level regulariser', reg_coeffs is not None and 'forbidden_coeff_list' in reg_coeffs),
+                            ('the speed_up regulariser', reg_coeffs is not None and 'speed_up' in reg_coeffs),
+                            ('forbid_dressed', reg_coeffs is not None and 'forbid_dressed' in reg_coeffs)):
+            if given:
+                raise ValueError('Grape: collapse_ops (open-system GRAPE) does not combine with %s' % name)
+        if _first_seed != 0 or plan_seeds is not None:
+            raise ValueError('Grape: collapse_ops (open-system GRAPE) does not run sharded (GrapeSharded)')
+        collapse_ops = _open.validate(collapse_ops, len(H0))
     if exact_gradient and time_comm is not None:
         raise ValueError('Grape: the exact gradient cannot be time-sharded (time_comm)')
     if robust is not None:
@@ -115,6 +137,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
                 hf.add('exact_gradient', data=np.array(1))
+        if collapse_ops is not None:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                hf.add('collapse_ops', data=np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), len(H0), len(H0)))
 
     if U0 is None:
         U0 = np.identity(len(H0))
@@ -132,6 +158,9 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     if robust is not None and Taylor_terms is None:
         # the largest Taylor order and squaring count any member's own problem would get (both only lower the truncation error)
         Taylor_terms = _robust.choose_taylor(H0, Hops, robust, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
+
+    if collapse_ops is not None and Taylor_terms is None:
+        Taylor_terms = _open.choose_taylor(H0, Hops, maxAmp, collapse_ops, float(total_time) / steps, steps, unitary_error)
 
     sample_base = None
     if transfer is not None and initial_guess is not None:
@@ -163,7 +192,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         sys_para.raw_shape = np.shape(sample_base)
     tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
                    plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust,
-                   transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient))   # constants -> HBM
+                   transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient),
+                   collapse_ops=collapse_ops)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
@@ -196,6 +226,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
     gradient array -- keep the ranks in lock step (csrc/qoc_gemm_ts.h).  Every rank runs the same optimiser on the whole pulse and returns
     the same (uks, U_final); only rank 0 writes the run log.  comm = None: a plain Grape call.  Unitary mode, no forbidden-level / speed_up term,
     n > 96, at most 8 states of interest; the reference has no counterpart (one device: main_grape/grape.py:106-109)."""
+    if kwargs.get('collapse_ops') is not None:
+        raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
     if comm is None:
         return Grape(*args, **kwargs)
     from quantum_optimal_control.core import hip_engine
@@ -229,6 +261,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
         raise ValueError('GrapeSharded: robust ensembles are not supported; run Grape(robust=..., restarts=R) on one GPU')
     if kwargs.get('transfer') is not None:
         raise ValueError('GrapeSharded: transfer functions are not supported; run Grape(transfer=..., restarts=R) on one GPU')
+    if kwargs.get('collapse_ops') is not None:
+        raise ValueError('GrapeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=..., restarts=R) on one GPU')
     if comm is not None:
         world, rank = comm.world, comm.rank
     elif dist is not None:
