@@ -9,6 +9,8 @@ was last granted.  The pairs below meet on every such instance, small count crea
   k_mfma_grad_rt<NT, MQ>    ((k + 3) & ~3) NT 256 complex numbers      csrc/qoc_mfma_backward.hip: qoc_mfma_setup
   k_mfma_grad<NT, MQ>       min(k, 4 or 2) control images              the same call; varies only behind QOC_GRAD_RT=0 (k <= 8 takes the row-tile kernel)
   k_mfma_backward<NT, true> pads + k control images                    variant 1 (and n <= 16), while the images fit the LDS
+  k_lb_forward / k_lb_backward  (c + 4) n (n | 1) complex numbers      csrc/qoc_lindblad.h: qoc_lb_lds_opt_in asks for the size rule's limit, not the engine's
+                            count; open engines beside open and closed ones: tests/test_open_system_edges.py::test_open_engine_beside_another
 
 The other call sites ask for a constant of the instance and need no pair: the latency mode's gradient kernels (csrc/qoc_mfma_latency.hip:
 the image count KC and NT are template arguments, NT = 4 always takes two), k_mfma_backward3 and k_mfma_downup (qoc_mfma_setup: KC = 4 | 5, MQ
