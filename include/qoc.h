@@ -251,6 +251,36 @@ int qoc_run_adam(qoc_handle h, const qoc_adam_params* p, int32_t* iterations_out
 int qoc_iterate(qoc_handle h, const qoc_adam_params* p, int32_t iters);
 int qoc_sync(qoc_handle h);
 
+/* ---- device-resident L-BFGS loop (no counterpart in the reference, whose L-BFGS-B is scipy's, one host round trip per evaluation) ------------
+ * One loop iteration is the evaluation of qoc_eval followed by one step kernel (csrc/qoc_lbfgs.h); the objective is reg_loss, the variable base.
+ * Every control set keeps its own history of `history` curvature pairs, direction, step length and flags, so n_seeds restarts are n_seeds
+ * independent quasi-Newton runs.  Per control set and evaluation (f, g = reg_loss and its gradient at x = base):
+ *   the evaluation of a restored point ends the set;  loss < conv_target or grad_squared < min_grad ends it where it stands;
+ *   acceptable = first evaluation, or f finite and f <= f_acc + c1 alpha g_acc.p (Armijo);
+ *   iterations >= max_iterations: done if acceptable, else base = x_acc and one more evaluation there (a set ends with its last evaluation
+ *     at the point it returns, after at most max_iterations + 2 evaluations);  otherwise iterations += 1 and
+ *   accept: the pair (x - x_acc, g - g_acc) enters the history if s.y > 1e-10 y.y; p = -H g by the L-BFGS recursion with H0 = (s.y / y.y) I of the
+ *     newest pair (empty history, or g.p >= 0 which also clears it: p = -g / |g|); alpha = 1; base = x + p;
+ *   reject: after max_ls rejected trials the history is cleared and the search restarts along -g_acc / |g_acc| with alpha = 1 (a search that
+ *     was steepest descent already: base = x_acc, one more evaluation, done); otherwise alpha *= shrink, base = x_acc + alpha p.
+ * Backtracking Armijo, no bounds, no interpolation.  The state ((2 history + 3) vectors of the variable's size per control set)
+ * is allocated by the first call: QOC_ERR_NOMEM if it does not fit (a later call with a longer history takes one more block, for 16 pairs; the
+ * engine keeps both until qoc_destroy).  qoc_set_base resets it as it resets the Adam slots; a call with another
+ * `history` resets it too.  QOC_ERR_INVALID (the message starts with the call's name): null params, history outside 1 .. 16, c1 or shrink
+ * outside (0, 1), max_ls < 1, a time-sharded engine.  Works on every other engine: ensembles, transfer functions, the exact gradient, open
+ * systems.  Finished control sets keep being evaluated at their final point, so every read-back belongs to it. */
+typedef struct qoc_lbfgs_params {
+    double conv_target, min_grad;      /* as qoc_adam_params */
+    double c1;                         /* Armijo constant, default 1e-4 */
+    double shrink;                     /* step factor on a rejected trial, default 0.5, in (0, 1) */
+    int32_t max_iterations;            /* as qoc_adam_params: bounds the evaluations (see the stop rule) */
+    int32_t history;                   /* M pairs kept, 1 .. 16, default 8 */
+    int32_t max_ls;                    /* rejected trials before the direction is reset, default 20 */
+    int32_t poll_every;
+} qoc_lbfgs_params;
+int qoc_iterate_lbfgs(qoc_handle h, const qoc_lbfgs_params* p, int32_t iters);      /* no host sync, like qoc_iterate */
+int qoc_run_lbfgs(qoc_handle h, const qoc_lbfgs_params* p, int32_t* iterations_out); /* polls done flags, like qoc_run_adam */
+
 /* Last evaluation's per-seed scalars [n_seeds] each (any pointer may be NULL). */
 int qoc_get_scalars(qoc_handle h, double* loss, double* reg_loss, double* grad_squared, double* unitary_scale,
                     int32_t* iterations, int32_t* done);

@@ -30,6 +30,7 @@
 #include "qoc_transfer.h"
 #include "qoc_exact_grad.h"
 #include "qoc_lindblad.h"
+#include "qoc_lbfgs.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
 // (QOC_PLAN_LAT_WORK = 4608 seeds x time slices: since the batch sweeps take their chunk boundaries and final_state from k_mfma_bnd_scan
@@ -104,6 +105,9 @@ struct qoc_engine {
     QocExact xg{};
     // open-system GRAPE (qoc_create_open, csrc/qoc_lindblad.h): density operators of the pairs of states of interest under a Lindblad master equation
     QocLb lb{};
+    // device-resident L-BFGS loop (qoc_iterate_lbfgs / qoc_run_lbfgs, csrc/qoc_lbfgs.h): per-set state, allocated by the first call for lq_cap pairs
+    QocLbfgsDev lq{};
+    int lq_cap = 0;
 };
 
 // the view that holds the control sets: the engine itself, or the group view of an ensemble engine
@@ -518,6 +522,73 @@ static QocAdamDev loop_params(const qoc_adam_params* p) {
     ap.lr = nullptr;
     return ap;
 }
+
+// ---- device-resident L-BFGS loop (csrc/qoc_lbfgs.h) ---------------------------------------------------------------------------------------
+// history, direction and flags of every control set back to "no step taken" (the vectors need no clearing: no slot is live)
+static int lbfgs_reset(qoc_engine* e) {
+    const QocLbfgsDev& L = e->lq;
+    const size_t B = (size_t)sets(e).B, R = 2 * (size_t)L.M + 1;
+    HIP_TRY(hipMemsetAsync(L.st, 0, B * 8 * sizeof(int), e->stream));
+    HIP_TRY(hipMemsetAsync(L.sc, 0, B * 4 * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(L.gram, 0, B * R * R * sizeof(double), e->stream));
+    return QOC_OK;
+}
+
+// checks the parameters of a loop call (`who` names it), allocates the state on the first call (or for a longer history) and resets it when the history changes
+static int lbfgs_prepare(qoc_engine* e, const qoc_lbfgs_params* p, const char* who, QocLbfgsDev* out) {
+    if (!p) return fail(QOC_ERR_INVALID, "%s: null params", who);
+    if (p->history < 1 || p->history > QOC_LBFGS_MAX_M) return fail(QOC_ERR_INVALID, "%s: history = %d, expected 1 .. %d", who, p->history, QOC_LBFGS_MAX_M);
+    if (!(p->c1 > 0.0 && p->c1 < 1.0)) return fail(QOC_ERR_INVALID, "%s: c1 = %g, expected a value in (0, 1)", who, p->c1);
+    if (!(p->shrink > 0.0 && p->shrink < 1.0)) return fail(QOC_ERR_INVALID, "%s: shrink = %g, expected a value in (0, 1)", who, p->shrink);
+    if (p->max_ls < 1) return fail(QOC_ERR_INVALID, "%s: max_ls = %d, expected >= 1", who, p->max_ls);
+    if (e->cfg.time_shards > 0 || e->gm.ts_G > 0)
+        return fail(QOC_ERR_INVALID, "%s: the L-BFGS loop does not run on a time-sharded engine (every rank would have to take the same line-search decisions)", who);
+    const QocDev& sd = sets(e);
+    const size_t B = (size_t)sd.B, N = (size_t)sd.k * sd.steps;
+    QocLbfgsDev& L = e->lq;
+    // The small arrays once, for the longest history.  The vectors for the history asked for first (what most engines ever use); a later, longer history takes
+    // ONE new block for QOC_LBFGS_MAX_M pairs -- the arena cannot give the first block back, so an engine holds at most these two until qoc_destroy, however
+    // the histories of later calls alternate.  The vectors come last: a QOC_ERR_NOMEM leaves nothing but the few KB of the small arrays behind.
+    if (!L.gram) {
+        const size_t R = QOC_LBFGS_ROWS;
+        TRY(dev_alloc(e, &L.gram, B * R * R));
+        TRY(dev_alloc(e, &L.sc, B * 4));
+        TRY(dev_alloc(e, &L.st, B * 8));
+    }
+    if (!L.vec || p->history > e->lq_cap) {
+        const size_t M = L.vec ? (size_t)QOC_LBFGS_MAX_M : (size_t)p->history;
+        double* vec = nullptr;
+        TRY(dev_alloc(e, &vec, B * (2 * M + 3) * N));
+        // (on the engine's stream, as every later use: the null stream orders nothing against it)
+        HIP_TRY(hipMemsetAsync(vec, 0, B * (2 * M + 3) * N * sizeof(double), e->stream));
+        L.vec = vec;
+        L.M = 0;
+        e->lq_cap = (int)M;
+    }
+    L.N = (int)N;
+    if (L.M != p->history) {
+        L.M = p->history;
+        TRY(lbfgs_reset(e));
+    }
+    L.conv_target = p->conv_target; L.min_grad = p->min_grad; L.c1 = p->c1; L.shrink = p->shrink;
+    L.max_iterations = p->max_iterations; L.max_ls = p->max_ls;
+    *out = L;
+    return QOC_OK;
+}
+
+// one loop iteration: the evaluate-only iteration of qoc_eval, then the step on the view that holds the control sets
+static int enqueue_lbfgs_iteration(qoc_engine* e, const QocLbfgsDev& L) {
+    QocAdamDev ap;
+    memset(&ap, 0, sizeof ap);
+    ap.mode = 0;
+    TRY(enqueue_iteration(e, ap));
+    const QocDev& sd = sets(e);
+    hipLaunchKernelGGL(k_lbfgs_step, dim3(sd.B), dim3(L.N >= 2048 ? 1024 : QOC_BLOCK), 0, e->stream, sd, L);
+    HIP_TRY(hipGetLastError());
+    e->controls_ready = false;                 // the variable moved on the device: u2 / w2 are not its controls
+    return QOC_OK;
+}
+
 
 // the response matrix of qoc_create_shaped as the host prepared it: the transposed copy and the nonzero window of every row and column
 struct ShapeHost {
@@ -1171,6 +1242,7 @@ int qoc_set_base(qoc_handle e, const double* base) {
     HIP_TRY(hipMemsetAsync(d.adam_t, 0, d.B * sizeof(int), e->stream));
     HIP_TRY(hipMemsetAsync(d.iters, 0, d.B * sizeof(int), e->stream));
     HIP_TRY(hipMemsetAsync(d.done, 0, d.B * sizeof(int), e->stream));
+    if (e->lq.gram && e->lq.M) TRY(lbfgs_reset(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->evaluated = false;
     e->controls_ready = false;
@@ -1280,6 +1352,41 @@ int qoc_run_adam(qoc_handle e, const qoc_adam_params* p, int32_t* iterations_out
         for (int b = 0; b < sd.B; ++b) all = all && done[b];
         if (all) break;
         if (launched >= budget) return fail(QOC_ERR_STATE, "qoc_run_adam: seeds not finished after %lld evaluations", launched);
+    }
+    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+int qoc_iterate_lbfgs(qoc_handle e, const qoc_lbfgs_params* p, int32_t iters) {
+    CHECK_H(e);
+    QocLbfgsDev L;
+    TRY(lbfgs_prepare(e, p, "qoc_iterate_lbfgs", &L));
+    for (int i = 0; i < iters; ++i) TRY(enqueue_lbfgs_iteration(e, L));
+    return QOC_OK;
+}
+
+int qoc_run_lbfgs(qoc_handle e, const qoc_lbfgs_params* p, int32_t* iterations_out) {
+    CHECK_H(e);
+    QocLbfgsDev L;
+    TRY(lbfgs_prepare(e, p, "qoc_run_lbfgs", &L));
+    const int poll = p->poll_every > 0 ? p->poll_every : 1;
+    const QocDev& sd = sets(e);
+    std::vector<int> done(sd.B);
+    // at most max_iterations evaluations that move the variable, one whose trial is refused at the limit, one of the accepted point restored
+    const long long budget = (long long)p->max_iterations + 2;
+    long long launched = 0;
+    while (true) {
+        int burst = poll;
+        if (launched + burst > budget) burst = (int)(budget - launched);
+        for (int i = 0; i < burst; ++i) TRY(enqueue_lbfgs_iteration(e, L));
+        launched += burst;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        TRY(small_check(e));
+        HIP_TRY(hipMemcpy(done.data(), sd.done, sd.B * sizeof(int), hipMemcpyDeviceToHost));
+        bool all = true;
+        for (int b = 0; b < sd.B; ++b) all = all && done[b];
+        if (all) break;
+        if (launched >= budget) return fail(QOC_ERR_STATE, "qoc_run_lbfgs: control sets not finished after %lld evaluations", launched);
     }
     if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
     return QOC_OK;

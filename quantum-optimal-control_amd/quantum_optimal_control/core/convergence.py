@@ -23,6 +23,10 @@ class Convergence(object):
         # extension, L-BFGS-B only: scipy's relative-reduction stop (absent: scipy's own default, as the reference); 0 switches it off, so that
         # only conv_target, min_grad and max_iterations end the run
         self.ftol = convergence['ftol'] if 'ftol' in convergence else None
+        # extension, method='LBFGS' only (the device-resident loop, csrc/qoc_lbfgs.h): pairs kept, Armijo constant, rejected trials before a reset
+        self.lbfgs_history = int(convergence['lbfgs_history']) if 'lbfgs_history' in convergence else 8
+        self.lbfgs_c1 = float(convergence['lbfgs_c1']) if 'lbfgs_c1' in convergence else 1e-4
+        self.lbfgs_max_ls = int(convergence['lbfgs_max_ls']) if 'lbfgs_max_ls' in convergence else 20
         self.reset_convergence()
 
     def reset_convergence(self):

@@ -49,6 +49,11 @@ class QocAdamParams(C.Structure):
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
 
 
+class QocLbfgsParams(C.Structure):
+    _fields_ = [('conv_target', C.c_double), ('min_grad', C.c_double), ('c1', C.c_double), ('shrink', C.c_double),
+                ('max_iterations', C.c_int32), ('history', C.c_int32), ('max_ls', C.c_int32), ('poll_every', C.c_int32)]
+
+
 _DP = C.POINTER(C.c_double)
 _IP = C.POINTER(C.c_int32)
 _lib = None
@@ -72,6 +77,8 @@ _SIGNATURES = {
     'qoc_adam_step': (C.c_int, [C.c_void_p, _DP]),
     'qoc_run_adam': (C.c_int, [C.c_void_p, C.POINTER(QocAdamParams), _IP]),
     'qoc_iterate': (C.c_int, [C.c_void_p, C.POINTER(QocAdamParams), C.c_int32]),
+    'qoc_iterate_lbfgs': (C.c_int, [C.c_void_p, C.POINTER(QocLbfgsParams), C.c_int32]),
+    'qoc_run_lbfgs': (C.c_int, [C.c_void_p, C.POINTER(QocLbfgsParams), _IP]),
     'qoc_sync': (C.c_int, [C.c_void_p]),
     'qoc_get_scalars': (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, _IP, _IP]),
     'qoc_get_uks': (C.c_int, [C.c_void_p, _DP]),
@@ -464,6 +471,25 @@ class HipEngine(object):
 
     def iterate(self, params, iters):
         _check(self._lib.qoc_iterate(self._h, C.byref(params), int(iters)))
+
+    @staticmethod
+    def lbfgs_params(conv_target=1e-8, min_grad=1e-25, max_iterations=5000, history=8, c1=1e-4, shrink=0.5, max_ls=20, poll_every=100):
+        """Parameters of the device-resident L-BFGS loop (include/qoc.h, qoc_lbfgs_params): `history` curvature pairs per control set (1 .. 16),
+        the Armijo constant `c1`, the factor `shrink` of a rejected trial step and the `max_ls` rejected trials after which the direction is reset."""
+        p = QocLbfgsParams()
+        p.conv_target, p.min_grad, p.c1, p.shrink = float(conv_target), float(min_grad), float(c1), float(shrink)
+        p.max_iterations, p.history, p.max_ls, p.poll_every = int(max_iterations), int(history), int(max_ls), int(poll_every)
+        return p
+
+    def run_lbfgs(self, params):
+        """The L-BFGS loop to the end of every control set (the host polls the done flags every params.poll_every iterations); the iteration counters."""
+        its = np.empty(self.n_seeds, dtype=np.int32)
+        _check(self._lib.qoc_run_lbfgs(self._h, C.byref(params), its.ctypes.data_as(_IP)))
+        return its
+
+    def iterate_lbfgs(self, params, iters):
+        """Exactly `iters` iterations of the L-BFGS loop (one evaluation and one step each), no host synchronisation."""
+        _check(self._lib.qoc_iterate_lbfgs(self._h, C.byref(params), int(iters)))
 
     def sync(self):
         _check(self._lib.qoc_sync(self._h))

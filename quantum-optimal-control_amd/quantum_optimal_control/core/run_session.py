@@ -2,6 +2,8 @@
 
 ADAM        device-resident loop (stop rule, LR schedule and Adam update run on the GPU; the host polls every
             update_step iterations to print the reference's progress line)
+LBFGS       device-resident L-BFGS loop (csrc/qoc_lbfgs.h): every control set runs its own quasi-Newton search with a backtracking Armijo line search on
+            the GPU, so `restarts` are independent runs; the host polls as for ADAM
 EVOLVE      one evaluation at the initial controls
 anything else is handed to scipy.optimize.minimize with (reg_loss, gradient) from the engine, as the reference does.
 """
@@ -35,6 +37,8 @@ class run_session(object):
             self.get_end_results()
         elif self.method == 'ADAM':
             self.start_adam_optimizer()
+        elif self.method == 'LBFGS':
+            self.start_lbfgs_optimizer()
         else:
             self.bfgs_optimize(method=self.method)
 
@@ -66,7 +70,55 @@ class run_session(object):
         self.end = True
         self.get_end_results()
 
-    def _take_scalars(self, s, replace_last=False):
+    # ---- L-BFGS on the device --------------------------------------------------------------------------------------
+    LBFGS_POLL = 32
+
+    def lbfgs_params(self):
+        """The loop's parameters from the convergence settings: conv_target, min_grad and max_iterations as for Adam, plus the optional keys
+        lbfgs_history (pairs kept, default 8), lbfgs_c1 (Armijo constant, 1e-4) and lbfgs_max_ls (rejected trials before the direction is reset, 20)."""
+        conv = self.conv
+        return self.engine.lbfgs_params(conv_target=conv.conv_target, min_grad=conv.min_grad, max_iterations=conv.max_iterations,
+                                        history=conv.lbfgs_history, c1=conv.lbfgs_c1, max_ls=conv.lbfgs_max_ls,
+                                        poll_every=max(1, int(conv.update_step)))
+
+    def start_lbfgs_optimizer(self):
+        """start_adam_optimizer's bursts, polls and log rows around the L-BFGS loop.  An evaluation is one point of a line search: rejected trials
+        count as iterations, and a logged row may belong to one (its loss above the accepted point's).  Everything a row holds -- loss, reg_loss,
+        uks (Get_uks reads the controls the last evaluation ran on), final state, inter_vecs -- belongs to that one evaluation, the last one enqueued;
+        the variable itself has already moved to the next trial point.  A row's iteration is the index of its evaluation, counted by the host (the
+        evaluation of a restored point included); the final row of a finished control set carries the device's counter instead: the trial points that
+        set evaluated, which leaves out the one or two evaluations that only ended it."""
+        eng, conv = self.engine, self.conv
+        self.start_time = time.time()
+        params = self.lbfgs_params()
+        # evaluations: max_iterations that move the variable, one whose trial is refused at the limit, one of the accepted point restored
+        budget = int(conv.max_iterations) + 2
+        u, ev = max(1, int(conv.update_step)), max(1, int(conv.evol_save_step))
+        launched = 0
+        while True:
+            it = launched
+            while it % u != 0 and it % ev != 0:
+                it += 1
+            n = min(it + 1, budget) - launched
+            # in bursts of at most LBFGS_POLL evaluations: a finished control set keeps being evaluated at its final point (nothing freezes it as
+            # the Adam loop's skip does), and L-BFGS ends after tens of evaluations, not thousands
+            while n > 0:
+                burst = min(n, self.LBFGS_POLL)
+                eng.iterate_lbfgs(params, burst)
+                launched += burst
+                n -= burst
+                s = eng.scalars()
+                if np.all(s['done']):
+                    break
+            self._take_scalars(s, evaluation=launched - 1)
+            self.end = bool(np.all(s['done']))
+            if self.end or launched >= budget:
+                break
+            self.update_and_save(launched - 1)
+        self.end = True
+        self.get_end_results()
+
+    def _take_scalars(self, s, replace_last=False, evaluation=None):
         b = self.seed
         self.l, self.rl = float(s['loss'][b]), float(s['reg_loss'][b])
         self.g_squared, self.metric = float(s['grad_squared'][b]), float(s['unitary_scale'][b])
@@ -74,6 +126,8 @@ class run_session(object):
             # the device counter is already one past the evaluation these scalars belong to, unless that evaluation
             # tripped the stop rule (run_session.py:53-60 evaluates, checks, then increments)
             self.iterations = int(s['iterations'][b]) - (0 if int(s['done'][b]) else 1)
+            if evaluation is not None and not int(s['done'][b]):
+                self.iterations = int(evaluation)          # the L-BFGS loop: the host counted the evaluations of a set that is still running
         if replace_last and self.conv.iterations:
             self.conv.iterations[-1], self.conv.costs[-1], self.conv.reg_costs[-1] = self.iterations, self.l, self.rl
         else:

@@ -48,14 +48,29 @@ def _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_conce
                     group.create_dataset(key, data=val)
 
 
+def _is_lbfgs(args, kwargs):
+    """method='LBFGS' (the device-resident L-BFGS loop) among the arguments of a Grape call, by keyword or by position."""
+    method = kwargs['method'] if 'method' in kwargs else (args[20] if len(args) > 20 else 'Adam')
+    return str(method).upper() == 'LBFGS'
+
+
 def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, convergence=None, U0=None, reg_coeffs=None,
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, _first_seed=0, _device=0, _return_session=False):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
+
+    ``method='LBFGS'`` (extension): the device-resident L-BFGS loop -- every control set runs its own quasi-Newton search (history of
+    ``convergence['lbfgs_history']`` = 8 curvature pairs, backtracking Armijo line search with ``lbfgs_c1`` = 1e-4, direction reset after
+    ``lbfgs_max_ls`` = 20 rejected trials) on the GPU, objective reg_loss, stop rule and progress rows as for ``'Adam'``; ``max_iterations``
+    bounds the evaluations (at most two more are spent on ending at an accepted point).  With ``restarts=R`` these are R independent runs and the
+    best is returned.  No bounds, no strong-Wolfe search: ``'L-BFGS-B'`` and ``'BFGS'`` remain scipy's, one control set, one host round trip per
+    evaluation.  The default first-order gradient differs by O(dt) from the derivative of the reported loss, so that for few, long
+    slices the Armijo test starts refusing steps before the target is reached: pass ``exact_gradient=True`` there.  Works with ``restarts``,
+    ``robust``, ``transfer``, ``exact_gradient`` and ``collapse_ops``; not with ``time_comm`` or the sharded entry points.
 
     ``robust`` (robust GRAPE): a dict with keys ``operators`` (q Hermitian n x n matrices P_q), ``offsets`` (E x q), ``amp_scales``
     (E x k, default ones) and ``weights`` (E, default uniform; normalised to sum 1), e.g. from helper_functions.robust.ensemble_grid.
@@ -95,6 +110,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if _first_seed != 0 or plan_seeds is not None:
             raise ValueError('Grape: collapse_ops (open-system GRAPE) does not run sharded (GrapeSharded)')
         collapse_ops = _open.validate(collapse_ops, len(H0))
+    if str(method).upper() == 'LBFGS' and time_comm is not None:
+        raise ValueError("Grape: method='LBFGS' cannot be time-sharded (time_comm)")
     if exact_gradient and time_comm is not None:
         raise ValueError('Grape: the exact gradient cannot be time-sharded (time_comm)')
     if robust is not None:
@@ -200,6 +217,9 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         SS = run_session(tfs, graph, conv, sys_para, method, show_plots=sys_para.show_plots, use_gpu=use_gpu)
         if transfer is not None:
             transfer.samples = np.array(SS.samples)
+        if _restart_info is not None:
+            # (a dict to fill: every control set's final scalars and variable, read before the engine goes -- examples/lbfgs_restarts.py)
+            _restart_info.update(tfs.engine.scalars(), base=tfs.engine.get_base(), best=int(SS.seed))
         if save:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -226,6 +246,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
     gradient array -- keep the ranks in lock step (csrc/qoc_gemm_ts.h).  Every rank runs the same optimiser on the whole pulse and returns
     the same (uks, U_final); only rank 0 writes the run log.  comm = None: a plain Grape call.  Unitary mode, no forbidden-level / speed_up term,
     n > 96, at most 8 states of interest; the reference has no counterpart (one device: main_grape/grape.py:106-109)."""
+    if _is_lbfgs(args, kwargs):
+        raise ValueError("GrapeTimeSharded: method='LBFGS' is not supported; run Grape(method='LBFGS') on one GPU")
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
     if comm is None:
@@ -256,6 +278,9 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
     (tests/sharded_script.py checks array_equal); an engine that holds more control sets than it plans for says so on stderr when that changes
     the kernels it runs."""
     from quantum_optimal_control.parallel_seeds import SeedShard
+    if _is_lbfgs(args, kwargs):
+        # (before any rank builds an engine: every rank raises alike)
+        raise ValueError("GrapeSharded: method='LBFGS' is not supported; run Grape(method='LBFGS', restarts=R) on one GPU")
     if kwargs.get('robust') is not None:
         # (before any rank builds an engine: every rank raises alike)
         raise ValueError('GrapeSharded: robust ensembles are not supported; run Grape(robust=..., restarts=R) on one GPU')
