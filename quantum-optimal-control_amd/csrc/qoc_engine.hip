@@ -75,6 +75,7 @@ struct qoc_engine {
     int fin_S = 0;
     // mfma path
     QocMfma mf;
+    QocMfmaPlan mp;            // its launches, resolved by qoc_mfma_setup
     QocGemm gm;
     QocSmall sm;                // workgroup-resident path (csrc/qoc_small.h)
     bool evaluated = false;
@@ -306,7 +307,7 @@ static TailKind tail_kind(const qoc_engine* e) {
     // plain array (k_ens_reduce), never the persistent chains' partials
     if (e->ens_E) return ks > 4 * 1024 && e->fin_part ? TAIL_SPLIT : (ks <= 8 * 1024 && ks > 4 * 1024 ? TAIL_FINISH8 : TAIL_FINISH4);
     if (e->path == QOC_PATH_SMALL) return TAIL_IN_LAUNCH;
-    if (e->path == QOC_PATH_MFMA && e->mf.latency && (!e->mf.lat_sources || e->mf.lat_src_fast) && !d.has_band && !(e->skip_mask & (16 | 32)))
+    if (e->path == QOC_PATH_MFMA && e->mp.tail_fusable && !d.has_band && !(e->skip_mask & (16 | 32)))
         return TAIL_LATENCY_FUSED;
     if (ks > 4 * 1024 && e->fin_part)
         return e->path == QOC_PATH_GEMM && e->gm.persistent && e->skip_mask == 0 ? TAIL_SPLIT_PARTIALS : TAIL_SPLIT;
@@ -336,16 +337,16 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
     const int skip = e->skip_mask;
     if (e->path == QOC_PATH_MFMA) {
         TRY(prof_begin(e));
-        if (!(skip & 2)) qoc_mfma_launch_expm(e->mf, d, e->stream);
+        if (!(skip & 2)) qoc_mfma_launch_expm(e->mp, e->mf, d, e->stream);
         TRY(prof_end(e));
-        if (!(skip & 4)) qoc_mfma_launch_forward(e->mf, d, e->stream);
-        if (skip & 64) qoc_mfma_launch_forward(e->mf, d, e->stream);        // debug: the same launch again (cold-start vs steady cost)
-        if (skip & 128) qoc_mfma_launch_backward(e->mf, d, e->stream);
+        if (!(skip & 4)) qoc_mfma_launch_forward(e->mp, e->mf, d, e->stream);
+        if (skip & 64) qoc_mfma_launch_forward(e->mp, e->mf, d, e->stream);        // debug: the same launch again (cold-start vs steady cost)
+        if (skip & 128) qoc_mfma_launch_backward(e->mp, e->mf, d, e->stream);
         // latency mode / k_mfma_downup: inside the backward kernel
-        if (!(skip & 8) && !e->mf.updown && (!e->mf.latency || (e->mf.lat_sources && !e->mf.lat_src_fast))) launch_loss(d, e->stream);
+        if (!(skip & 8) && e->mp.engine_loss) launch_loss(d, e->stream);
         if (!(skip & 16)) {
-            if (fused_tail) qoc_mfma_latency_gradient(e->mf, d, &ap, e->stream);
-            else qoc_mfma_launch_backward(e->mf, d, e->stream);
+            if (fused_tail) qoc_mfma_latency_gradient(e->mp, e->mf, d, &ap, e->stream);
+            else qoc_mfma_launch_backward(e->mp, e->mf, d, e->stream);
         }
     } else if (e->path == QOC_PATH_GEMM && e->gm.ts_G > 0) {            // one trajectory sharded along the time axis (qoc_gemm_ts.h)
         const int rc = qoc_gemm_ts_evaluate(e->gm, d, e->stream, [&]() { launch_loss(d, e->stream); }, [&]() { return prof_begin(e); },
@@ -434,7 +435,7 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     if (e->path == QOC_PATH_SMALL) return enqueue_small(e, ap, 1);
     const TailKind tail = tail_kind(e);
     const int skip = e->skip_mask;
-    const bool own_controls = e->path == QOC_PATH_MFMA && e->mf.latency && e->mf.NT == 2;
+    const bool own_controls = e->path == QOC_PATH_MFMA && e->mp.own_controls;
     const bool swap_in = e->controls_ready && !own_controls && !(skip & 1);
     QocDev& cv = sets(e);                    // (an ensemble: the group view holds the controls of the control sets)
     if (swap_in) { std::swap(cv.u, cv.u2); std::swap(cv.w, cv.w2); }
@@ -442,7 +443,7 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     QocDev d = e->d;
     if (own_controls) { d.u2 = nullptr; d.w2 = nullptr; }
     d.skip_done = ap.mode == 1 ? 1 : 0;      // qoc_eval / explicit steps always evaluate every seed
-    d.uscale_in_loss = (e->path == QOC_PATH_MFMA && !e->mf.latency && !e->mf.updown) ? 1 : 0;
+    d.uscale_in_loss = (e->path == QOC_PATH_MFMA && e->mp.uscale_in_loss) ? 1 : 0;
     QocDev gd = e->g;
     gd.skip_done = d.skip_done;
     const bool fused_tail = tail == TAIL_LATENCY_FUSED;
@@ -455,11 +456,10 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     // the Adam tail ran: u2 / w2 belong to the moved variable
     e->controls_ready = ap.mode != 0 && !own_controls && !(skip & (16 | 32));
     // final_state / unitary_scale are formed when read back
-    e->final_stale = (e->path == QOC_PATH_MFMA && (e->mf.latency || e->mf.updown)) ||
+    e->final_stale = (e->path == QOC_PATH_MFMA && e->mp.final_on_readback) ||
                      (e->path == QOC_PATH_GEMM && e->gm.ts_G <= 0 && qoc_gemm_lazy_final(e->gm, e->d));
     // inter_vecs too, unless the batch kernels' source recursion needed them anyway
-    e->inter_stale = (e->path == QOC_PATH_MFMA && e->final_stale && (!e->mf.lat_sources || e->mf.lat_src_fast))
-                     || (e->path == QOC_PATH_MFMA && e->mf.updown);                  // (k_mfma_downup stores no Psi_t either)
+    e->inter_stale = e->path == QOC_PATH_MFMA && e->mp.inter_on_readback;          // (k_mfma_downup stores no Psi_t either)
     return QOC_OK;
 }
 
@@ -501,11 +501,11 @@ static int refresh_final(qoc_engine* e) {
     // the boundary chain once more, with X beside the vectors
     if (e->path == QOC_PATH_GEMM) qoc_gemm_forward(e->gm, e->d, e->stream, true);
     else if (e->d.state_transfer) {                                                    // no final_state; unitary_scale from Psi_N
-        if (e->inter_stale) { qoc_mfma_unpack_inter(e->mf, e->d, e->stream); e->inter_stale = false; }
+        if (e->inter_stale) { qoc_mfma_unpack_inter(e->mp, e->mf, e->d, e->stream); e->inter_stale = false; }
         qoc_mfma_uscale_state_transfer(e->d, e->stream);
     }
-    else if (e->mf.latency) qoc_mfma_final_state(e->mf, e->d, e->stream);
-    else qoc_mfma_final_state_batch(e->mf, e->d, e->stream);
+    else if (e->mp.final_from_groups) qoc_mfma_final_state(e->mp, e->mf, e->d, e->stream);
+    else qoc_mfma_final_state_batch(e->mp, e->mf, e->d, e->stream);
     HIP_TRY(hipGetLastError());
     e->final_stale = false;
     return QOC_OK;
@@ -905,7 +905,7 @@ static int setup_path(qoc_engine* e, const double* Hs, bool antiherm, const Auto
                                               "a Taylor degree >= 2 (n=%d k=%d T=%d)", c.n, c.k, d.T);
         // state transfer: sum_{j < T} A^j / j! is the polynomial of degree T - 1 (no squarings: d.s = 0)
         d.T = qoc_mfma_degree(d);
-        rc = qoc_mfma_setup(e->mf, d, c.chunks, (const cplx*)Hs, e->allocs, msg);
+        rc = qoc_mfma_setup(e->mf, e->mp, d, c.chunks, (const cplx*)Hs, e->allocs, msg);
         if (rc) return fail(rc, "qoc_create: %s", msg.c_str());
         e->chunks = e->mf.C;
         break;
@@ -1454,7 +1454,7 @@ int qoc_get_inter_vecs(qoc_handle e, double* inter) {
     if (e->path == QOC_PATH_GEMM) TRY(qoc_gemm_ts_gather_inter(e->gm, e->d, e->stream));
     if (e->path == QOC_PATH_SMALL) TRY(refresh_small(e, true));
     else if (e->inter_stale) {                                       // latency mode: the sweeps keep Psi_t in their own layout
-        qoc_mfma_unpack_inter(e->mf, e->d, e->stream);
+        qoc_mfma_unpack_inter(e->mp, e->mf, e->d, e->stream);
         HIP_TRY(hipGetLastError());
         e->inter_stale = false;
     }
@@ -1540,16 +1540,11 @@ int qoc_profile_enable(qoc_handle e, int32_t on) {
 int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, double* total_ms) {
     CHECK_H(e);
     TRY(prof_collect(e));
-    // the MFMA path's kernel of the exponentials by its variant 2 .. 8 (else k_mfma_expm_chunk; 5 with NT = 3: k_mfma_expm_rows per slice)
-    static const char* const expm[] = {"k_mfma_expm_chunk4", "k_mfma_expm_chunk4w", "k_mfma_expm_chunk4s",
-        "k_mfma_expm_slice2 + k_mfma_chain_rows", "k_mfma_expm_pair", "k_mfma_expm_rows", "k_mfma_expm_inplace"};
-    const int v = e->path == QOC_PATH_MFMA ? qoc_mfma_expm_variant(e->mf, e->d) : 0;
     if (kernel_name)
         *kernel_name = e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
                        : e->path == QOC_PATH_GEMM ? (e->gm.direct ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
                            : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
-                       : e->path == QOC_PATH_MFMA ? (v == 5 && e->mf.NT == 3 ? "k_mfma_expm_rows (per slice) + k_mfma_chain_rows"
-                           : v >= 2 && v <= 8 ? expm[v - 2] : "k_mfma_expm_chunk")
+                       : e->path == QOC_PATH_MFMA ? e->mp.expm_name             // (the kernel of the exponentials, by its variant)
                        : e->path == QOC_PATH_ST_FUSED ? "k_st_fwd_fused" : (e->d.state_transfer ? "k_st_fwd_generic" : "k_expm_generic");
     if (launches) *launches = e->prof_launches;
     if (total_ms) *total_ms = e->prof_ms;
@@ -1584,12 +1579,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
     char tmp[384];
     if (e->path == QOC_PATH_MFMA) {
-        const QocMfma& mf = e->mf;
-        const bool split = (mf.NT > 2 || (mf.NT == 2 && e->d.k >= 6)) && mf.variant != 1;
-        const char* sweeps = mf.latency ? (mf.lat_sources ? "latency_sources" : "latency")
-                             : mf.updown ? "downup" : (split ? (mf.grad_rt ? "row_tile_gradient" : "split") : (mf.variant == 1
-                                 || mf.NT == 1 || mf.NT == 4 ? "one_wave" : "pair"));
-        snprintf(tmp, sizeof tmp, "path=mfma nt=%d expm=%d chunks=%d sweeps=%s", mf.NT, qoc_mfma_expm_variant(mf, e->d), mf.C, sweeps);
+        snprintf(tmp, sizeof tmp, "path=mfma nt=%d expm=%d chunks=%d sweeps=%s", e->mf.NT, e->mp.expm_variant, e->mf.C, e->mp.sweeps);
     } else if (e->path == QOC_PATH_GEMM) {
         const QocGemm& g = e->gm;
         int w = snprintf(tmp, sizeof tmp, "path=gemm route=%s chunks=%d slices_per_chunk=%d chains=%s",
@@ -1617,7 +1607,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (tail == TAIL_IN_LAUNCH) add(" tail=%s", "in_launch");
     else if (tail == TAIL_SPLIT) add(" tail=split%d", e->fin_S);
     else if (tail == TAIL_SPLIT_PARTIALS) add(" tail=split%d_partials", e->fin_S);
-    else if (tail == TAIL_LATENCY_FUSED) add(" tail=latency_fused_%s", ks <= QF_E * 64 * (16 / e->mf.NT) * e->mf.NT ? "regs" : "memory");
+    else if (tail == TAIL_LATENCY_FUSED) add(" tail=latency_fused_%s", ks <= QF_E * (int)e->mp.grad_lat.block.x ? "regs" : "memory");
     else {
         const int threads = ks >= 2048 ? 1024 : QOC_BLOCK, qfe = tail == TAIL_FINISH8 ? 8 : QF_E;
         add(" tail=finish%d_%s", threads, tail == TAIL_FINISH8 ? "regs8" : (ks <= qfe * threads ? "regs" : "memory"));

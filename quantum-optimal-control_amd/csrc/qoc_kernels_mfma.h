@@ -29,7 +29,7 @@
 // own translation unit (qoc_mfma_expm.hip, qoc_mfma_forward.hip, qoc_mfma_backward.hip: the three compile in parallel) behind the
 // host entry points declared below.
 #pragma once
-#include "qoc_mfma_frag.h"
+#include "qoc_mfma_plan.h"
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 
@@ -84,16 +84,19 @@ static inline bool qoc_mfma_latency_ok(const QocDev& d) {
     return d.m <= 16 && d.k <= 8 && qoc_mfma_degree(d) >= 2 && qoc_mfma_degree(d) <= 22;
 }
 
-// host entry points (defined next to their kernels)
-int qoc_mfma_setup(QocMfma& mf, const QocDev& d, int chunks_req, const cplx* Hs_host, std::vector<void*>& allocs, std::string& msg);   // qoc_mfma_backward.hip
-void qoc_mfma_launch_expm(QocMfma& mf, const QocDev& d, hipStream_t s);       // qoc_mfma_expm.hip
-void qoc_mfma_launch_expm_inplace(QocMfma& mf, const QocDev& d, hipStream_t s);   // qoc_mfma_expm_inplace.hip (variant 8)
-void qoc_mfma_launch_forward(QocMfma& mf, const QocDev& d, hipStream_t s);    // qoc_mfma_forward.hip
-void qoc_mfma_launch_backward(QocMfma& mf, const QocDev& d, hipStream_t s);   // qoc_mfma_backward.hip
-void qoc_mfma_final_state(QocMfma& mf, const QocDev& d, hipStream_t s);       // qoc_mfma_expm.hip: latency mode, on read-back
-void qoc_mfma_uscale_state_transfer(const QocDev& d, hipStream_t s);            // qoc_mfma_forward.hip: state transfer on those routes, on read-back
-void qoc_mfma_final_state_batch(QocMfma& mf, const QocDev& d, hipStream_t s);   // qoc_mfma_forward.hip: k_mfma_downup batches, on read-back
-void qoc_mfma_unpack_inter(QocMfma& mf, const QocDev& d, hipStream_t s);      // qoc_mfma_forward.hip: latency mode, on read-back
-int qoc_mfma_latency_setup(QocMfma& mf, const QocDev& d, std::string& msg);    // qoc_mfma_latency.hip
-void qoc_mfma_latency_sweeps(QocMfma& mf, const QocDev& d, hipStream_t s);    //   forward + z-free adjoint sweep in one launch (lat_sources: forward only, then d.inter unpacked)
-void qoc_mfma_latency_gradient(QocMfma& mf, const QocDev& d, const QocAdamDev* fused_tail, hipStream_t s);  //   slice-parallel gradient, overlap z, loss
+// host entry points (defined next to their kernels).  qoc_mfma_setup fixes NT, C and the flags, allocates, and then has each translation unit
+// resolve its launches into the plan (qoc_mfma_plan.h; a message: an LDS reservation failed); the launchers walk the plan's records
+int qoc_mfma_setup(QocMfma& mf, QocMfmaPlan& plan, const QocDev& d, int chunks_req, const cplx* Hs_host, std::vector<void*>& allocs, std::string& msg);   // qoc_mfma_backward.hip
+const char* qoc_mfma_resolve_expm(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d);          // qoc_mfma_expm.hip
+void qoc_mfma_resolve_expm_inplace(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d);         // qoc_mfma_expm_inplace.hip (variant 8)
+void qoc_mfma_resolve_forward(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d);              // qoc_mfma_forward.hip
+const char* qoc_mfma_resolve_latency(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d);       // qoc_mfma_latency.hip
+void qoc_mfma_launch_expm(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);
+void qoc_mfma_launch_forward(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);
+void qoc_mfma_launch_backward(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);
+void qoc_mfma_latency_sweeps(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);    // forward + z-free adjoint sweep in one launch (lat_sources: forward only, then d.inter unpacked)
+void qoc_mfma_latency_gradient(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, const QocAdamDev* fused_tail, hipStream_t s);  // slice-parallel gradient, overlap z, loss
+void qoc_mfma_final_state(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);        // latency mode, on read-back
+void qoc_mfma_final_state_batch(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);  // k_mfma_downup batches, on read-back
+void qoc_mfma_unpack_inter(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s);       // latency mode / k_mfma_downup, on read-back
+void qoc_mfma_uscale_state_transfer(const QocDev& d, hipStream_t s);            // state transfer on those routes, on read-back

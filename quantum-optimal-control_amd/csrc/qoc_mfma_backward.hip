@@ -5,29 +5,65 @@
 #include "qoc_mfma_backward.h"
 #include "qoc_mfma_downup.h"
 
-// k_mfma_downup for this problem: 4 or 5 control images in LDS, active 4-row strips of the padded propagators = ceil(n / 4)
-static const void* qoc_downup_kernel(const QocDev& d) {
-    const int qa = qoc_active_strips(d.n);
-#define QOC_DU(KCv) (qa == 8 ? (const void*)k_mfma_downup<2, KCv, 8> : qa == 7 ? (const void*)k_mfma_downup<2, KCv, 7> : \
-                     qa == 6 ? (const void*)k_mfma_downup<2, KCv, 6> : (const void*)k_mfma_downup<2, KCv, 5>)
-    return d.k == 5 ? QOC_DU(5) : QOC_DU(4);
-#undef QOC_DU
+// The backward half of a batch iteration (and of the latency mode with a state regulariser on the batch kernels' recursion).
+// NT = 2: k <= 5 -> k_mfma_backward3 (pair of waves per item, control images in LDS) or k_mfma_downup; k >= 6 -> costate sweep + k_mfma_grad.
+// The choice must not depend on the batch size: the gradient sums associate differently between the kernels, and a seed has
+// to evolve bit-identically whatever batch / GPU it is sharded into.  variant 1 keeps the one-wave 16x16x4 kernel (A/B).
+template <int NT>
+static const char* qoc_resolve_backward(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, bool split_grad) {
+    const unsigned items = d.B * mf.C, g4 = (items + 3) / 4, slices = d.B * d.steps;
+    const bool src = d.n_forb > 0 || d.has_speed, fast = mf.variant != 1;
+    const QocOneOf<2, 4> mq{mf.mq <= 2 ? 2 : 4};
+    const QocOneOf<5, 4> kc{d.k == 5 ? 5 : 4};                          // control images in LDS
+    const QocOneOf<8, 7, 6, 5> qa{qoc_active_strips(d.n)};              // NT = 2: active 4-row strips of the padded propagators = ceil(n / 4)
+    if (src && mf.C > 1) {
+        const unsigned wpg = mf.lat_sources ? 1 : 4;                     // latency mode: one sweep per workgroup, i.e. per CU
+        if (NT == 2 && fast) qoc_pick([&](auto MQ, auto QA) { p.offsets.set(k_mfma_bwd_offsets2<MQ, false, QA>, (items + wpg - 1) / wpg, 64 * wpg); }, mq, qa);
+        else p.offsets.set(k_mfma_bwd_offsets<NT>, g4, 256);
+    }
+    if constexpr (NT == 2) if (fast && d.k <= 5) {
+        if (mf.lat_sources) {
+            // latency mode with a state regulariser: group offsets first, then the sweep with two-level affine boundaries; one pair of
+            // waves per workgroup (per CU)
+            qoc_pick([&](auto MQ, auto KC) {
+                p.sweep_groups.set(k_mfma_backward3<MQ, true, KC, 2>, d.B * mf.NG, 128, mf.bwd_lds3);
+                p.sweep.set(k_mfma_backward3<MQ, true, KC, 1>, items, 128, mf.bwd_lds3);
+            }, mq, kc);
+            return p.sweep_groups.reserve() && p.sweep.reserve() ? nullptr : "MFMA path: cannot reserve LDS for the two-level backward kernel";
+        }
+        const char* msg = "MFMA path: cannot reserve LDS for the prefetching backward kernel";
+        if (mf.updown) {                                                  // 4 items per workgroup, a wave per half chunk
+            qoc_pick([&](auto KC, auto QA) { p.sweep.set(k_mfma_downup<2, KC, QA>, g4, 512, mf.du_lds); }, kc, qa);
+            msg = "MFMA path: cannot reserve LDS for the fused sweep kernel";
+        } else if (mf.BndA) {                                             // 4 pairs of waves per workgroup
+            qoc_pick([&](auto MQ, auto KC) { p.sweep.set(k_mfma_backward3<MQ, false, KC, 3>, g4, 512, mf.bwd_lds3); }, mq, kc);
+            msg = "MFMA path: cannot reserve LDS for the backward kernel with precomputed boundaries";
+        }
+        // with a state regulariser on the active strips of K
+        else if (src) qoc_pick([&](auto MQ, auto KC, auto QA) { p.sweep.set(k_mfma_backward3<MQ, true, KC, 0, QA>, g4, 512, mf.bwd_lds3); }, mq, kc, qa);
+        else qoc_pick([&](auto MQ, auto KC) { p.sweep.set(k_mfma_backward3<MQ, false, KC>, g4, 512, mf.bwd_lds3); }, mq, kc);
+        return p.sweep.reserve() ? nullptr : msg;
+    }
+    if constexpr (NT >= 2) if (split_grad) {
+        // NT = 2, k >= 6: the control images fit in LDS next to no sweep's pads; costate sweep + slice-parallel gradient kernel (4 images
+        // per pass) instead of the row-split 16x16x4 sweep reading them from L2 (C2 x 64 with k = 8: 1.55 vs 1.71 ms per iteration)
+        if constexpr (NT == 2) qoc_pick([&](auto MQ, auto QA) { p.costates.set(k_mfma_bwd_offsets2<MQ, true, QA>, g4, 256); }, mq, qa);
+        // n > 32: the sweep only propagates the costates, the gradients are formed slice-parallel with the control images in LDS
+        // (no pad, no images; on the active strips ceil(n / 4) of the problem padded to 16 NT)
+        else qoc_pick([&](auto QA) { p.sweep1.set(k_mfma_backward<NT, false, true, QA>, g4, 256); }, QocOneOf<4 * NT - 3, 4 * NT - 2, 4 * NT - 1, 4 * NT>{(d.n + 3) / 4});
+        const unsigned cap = NT == 2 ? 2048 : 1024, gg = (slices + 3) / 4 < cap ? (slices + 3) / 4 : cap;
+        qoc_pick([&](auto MQ) {
+            if (mf.grad_rt) p.grad.set(k_mfma_grad_rt<NT, MQ>, NT * (gg < 512 ? gg : 512), 256, mf.grad_lds);
+            else p.grad.set(k_mfma_grad<NT, MQ>, gg, 256, mf.grad_lds);
+        }, mq);
+        if (mf.grad_rt) p.grad_sum.set(k_mfma_grad_sum, 256, 256);
+        return p.grad.reserve() ? nullptr : "MFMA path: cannot reserve LDS for the gradient kernel";
+    }
+    qoc_pick([&](auto H) { p.sweep1.set(k_mfma_backward<NT, H != 0>, g4, 256, mf.bwd_lds); }, QocOneOf<1, 0>{mf.h_in_lds});
+    return p.sweep1.reserve() ? nullptr : "MFMA path: cannot reserve LDS for the backward kernel";
 }
 
-// the batch sweep k_mfma_backward3<MODE 0>; with a state regulariser (the route that takes it by default) on the active strips of K
-static const void* qoc_backward3_kernel(const QocMfma& mf, const QocDev& d) {
-    const bool src = d.n_forb > 0 || d.has_speed;
-    const int qa = qoc_active_strips(d.n);
-#define QOC_B3S(MQv, KCv) (qa == 8 ? (const void*)k_mfma_backward3<MQv, true, KCv, 0, 8> : qa == 7 ? (const void*)k_mfma_backward3<MQv, true, KCv, 0, 7> : \
-                           qa == 6 ? (const void*)k_mfma_backward3<MQv, true, KCv, 0, 6> : (const void*)k_mfma_backward3<MQv, true, KCv, 0, 5>)
-#define QOC_B3K(MQv, KCv) (src ? QOC_B3S(MQv, KCv) : (const void*)k_mfma_backward3<MQv, false, KCv>)
-    if (d.k == 5) return mf.mq <= 2 ? QOC_B3K(2, 5) : QOC_B3K(4, 5);
-    return mf.mq <= 2 ? QOC_B3K(2, 4) : QOC_B3K(4, 4);
-#undef QOC_B3K
-#undef QOC_B3S
-}
-
-int qoc_mfma_setup(QocMfma& mf, const QocDev& d, int chunks_req, const cplx* Hs_host,
+int qoc_mfma_setup(QocMfma& mf, QocMfmaPlan& plan, const QocDev& d, int chunks_req, const cplx* Hs_host,
                                  std::vector<void*>& allocs, std::string& msg) {
     // (latency mode: NT = 2 kernels only -- a smaller problem is padded to 32: one trajectory of n = 16 runs 0.083 ms like n = 17, not 0.20)
     // (latency mode of 32 < n <= 48: NT = 3 with up to four controls, the NT = 4 kernels on the problem padded to 64 with more)
@@ -166,163 +202,47 @@ int qoc_mfma_setup(QocMfma& mf, const QocDev& d, int chunks_req, const cplx* Hs_
         const int kc = d.k == 5 ? 5 : 4;
         mf.bwd_lds3 = (size_t)kc * FR * sizeof(cplx) + (size_t)8 * 2 * 16 * B2_LDP * sizeof(cplx) + 4 * 2 * 2 * 4 * kc * sizeof(double);
     }
-    const void* b3k = qoc_backward3_kernel(mf, d);
     if (mf.latency) {
-        if (qoc_mfma_latency_setup(mf, d, msg) != 0) return -2;
         void* p = nullptr;
         if (hipMalloc(&p, (size_t)d.B * sizeof(unsigned)) != hipSuccess) { msg = "MFMA path: out of device memory"; return -3; }
         allocs.push_back(p);
         if (hipMemset(p, 0, (size_t)d.B * sizeof(unsigned)) != hipSuccess) { msg = "MFMA path: clearing the arrival counters failed"; return -2; }
         mf.lat_count = (unsigned*)p;
     }
-    if (NT == 2 && mf.lat_sources && d.k <= 5) {
-#define QOC_B3L(MQv, KCv, MODEv) (const void*)k_mfma_backward3<MQv, true, KCv, MODEv>
-        const void* k1 = d.k == 5 ? (mf.mq <= 2 ? QOC_B3L(2, 5, 1) : QOC_B3L(4, 5, 1)) : (mf.mq <= 2 ? QOC_B3L(2, 4, 1) : QOC_B3L(4, 4, 1));
-        const void* k2 = d.k == 5 ? (mf.mq <= 2 ? QOC_B3L(2, 5, 2) : QOC_B3L(4, 5, 2)) : (mf.mq <= 2 ? QOC_B3L(2, 4, 2) : QOC_B3L(4, 4, 2));
-#undef QOC_B3L
-        if (hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds3) != hipSuccess ||
-            hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds3) != hipSuccess) {
-            msg = "MFMA path: cannot reserve LDS for the two-level backward kernel";
-            return -2;
-        }
-    }
-    if (NT == 2 && mf.updown) {
+    if (mf.updown) {
         const int kc = d.k == 5 ? 5 : 4, mqv = mf.mq <= 2 ? 2 : 4;
         mf.du_lds = (size_t)kc * FR * sizeof(cplx) + (size_t)8 * 4 * mqv * F2_LDP * sizeof(cplx) + (size_t)4 * 2 * NT * mqv * 64 * sizeof(cplx) +
                     (size_t)8 * 4 * kc * sizeof(double) + 8 * sizeof(int);          // control images, wave images, exchange buffers, row partials, flags
-        if (hipFuncSetAttribute(qoc_downup_kernel(d), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.du_lds) != hipSuccess) {
-            msg = "MFMA path: cannot reserve LDS for the fused sweep kernel";
-            return -2;
-        }
     }
-    if (NT == 2 && bnd_adj) {
-        const void* k3 = d.k == 5 ? (mf.mq <= 2 ? (const void*)k_mfma_backward3<2, false, 5, 3> : (const void*)k_mfma_backward3<4, false, 5, 3>)
-                                  : (mf.mq <= 2 ? (const void*)k_mfma_backward3<2, false, 4, 3> : (const void*)k_mfma_backward3<4, false, 4, 3>);
-        if (hipFuncSetAttribute(k3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds3) != hipSuccess) {
-            msg = "MFMA path: cannot reserve LDS for the backward kernel with precomputed boundaries";
-            return -2;
-        }
-    }
-    if (NT == 2 && hipFuncSetAttribute(b3k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds3) != hipSuccess) {
-        msg = "MFMA path: cannot reserve LDS for the prefetching backward kernel";
-        return -2;
-    }
-    if (split_grad) {
-        const void* gk = NT == 2 ? (mf.mq <= 2 ? (const void*)k_mfma_grad<2, 2> : (const void*)k_mfma_grad<2, 4>)
-                       : NT == 3 ? (mf.mq <= 2 ? (const void*)k_mfma_grad<3, 2> : (const void*)k_mfma_grad<3, 4>)
-                                 : (mf.mq <= 2 ? (const void*)k_mfma_grad<4, 2> : (const void*)k_mfma_grad<4, 4>);
-        if (mf.grad_rt)
-            gk = NT == 2 ? (mf.mq <= 2 ? (const void*)k_mfma_grad_rt<2, 2> : (const void*)k_mfma_grad_rt<2, 4>)
-               : NT == 3 ? (mf.mq <= 2 ? (const void*)k_mfma_grad_rt<3, 2> : (const void*)k_mfma_grad_rt<3, 4>)
-                         : (mf.mq <= 2 ? (const void*)k_mfma_grad_rt<4, 2> : (const void*)k_mfma_grad_rt<4, 4>);
-        if (hipFuncSetAttribute(gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.grad_lds) != hipSuccess) { msg = "MFMA path: cannot reserve LDS for the gradient kernel"; return -2; }
-    }
-    if (mf.h_in_lds) {
-        const hipError_t e1 = hipFuncSetAttribute((const void*)k_mfma_backward<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds);
-        const hipError_t e2 = hipFuncSetAttribute((const void*)k_mfma_backward<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds);
-        const hipError_t e3 = hipFuncSetAttribute((const void*)k_mfma_backward<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds);
-        const hipError_t e4 = hipFuncSetAttribute((const void*)k_mfma_backward<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf.bwd_lds);
-        if ((NT == 1 ? e1 : (NT == 2 ? e2 : (NT == 3 ? e3 : e4))) != hipSuccess) {
-            msg = "MFMA path: cannot reserve LDS for the backward kernel";
-            return -2;
-        }
-    }
+    // every launch of an iteration and of the read-backs, once: the kernels, their grids, their LDS (reserved here and nowhere else), and what
+    // the engine needs to know about them
+    plan = QocMfmaPlan{};
+    const bool lat_own = mf.latency && (!mf.lat_sources || mf.lat_src_fast);       // latency mode on its own sweeps and gradient kernel
+    plan.engine_loss = !mf.updown && !lat_own;
+    plan.tail_fusable = lat_own;
+    plan.own_controls = mf.latency && NT == 2;
+    plan.uscale_in_loss = !mf.latency && !mf.updown;
+    plan.final_on_readback = mf.latency || mf.updown;
+    plan.final_from_groups = mf.latency;
+    plan.inter_on_readback = lat_own || mf.updown;
+    plan.sweeps = mf.latency ? (mf.lat_sources ? "latency_sources" : "latency")
+                  : mf.updown ? "downup" : (split_grad ? (mf.grad_rt ? "row_tile_gradient" : "split") : (mf.variant == 1 || NT == 1 || NT == 4 ? "one_wave" : "pair"));
+    const char* err = qoc_mfma_resolve_expm(plan, mf, d);
+    qoc_mfma_resolve_expm_inplace(plan, mf, d);
+    qoc_mfma_resolve_forward(plan, mf, d);
+    if (!err) err = qoc_mfma_resolve_latency(plan, mf, d);
+    if (!err && !lat_own) qoc_pick([&](auto NTc) { err = qoc_resolve_backward<NTc>(plan, mf, d, split_grad); }, QocOneOf<1, 2, 3, 4>{NT});
+    if (err) { msg = err; return -2; }
     return 0;
 }
 
-template <int NT>
-static inline void qoc_mfma_launch_all_backward(QocMfma& mf, const QocDev& d, hipStream_t s) {
-    const int items = d.B * mf.C;
-    if ((d.n_forb > 0 || d.has_speed) && mf.C > 1) {
-        if (NT == 2 && mf.variant != 1) {
-            const int wpg = mf.lat_sources ? 1 : 4;                      // latency mode: one sweep per workgroup, i.e. per CU
-#define QOC_O2(QAv) do { if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_bwd_offsets2<2, false, QAv>), dim3((items + wpg - 1) / wpg), dim3(64 * wpg), 0, s, d, mf); \
-                         else hipLaunchKernelGGL((k_mfma_bwd_offsets2<4, false, QAv>), dim3((items + wpg - 1) / wpg), dim3(64 * wpg), 0, s, d, mf); } while (0)
-            QOC_QA_SWITCH(qoc_active_strips(d.n), QOC_O2);
-#undef QOC_O2
-        } else {
-            hipLaunchKernelGGL(k_mfma_bwd_offsets<NT>, dim3((items + 3) / 4), dim3(256), 0, s, d, mf);
-        }
-    }
-    // NT = 2: k <= 5 -> k_mfma_backward3 (pair of waves per item, control images in LDS); k >= 6 -> costate sweep + k_mfma_grad.
-    // The choice must not depend on the batch size: the gradient sums associate differently between the kernels, and a seed has
-    // to evolve bit-identically whatever batch / GPU it is sharded into.  variant 1 keeps the one-wave 16x16x4 kernel (A/B).
-    if (NT == 2 && mf.variant != 1) {
-        if (d.k <= 5) {
-            const bool src = d.n_forb > 0 || d.has_speed;
-            if (mf.lat_sources) {
-                // latency mode with a state regulariser: group offsets first, then the sweep with two-level affine boundaries; one pair of
-                // waves per workgroup (per CU)
-                const dim3 gg(d.B * mf.NG), gc(items), b1(128);
-#define QOC_B3L(MQv, MODEv, GRID) do { if (d.k == 5) hipLaunchKernelGGL((k_mfma_backward3<MQv, true, 5, MODEv>), GRID, b1, mf.bwd_lds3, s, d, mf); \
-                                       else hipLaunchKernelGGL((k_mfma_backward3<MQv, true, 4, MODEv>), GRID, b1, mf.bwd_lds3, s, d, mf); } while (0)
-                if (mf.mq <= 2) { QOC_B3L(2, 2, gg); QOC_B3L(2, 1, gc); } else { QOC_B3L(4, 2, gg); QOC_B3L(4, 1, gc); }
-#undef QOC_B3L
-                return;
-            }
-            const dim3 g3((items + 3) / 4), b3(512);                     // 4 pairs of waves per workgroup
-#define QOC_B3B(MQv) do { if (d.k == 5) hipLaunchKernelGGL((k_mfma_backward3<MQv, false, 5, 3>), g3, b3, mf.bwd_lds3, s, d, mf); \
-                          else hipLaunchKernelGGL((k_mfma_backward3<MQv, false, 4, 3>), g3, b3, mf.bwd_lds3, s, d, mf); } while (0)
-            if (mf.updown && !src) {
-                const dim3 gd((items + 3) / 4), bd(512);                  // 4 items per workgroup, a wave per half chunk
-                void* kargs[] = {(void*)&d, (void*)&mf};
-                (void)hipLaunchKernel(qoc_downup_kernel(d), gd, bd, kargs, mf.du_lds, s);
-            }
-            else if (mf.BndA && !src) { if (mf.mq <= 2) QOC_B3B(2); else QOC_B3B(4); }
-            else {
-                void* kargs[] = {(void*)&d, (void*)&mf};
-                (void)hipLaunchKernel(qoc_backward3_kernel(mf, d), g3, b3, kargs, mf.bwd_lds3, s);
-            }
-#undef QOC_B3B
-            return;
-        }
-        {
-            // k >= 6: the control images fit in LDS next to no sweep's pads; costate sweep + slice-parallel gradient kernel (4 images
-            // per pass) instead of the row-split 16x16x4 sweep reading them from L2 (C2 x 64 with k = 8: 1.55 vs 1.71 ms per iteration)
-#define QOC_O2F(QAv) do { if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_bwd_offsets2<2, true, QAv>), dim3((items + 3) / 4), dim3(256), 0, s, d, mf); \
-                          else hipLaunchKernelGGL((k_mfma_bwd_offsets2<4, true, QAv>), dim3((items + 3) / 4), dim3(256), 0, s, d, mf); } while (0)
-            QOC_QA_SWITCH(qoc_active_strips(d.n), QOC_O2F);
-#undef QOC_O2F
-            const int slices = d.B * d.steps;
-            int gg = (slices + 3) / 4; if (gg > 2048) gg = 2048;
-            if (mf.grad_rt) {
-                if (gg > 512) gg = 512;
-                if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_grad_rt<2, 2>), dim3(2 * gg), dim3(256), mf.grad_lds, s, d, mf);
-                else hipLaunchKernelGGL((k_mfma_grad_rt<2, 4>), dim3(2 * gg), dim3(256), mf.grad_lds, s, d, mf);
-                hipLaunchKernelGGL(k_mfma_grad_sum, dim3(256), dim3(256), 0, s, d, mf, 2);
-            }
-            else if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_grad<2, 2>), dim3(gg), dim3(256), mf.grad_lds, s, d, mf);
-            else hipLaunchKernelGGL((k_mfma_grad<2, 4>), dim3(gg), dim3(256), mf.grad_lds, s, d, mf);
-        }
-        return;
-    }
-    if (NT > 2 && mf.variant != 1) {
-        // n > 32: the sweep only propagates the costates, the gradients are formed slice-parallel with the control images in LDS
-        // (no pad, no images; on the active strips ceil(n / 4) of the problem padded to 16 NT)
-#define QOC_BWS(QAv) hipLaunchKernelGGL((k_mfma_backward<NT, false, true, QAv>), dim3((items + 3) / 4), dim3(256), 0, s, d, mf, 0)
-        switch (4 * NT - (d.n + 3) / 4) { case 3: QOC_BWS(4 * NT - 3); break; case 2: QOC_BWS(4 * NT - 2); break; case 1: QOC_BWS(4 * NT - 1); break; default: QOC_BWS(4 * NT); break; }
-#undef QOC_BWS
-        const int slices = d.B * d.steps;
-        int gg = (slices + 3) / 4; if (gg > 1024) gg = 1024;
-        constexpr int GN = NT > 2 ? NT : 3;                                  // (never launched for NT <= 2)
-        if (mf.grad_rt) {
-            int g2 = (slices + 3) / 4; if (g2 > 512) g2 = 512;
-            if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_grad_rt<GN, 2>), dim3(GN * g2), dim3(256), mf.grad_lds, s, d, mf);
-            else hipLaunchKernelGGL((k_mfma_grad_rt<GN, 4>), dim3(GN * g2), dim3(256), mf.grad_lds, s, d, mf);
-            hipLaunchKernelGGL(k_mfma_grad_sum, dim3(256), dim3(256), 0, s, d, mf, GN);
-            return;
-        }
-        if (mf.mq <= 2) hipLaunchKernelGGL((k_mfma_grad<GN, 2>), dim3(gg), dim3(256), mf.grad_lds, s, d, mf);
-        else hipLaunchKernelGGL((k_mfma_grad<GN, 4>), dim3(gg), dim3(256), mf.grad_lds, s, d, mf);
-        return;
-    }
-    if (mf.h_in_lds)
-        hipLaunchKernelGGL((k_mfma_backward<NT, true>), dim3((items + 3) / 4), dim3(256), mf.bwd_lds, s, d, mf, 0);
-    else
-        hipLaunchKernelGGL((k_mfma_backward<NT, false>), dim3((items + 3) / 4), dim3(256), mf.bwd_lds, s, d, mf, 0);
+void qoc_mfma_launch_backward(const QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, hipStream_t s) {
+    if (p.tail_fusable) { qoc_mfma_latency_gradient(p, mf, d, nullptr, s); return; }
+    p.offsets.run(s, d, mf);
+    p.costates.run(s, d, mf);
+    p.sweep_groups.run(s, d, mf);
+    p.sweep.run(s, d, mf);
+    p.sweep1.run(s, d, mf, 0);
+    p.grad.run(s, d, mf);
+    p.grad_sum.run(s, d, mf, mf.NT);
 }
-void qoc_mfma_launch_backward(QocMfma& mf, const QocDev& d, hipStream_t s) {
-    if (mf.latency && (!mf.lat_sources || mf.lat_src_fast)) { qoc_mfma_latency_gradient(mf, d, nullptr, s); return; }
-    if (mf.NT == 1) qoc_mfma_launch_all_backward<1>(mf, d, s); else if (mf.NT == 2) qoc_mfma_launch_all_backward<2>(mf, d, s); else if (mf.NT == 3) qoc_mfma_launch_all_backward<3>(mf, d, s); else qoc_mfma_launch_all_backward<4>(mf, d, s);
-}
-

@@ -1,18 +1,12 @@
-// qoc_mfma_expm_inplace.hip -- translation unit of k_mfma_expm_inplace (qoc_mfma_expm_inplace.h) and its launcher.
+// qoc_mfma_expm_inplace.hip -- translation unit of k_mfma_expm_inplace (qoc_mfma_expm_inplace.h) and its resolver.
 // Compiled with -mllvm -amdgpu-mfma-vgpr-form (__graft_entry__.UNIT_FLAGS): the accumulators of its products live in VGPRs.
 #include "qoc_kernels_mfma.h"
 #include "qoc_mfma_expm_inplace.h"
 
-void qoc_mfma_launch_expm_inplace(QocMfma& mf, const QocDev& d, hipStream_t s) {
-    const dim3 grid(d.B * mf.C), block(64);
-    const bool even = (d.T & 1) == 0, s0 = d.s == 0;
-    // active 4-row strips of the padded 32 x 32 matrices: ceil(n / 4) (17 <= n <= 32: 5 .. 8)
-    const int qa = qoc_active_strips(d.n);
-#define QOC_IP(KCv, EVv, S0v) do { if (qa == 8) hipLaunchKernelGGL((k_mfma_expm_inplace<KCv, EVv, S0v, 8>), grid, block, 0, s, d, mf); \
-                                   else if (qa == 7) hipLaunchKernelGGL((k_mfma_expm_inplace<KCv, EVv, S0v, 7>), grid, block, 0, s, d, mf); \
-                                   else if (qa == 6) hipLaunchKernelGGL((k_mfma_expm_inplace<KCv, EVv, S0v, 6>), grid, block, 0, s, d, mf); \
-                                   else hipLaunchKernelGGL((k_mfma_expm_inplace<KCv, EVv, S0v, 5>), grid, block, 0, s, d, mf); } while (0)
-    if (d.k <= 4) { if (even) { if (s0) QOC_IP(4, true, true); else QOC_IP(4, true, false); } else { if (s0) QOC_IP(4, false, true); else QOC_IP(4, false, false); } }
-    else { if (even) { if (s0) QOC_IP(8, true, true); else QOC_IP(8, true, false); } else { if (s0) QOC_IP(8, false, true); else QOC_IP(8, false, false); } }
-#undef QOC_IP
+// variant 8 (after qoc_mfma_resolve_expm): 4 or 8 control images, even / odd Taylor degree, s = 0, active 4-row strips of the padded 32 x 32
+// matrices: ceil(n / 4) (17 <= n <= 32: 5 .. 8)
+void qoc_mfma_resolve_expm_inplace(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d) {
+    if (p.expm_variant != 8) return;
+    qoc_pick([&](auto KC, auto EVEN, auto S0, auto QA) { p.expm.set(k_mfma_expm_inplace<KC, EVEN != 0, S0 != 0, QA>, d.B * mf.C, 64); },
+             QocOneOf<4, 8>{d.k <= 4 ? 4 : 8}, QocOneOf<1, 0>{(d.T & 1) == 0}, QocOneOf<1, 0>{d.s == 0}, QocOneOf<8, 7, 6, 5>{qoc_active_strips(d.n)});
 }

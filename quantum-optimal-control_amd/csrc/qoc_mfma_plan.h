@@ -1,0 +1,74 @@
+// qoc_mfma_plan.h -- host side of the MFMA path: which kernel every launch of an iteration and of a read-back is, with what grid, block and
+// dynamic LDS.  qoc_mfma_setup resolves all of it once (one resolver per translation unit, next to the kernels it picks from) and opts the
+// picked kernels in for their LDS; the launchers walk the records.  QocMfma stays the kernels' argument; the plan lives beside it in the engine.
+#pragma once
+#include <type_traits>
+#include "qoc_mfma_frag.h"
+
+// one launch, typed by the kernel's argument list.  fn == nullptr: this engine never makes the launch
+template <class... A> struct QocLaunch {
+    void (*fn)(A...) = nullptr;
+    dim3 grid, block;
+    size_t lds = 0;
+    void set(void (*f)(A...), unsigned g, unsigned b, size_t l = 0) { fn = f; grid = dim3(g); block = dim3(b); lds = l; }
+    void run(hipStream_t s, const A&... a) const { if (fn) hipLaunchKernelGGL(fn, grid, block, lds, s, a...); }
+    bool reserve() const { return !fn || !lds || hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }
+};
+
+// the one idiom for the template ladders: qoc_pick(f, QocOneOf<4, 8>{kc}, QocOneOf<8, 7, 6, 5>{qa}) calls f(integral_constant<int, kc>,
+// integral_constant<int, qa>) -- each run-time value as the compile-time constant of its list that equals it, the LAST of the list when none does
+template <int... Vs> struct QocOneOf { int v; };
+template <class F> static inline void qoc_pick(F&& f) { f(); }
+template <class F, int V0, int... Vs, class... Rest> static inline void qoc_pick(F&& f, QocOneOf<V0, Vs...> a, Rest... rest) {
+    if constexpr (sizeof...(Vs) > 0) { if (a.v != V0) { qoc_pick(f, QocOneOf<Vs...>{a.v}, rest...); return; } }
+    qoc_pick([&](auto... c) { f(std::integral_constant<int, V0>{}, c...); }, rest...);
+}
+
+struct QocMfmaPlan {
+    using K1 = QocLaunch<QocDev>;
+    using K2 = QocLaunch<QocDev, QocMfma>;
+    using K3 = QocLaunch<QocDev, QocMfma, int>;
+    using KScan = QocLaunch<QocDev, QocMfma, int, int, const cplx*, const cplx*, int>;
+    using KChain = QocLaunch<QocDev, QocMfma, const cplx*, int, int, int, cplx*, int, const cplx*, cplx*>;
+    using KGradLat = QocLaunch<QocDev, QocMfma, QocAdamDev, int>;
+    // an iteration, in launch order.  qoc_mfma_launch_expm: K_t (batch kernels: with the chunk products), latency mode: chunk and group products
+    K2 expm;
+    KChain chain_chunks, chain_groups;
+    // qoc_mfma_launch_forward: chunk boundaries, the sweep (none: it runs inside k_mfma_downup), unitary_scale unless k_loss forms it
+    KScan scan;
+    K2 forward;
+    K1 uscale;
+    // ... in latency mode (qoc_mfma_latency_sweeps): both sweeps, then the loss from PsiL or (batch backward kernels) d.inter for k_loss
+    K3 sweep_lat;
+    K2 loss_lat;
+    K3 sweep_unpack;
+    // qoc_mfma_launch_backward: chunk offsets of the source recursion, costates for the gradient kernel, group sweep, the sweep (by its
+    // signature: k_mfma_backward3 / k_mfma_downup or k_mfma_backward), the slice-parallel gradient and the sum of its row-tile partials
+    K2 offsets, costates, sweep_groups, sweep;
+    K3 sweep1;
+    K2 grad;
+    K3 grad_sum;
+    // qoc_mfma_latency_gradient: chunk offsets, group offsets and total costate of the source recursion, then the gradient (+ the fused tail)
+    K3 src_chunks, src_groups, src_total;
+    KGradLat grad_lat;
+    // read-backs: qoc_mfma_final_state (latency mode), qoc_mfma_final_state_batch (k_mfma_downup), qoc_mfma_unpack_inter
+    KChain final_chain;
+    K2 final_unpack;
+    KScan final_scan;
+    K1 final_uscale;
+    K3 inter_unpack;
+    K2 inter_forward;
+    // fixed integer arguments of these launches
+    int MQ = 4, scan_flags = 0, final_scan_flags = 0, sweep_offsets = 0;
+    // what the engine needs to know, by name
+    bool engine_loss = true;           // the engine launches k_loss between the sweeps (else a sweep kernel forms the loss)
+    bool tail_fusable = false;         // the gradient kernel can run the tail of the iteration (qoc_mfma_latency_gradient with Adam parameters)
+    bool own_controls = false;         // the slice kernel forms its own controls
+    bool uscale_in_loss = false;       // QocDev::uscale_in_loss of an iteration
+    bool final_on_readback = false;    // final_state / unitary_scale are formed when read back ...
+    bool final_from_groups = false;    //   ... by qoc_mfma_final_state (else qoc_mfma_final_state_batch)
+    bool inter_on_readback = false;    // inter_vecs too (qoc_mfma_unpack_inter)
+    const char* sweeps = "";           // qoc_plan_describe: sweeps=<word> expm=<number>
+    int expm_variant = 1;
+    const char* expm_name = "";        // qoc_profile_read
+};

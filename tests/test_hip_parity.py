@@ -127,12 +127,40 @@ def test_fused_sweep_kernel_edge_shapes(n, k, steps, m, chunks, seeds):
     eng.close()
 
 
-@pytest.mark.parametrize('kernel', [1, 2, 3, 4, 5, 6, 7, 8], ids=['mfma16', 'mfma4_two_waves', 'mfma4_one_wave', 'mfma4_streamed_image', 'latency_mode', 'mfma4_pair_two_per_simd', 'mfma4_row_blocks',
-                                                                 'mfma4_inplace_image'])
-@pytest.mark.parametrize('variant', ['plain', 'sources', 'small_n', 'dressed', 'n40_nt3', 'n48_k4_sources_nt3', 'n64_nt4', 'n18_T2_s1', 'n32_T3_s0',
-                                     'n25_k8_T7', 'n17_k1_T4_s4', 'n30_m13_k2', 'n32_m4_k3', 'n26_k5_plain', 'n28_k7_sources', 'n26_k5_sources',
-                                     'n22_dressed3', 'n40_dressed_nt3', 'n20_dressed5', 'n44_k6'])
-@pytest.mark.parametrize('chunks', [0, 1, 7])
+EXPM_KERNEL_IDS = ['mfma16', 'mfma4_two_waves', 'mfma4_one_wave', 'mfma4_streamed_image', 'latency_mode', 'mfma4_pair_two_per_simd', 'mfma4_row_blocks', 'mfma4_inplace_image']
+EXPM_SHAPES = ['plain', 'sources', 'small_n', 'dressed', 'n40_nt3', 'n48_k4_sources_nt3', 'n64_nt4', 'n18_T2_s1', 'n32_T3_s0',
+               'n25_k8_T7', 'n17_k1_T4_s4', 'n30_m13_k2', 'n32_m4_k3', 'n26_k5_plain', 'n28_k7_sources', 'n26_k5_sources',
+               'n22_dressed3', 'n40_dressed_nt3', 'n20_dressed5', 'n44_k6']
+# Single rows beside the full grid: (shape, kernel) pairs that run the kernel instances the grid does not reach -- the active-strip counts at both
+# ends of every 4-wide band of n, the even / odd degree and s = 0 instances of k_mfma_expm_inplace, 5 and 8 control images, both column-group
+# counts, the read-back of a state transfer.  The list is the greedy cover that tools/mfma_launch_trace.hip (-s 0 against -f <the rows here>) gives for
+# the instances an engine can reach without an experimental switch.  A shape: n, k, m, Taylor terms, scaling, state regulariser (none, undressed
+# forbidden levels, speed_up, dressed levels x 3, x 5), or state transfer (st); 12 slices, AUTO chunks.
+EXPM_COVER_ROWS = [
+    ('cover_n1_k5_m1_T5_s2_none', 5), ('cover_n9_k1_m5_T5_s2_forbidden', 1), ('cover_n9_k1_m9_T5_s2_dressed5', 5), ('cover_n9_k5_m9_T5_s2_none', 5),
+    ('cover_n9_k6_m9_T5_s2_none', 5), ('cover_n9_k6_m9_T5_s2_dressed5', 5), ('cover_n17_k1_m5_T3_s0_none', 8), ('cover_n17_k1_m12_T4_s0_forbidden', 8),
+    ('cover_n17_k5_m5_T4_s0_forbidden', 8), ('cover_n17_k5_m5_T5_s2_none', 8), ('cover_n17_k5_m12_T3_s0_none', 8), ('cover_n17_k5_m12_T4_s2_forbidden', 8),
+    ('cover_n17_k6_m5_T5_s2_dressed5', 5), ('cover_n21_k1_m5_T4_s0_none', 8), ('cover_n21_k1_m5_T4_s2_none', 8), ('cover_n21_k1_m12_T3_s0_forbidden', 8),
+    ('cover_n21_k5_m5_T4_s0_forbidden', 8), ('cover_n21_k5_m5_T5_s2_none', 8), ('cover_n21_k5_m12_T3_s0_forbidden', 8), ('cover_n21_k5_m12_T5_s2_dressed5', 5),
+    ('cover_n21_k6_m5_T5_s2_none', 2), ('cover_n25_k1_m5_T3_s0_forbidden', 8), ('cover_n25_k1_m5_T4_s0_none', 8), ('cover_n25_k1_m5_T4_s2_none', 8),
+    ('cover_n25_k1_m5_T5_s2_none', 5), ('cover_n25_k1_m12_T5_s2_forbidden', 8), ('cover_n25_k5_m5_T4_s2_none', 8), ('cover_n25_k5_m12_T4_s0_forbidden', 8),
+    ('cover_n25_k6_m12_T3_s0_none', 8), ('cover_n29_k1_m5_T5_s2_forbidden', 2), ('cover_n29_k1_m12_T4_s0_forbidden', 8), ('cover_n29_k5_m5_T4_s0_forbidden', 8),
+    ('cover_n29_k5_m5_T5_s2_none', 8), ('cover_n29_k5_m5_T5_s2_dressed5', 5), ('cover_n29_k5_m12_T3_s0_forbidden', 8), ('cover_n29_k6_m5_T4_s2_none', 8),
+    ('cover_n29_k6_m12_T5_s2_none', 2), ('cover_n33_k1_m5_T5_s2_none', 3), ('cover_n33_k1_m5_T5_s2_none', 5), ('cover_n33_k5_m12_T5_s2_none', 3),
+    ('cover_n37_k5_m12_T5_s2_none', 3), ('cover_n41_k1_m5_T5_s2_none', 5), ('cover_n41_k1_m12_T5_s2_none', 3), ('cover_n45_k5_m5_T5_s2_none', 3),
+    ('cover_n49_k1_m5_T5_s2_none', 1), ('cover_n49_k1_m12_T5_s2_none', 3), ('cover_n49_k1_m12_T5_s2_dressed3', 5), ('cover_n49_k5_m5_T5_s2_none', 3),
+    ('cover_n53_k1_m5_T5_s2_none', 3), ('cover_n53_k1_m5_T5_s2_none', 5), ('cover_n53_k5_m5_T5_s2_none', 3), ('cover_n53_k5_m5_T5_s2_none', 5),
+    ('cover_n57_k1_m5_T5_s2_none', 5), ('cover_n57_k5_m5_T5_s2_none', 3), ('cover_n57_k5_m5_T5_s2_none', 5), ('cover_n61_k5_m5_T5_s2_none', 3),
+    ('cover_n61_k5_m5_T5_s2_none', 5), ('cover_st_n20_k3', 8), ('cover_st_n20_k3', 5),
+]
+
+
+def expm_kernel_rows():
+    rows = [(chunks, shape, kernel) for kernel in range(1, 9) for shape in EXPM_SHAPES for chunks in (0, 1, 7)]
+    return rows + [(0, shape, kernel) for shape, kernel in EXPM_COVER_ROWS]
+
+
+@pytest.mark.parametrize('chunks,variant,kernel', expm_kernel_rows(), ids=['%d-%s-%s' % (c, v, EXPM_KERNEL_IDS[k - 1]) for c, v, k in expm_kernel_rows()])
 def test_mfma_exponential_kernels(chunks, variant, kernel):
     """The four kernels of the exponentials (qoc_config.variant), whatever AUTO would pick (n > 32: variants 3, 4 = variant 2;
     n <= 16: variant 4 = variant 3)."""
@@ -195,6 +223,25 @@ def _mfma_path_parity(chunks, variant, kernel):
         c['reg_coeffs'] = {'forbidden_coeff_list': [3.0], 'states_forbidden_list': [43], 'dwdt': 0.1}
     elif variant == 'n57_k1_nt4':
         c = cases.case_c2(n=57, k=1, steps=9, m=3, taylor=(4, 1), seed=15)
+    elif variant.startswith('cover_st_'):
+        n_, k_ = (int(x[1:]) for x in variant.split('_')[2:])
+        c = cases.case_c3(n=n_, k=k_, steps=12, taylor=(8, 0))
+        c['total_time'] = 1.0
+    elif variant.startswith('cover_'):
+        # cover_n<n>_k<k>_m<m>_T<terms>_s<scaling>_<none | forbidden | speedup | dressed3 | dressed5>
+        n_, k_, m_, T_, s_ = (int(x[1:]) for x in variant.split('_')[1:6])
+        reg = variant.split('_')[6]
+        c = cases.case_c2(n=n_, k=k_, steps=12, m=m_, taylor=(T_, s_), seed=100 + n_ + k_)
+        if reg == 'forbidden':
+            c['reg_coeffs'] = {'forbidden_coeff_list': [3.0, 2.0], 'states_forbidden_list': [n_ - 1, n_ - 2]}
+        elif reg == 'speedup':
+            c['reg_coeffs'] = {'speed_up': 0.4}
+        elif reg.startswith('dressed'):
+            from quantum_optimal_control.helper_functions import grape_functions as gf
+            lv = [n_ - 1, n_ - 2, 1, 2, 3][:int(reg[7:])]
+            w, v, did = gf.get_dressed_info(c['H0'])
+            c['dressed_info'] = dict(eigenvectors=v, dressed_id=did, eigenvalues=w, is_dressed=True)
+            c['reg_coeffs'] = {'dwdt': 0.1, 'forbidden_coeff_list': [3.0 + i for i in range(len(lv))], 'states_forbidden_list': lv, 'forbid_dressed': True}
     else:
         c = cases.case_dressed()
     sp = oracle_system(c)
