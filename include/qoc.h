@@ -165,6 +165,22 @@ int qoc_get_member_scalars(qoc_handle h, double* loss, double* reg_state);
 /* Every member's final unitary of the last evaluation: [n_seeds][E][n][n] complex (unitary mode only). */
 int qoc_get_member_final_unitary(qoc_handle h, double* Uf);
 
+/* ---- risk-sensitive robust GRAPE: the soft worst case over the members in place of their weighted mean (no counterpart in the reference) ----
+ * With beta > 0, the member costs c_e = loss_e + (forbidden levels + speed_up)_e and c_max their maximum, per control set:
+ *   J        = c_max + log1p(sum_e weights[e] expm1(beta (c_e - c_max))) / beta     (members summed in the order 0 .. E-1)
+ *   pi_e     = weights[e] exp(beta (c_e - c_max)) / (1 + that sum)                  = dJ / dc_e, the tilted weights
+ *   grad     : the members' gradients weighted by pi_e in place of weights[e]
+ *   reg_state = sum_e pi_e (forbidden levels + speed_up)_e;  loss = J - reg_state  (the value the stop rule tests: J itself without state
+ *   regularisers);  reg_loss = J + the pulse regularisers;  unitary_scale stays the weights' mean.
+ * With sum weights = 1, mean <= J <= max; beta = 0 (the default) is the weighted mean of qoc_create_ensemble, bit for bit, and beta -> infinity
+ * the hard worst case (exp underflows to 0 on every member but the worst).  Valid on engines made by qoc_create_ensemble or qoc_create_shaped
+ * (QOC_ERR_STATE on any other); beta negative, NaN or infinite: QOC_ERR_INVALID.  May be called between evaluations (annealing): it waits for
+ * the enqueued work and holds from the next evaluation.  The first call with beta > 0 allocates the [n_seeds][E] weights. */
+int qoc_set_risk(qoc_handle h, double beta);
+/* pi_e of the last evaluation, [n_seeds][E]; the weights themselves at beta = 0 (and before the first evaluation under a risk).  A control
+ * set that a loop has finished keeps the weights of its last evaluation.  QOC_ERR_STATE on a non-ensemble engine. */
+int qoc_get_member_weights(qoc_handle h, double* pi);
+
 /* ---- transfer-function GRAPE: the variable is the AWG's samples, the pulse a known linear response of them (no counterpart in the
  * reference, whose dwdt / bandpass / envelope penalties shrink what a line will not pass but do not model what it does) ----------------
  * T is a real steps x n_samples matrix (zero-order hold, interpolation, a filter or line response).  Per control set, with the variable

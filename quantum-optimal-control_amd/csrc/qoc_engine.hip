@@ -98,6 +98,9 @@ struct qoc_engine {
     QocDev g;
     QocEns en{};
     std::vector<double> ens_wt;     // host copy of the weights (unitary_scale of a group is formed on read-back)
+    // risk-sensitive objective (qoc_set_risk, k_ens_tilt): beta > 0 replaces the weighted mean by the soft worst case over the members
+    double risk_beta = 0.0;
+    double* risk_pi = nullptr;      // [G][E] tilted weights of the last evaluation, allocated by the first qoc_set_risk with beta > 0
     // transfer-function GRAPE (qoc_create_shaped, csrc/qoc_transfer.h): an ensemble engine whose group view is the SAMPLE view (P samples per
     // control in place of the time slices) and whose glue kernels apply the response matrix
     bool shaped = false;
@@ -390,10 +393,21 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
     }
     return QOC_OK;
 }
+// the soft worst case of one member is that member, whatever beta: a one-member ensemble keeps the mean's launches
+static inline bool risk_on(const qoc_engine* e) { return e->risk_beta > 0.0 && e->ens_E > 1; }
 // 3. an ensemble: the members' gradients and losses, weighted, into the group view
 static void enqueue_ens_reduce(const qoc_engine* e, const QocDev& d, const QocDev& gd) {
     const int ks = gd.k * gd.steps;
     const dim3 per_thread((unsigned)((ks + 255) / 256), (unsigned)gd.B), per_wave((unsigned)((ks + 3) / 4), (unsigned)gd.B);
+    if (risk_on(e)) {
+        // the tilted weights and the scalars of every control set from its members' costs, then the same reduce with those weights
+        hipLaunchKernelGGL(k_ens_tilt, dim3((unsigned)gd.B), dim3(QOC_TILT_BLOCK), 0, e->stream, d, gd, e->en, e->risk_beta, e->risk_pi);
+        if (!e->shaped) hipLaunchKernelGGL(k_ens_reduce_risk, per_thread, dim3(256), 0, e->stream, d, gd, e->en, e->risk_pi);
+        else if (e->sh.col_band <= QOC_SHAPE_WAVE_FROM)
+            hipLaunchKernelGGL(k_shape_reduce_risk<1>, per_thread, dim3(256), 0, e->stream, d, gd, e->en, e->sh, e->risk_pi);
+        else hipLaunchKernelGGL(k_shape_reduce_risk<64>, per_wave, dim3(256), 0, e->stream, d, gd, e->en, e->sh, e->risk_pi);
+        return;
+    }
     if (!e->shaped) hipLaunchKernelGGL(k_ens_reduce, per_thread, dim3(256), 0, e->stream, d, gd, e->en);
     else if (e->sh.col_band <= QOC_SHAPE_WAVE_FROM)
         hipLaunchKernelGGL(k_shape_reduce<1>, per_thread, dim3(256), 0, e->stream, d, gd, e->en, e->sh);
@@ -1513,6 +1527,43 @@ int qoc_get_member_scalars(qoc_handle e, double* loss, double* reg_state) {
     const size_t sz = (size_t)e->d.B * sizeof(double);
     if (loss) HIP_TRY(hipMemcpy(loss, e->d.loss, sz, hipMemcpyDeviceToHost));
     if (reg_state) HIP_TRY(hipMemcpy(reg_state, e->d.reg_state, sz, hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+// the weights every control set starts from: the members' own
+static int risk_fill_weights(qoc_engine* e) {
+    const size_t E = (size_t)e->ens_E;
+    std::vector<double> w((size_t)e->g.B * E);
+    for (size_t i = 0; i < w.size(); ++i) w[i] = e->ens_wt[i % E];
+    HIP_TRY(hipMemcpy(e->risk_pi, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    return QOC_OK;
+}
+
+int qoc_set_risk(qoc_handle e, double beta) {
+    CHECK_H(e);
+    if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_set_risk: not an ensemble engine (qoc_create_ensemble, qoc_create_shaped)");
+    if (std::isnan(beta)) return fail(QOC_ERR_INVALID, "qoc_set_risk: beta is NaN");
+    if (std::isinf(beta)) return fail(QOC_ERR_INVALID, "qoc_set_risk: beta is infinite (a hard maximum is the limit of large finite beta)");
+    if (beta < 0.0) return fail(QOC_ERR_INVALID, "qoc_set_risk: beta = %g is negative (>= 0; 0 is the weighted mean)", beta);
+    HIP_TRY(hipStreamSynchronize(e->stream));            // (the evaluations enqueued so far keep the beta they were enqueued with)
+    if (beta > 0.0 && !e->risk_pi) TRY(dev_alloc(e, &e->risk_pi, (size_t)e->g.B * e->ens_E));
+    // leaving the mean: a control set that is not evaluated again (finished in a loop) holds the members' own weights
+    if (beta > 0.0 && e->risk_beta == 0.0) TRY(risk_fill_weights(e));
+    e->risk_beta = beta;
+    return QOC_OK;
+}
+
+int qoc_get_member_weights(qoc_handle e, double* pi) {
+    CHECK_H(e);
+    if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_weights: not an ensemble engine (qoc_create_ensemble, qoc_create_shaped)");
+    if (!pi) return fail(QOC_ERR_INVALID, "qoc_get_member_weights: null output");
+    const size_t E = (size_t)e->ens_E, cnt = (size_t)e->g.B * E;
+    if (!risk_on(e)) {
+        for (size_t i = 0; i < cnt; ++i) pi[i] = e->ens_wt[i % E];
+        return QOC_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(pi, e->risk_pi, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 

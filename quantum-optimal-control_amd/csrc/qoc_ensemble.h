@@ -75,3 +75,82 @@ __global__ void __launch_bounds__(256) k_ens_reduce(QocDev t, QocDev g, QocEns e
         g.reg_state[gi] = r;
     }
 }
+
+// ---- risk-sensitive ensembles (qoc_set_risk, beta > 0): the soft worst case J = c_max + log1p(sum_e w_e expm1(beta (c_e - c_max))) / beta of
+// the members' costs c_e = loss_e + reg_state_e in place of their weighted mean.  k_ens_tilt forms J and the tilted weights pi_e = dJ/dc_e of
+// one control set; the _risk reduce kernels are k_ens_reduce / k_shape_reduce with pi + g E where those read en.wt, and leave the scalars alone.
+
+#define QOC_TILT_BLOCK 256
+
+// One workgroup per control set, launched after the backward kernels and before the reduce.  The transcendental work (expm1, exp: one each
+// per member) is spread over the threads, members e = tid, tid + 256, ..; the maximum is exact in any order (threads, then an LDS tree); the
+// two sums -- S over w_e expm1(x_e), reg_state over pi_e reg_state_e -- are added by thread 0 alone in the order 0 .. E-1 from member 0's
+// term, out of the terms the threads left in pi[] (S) and of pi[] itself (reg_state): a few thousand dependent adds at most, beside G E
+// trajectories of backward sweeps.  The maximum runs over the members with w_e > 0 (all of them, unless the caller gave a zero weight: such
+// a member has pi_e = 0 and must not set the shift either).  No atomics, no contraction: two evaluations agree bit for bit.  A finished
+// control set of a loop iteration keeps its values and weights.
+__global__ void __launch_bounds__(QOC_TILT_BLOCK) k_ens_tilt(QocDev t, QocDev g, QocEns en, double beta, double* __restrict__ pi_all) {
+#pragma clang fp contract(off)
+    const int gi = blockIdx.x;
+    if (g.skip_done && g.done[gi]) return;
+    const int E = en.E, tid = threadIdx.x;
+    const double* loss = t.loss + (size_t)gi * E;
+    const double* reg = t.reg_state + (size_t)gi * E;
+    double* pi = pi_all + (size_t)gi * E;
+    __shared__ double red[QOC_TILT_BLOCK];
+    __shared__ double bc;
+    double m = -INFINITY;
+    for (int e = tid; e < E; e += QOC_TILT_BLOCK) {
+        const double c = loss[e] + reg[e];
+        if (en.wt[e] > 0.0 && c > m) m = c;                  // (a NaN cost is no maximum, but reaches J through its x_e)
+    }
+    red[tid] = m;
+    __syncthreads();
+    for (int off = QOC_TILT_BLOCK / 2; off > 0; off >>= 1) {
+        if (tid < off) { const double a = red[tid], b = red[tid + off]; red[tid] = b > a ? b : a; }
+        __syncthreads();
+    }
+    const double cmax = red[0];
+    for (int e = tid; e < E; e += QOC_TILT_BLOCK) {
+        const double w = en.wt[e];
+        pi[e] = w > 0.0 ? w * expm1(beta * ((loss[e] + reg[e]) - cmax)) : 0.0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double S = pi[0];
+        for (int e = 1; e < E; ++e) S = S + pi[e];
+        bc = S;
+    }
+    __syncthreads();
+    const double S = bc, den = 1.0 + S;
+    for (int e = tid; e < E; e += QOC_TILT_BLOCK) {
+        const double w = en.wt[e];
+        pi[e] = w > 0.0 ? w * exp(beta * ((loss[e] + reg[e]) - cmax)) / den : 0.0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double r = pi[0] * reg[0];
+        for (int e = 1; e < E; ++e) r = r + pi[e] * reg[e];
+        const double J = cmax + log1p(S) / beta;
+        g.loss[gi] = J - r;
+        g.reg_state[gi] = r;
+    }
+}
+
+// k_ens_reduce with the control set's tilted weights: same grid, same member order from member 0's term; the scalars are k_ens_tilt's.
+__global__ void __launch_bounds__(256) k_ens_reduce_risk(QocDev t, QocDev g, QocEns en, const double* __restrict__ pi_all) {
+#pragma clang fp contract(off)
+    const int gi = blockIdx.y;
+    if (g.skip_done && g.done[gi]) return;
+    const int steps = g.steps, k = g.k, kp = t.k, E = en.E, ks = k * steps;
+    const size_t tstride = (size_t)kp * steps;
+    const double* src = t.dLdu + (size_t)gi * E * tstride;
+    const double* pi = pi_all + (size_t)gi * E;
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o < ks) {
+        const int j = o / steps;
+        double acc = (pi[0] * en.a[j]) * src[o];
+        for (int e = 1; e < E; ++e) acc = acc + (pi[e] * en.a[(size_t)e * k + j]) * src[(size_t)e * tstride + o];
+        g.dLdu[(size_t)gi * ks + o] = acc;
+    }
+}

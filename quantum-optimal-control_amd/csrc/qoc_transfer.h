@@ -110,3 +110,34 @@ __global__ void __launch_bounds__(256) k_shape_reduce(QocDev t, QocDev s, QocEns
         s.reg_state[gi] = r;
     }
 }
+
+// k_shape_reduce with the control set's tilted weights (k_ens_tilt, csrc/qoc_ensemble.h) where that reads en.wt: same grids, same orders of
+// members, slices and lanes; the scalars are k_ens_tilt's.
+template <int LANES>
+__global__ void __launch_bounds__(256) k_shape_reduce_risk(QocDev t, QocDev s, QocEns en, QocShape sh, const double* __restrict__ pi_all) {
+#pragma clang fp contract(off)
+    const int gi = blockIdx.y;
+    if (s.skip_done && s.done[gi]) return;
+    const int steps = t.steps, P = sh.P, k = s.k, kp = t.k, E = en.E, kP = k * P;
+    const size_t tstride = (size_t)kp * steps;
+    QocEns er = en;
+    er.wt = pi_all + (size_t)gi * E;
+    const int o = (int)((blockIdx.x * blockDim.x + threadIdx.x) / LANES), lane = threadIdx.x % LANES;
+    if (o < kP) {                                   // (LANES = 64: uniform over the wave)
+        const int j = o / P, p = o % P;
+        const int2 win = sh.col_win[p];
+        const double* col = sh.Tt + (size_t)p * steps;
+        const double* src = t.dLdu + (size_t)gi * E * tstride + (size_t)j * steps;
+        double acc = 0.0;
+        int tt = win.x + lane;
+        if (tt < win.y) {
+            acc = col[tt] * shape_member_sum(src + tt, er, j, k, tstride);
+            for (tt += LANES; tt < win.y; tt += LANES) acc = acc + col[tt] * shape_member_sum(src + tt, er, j, k, tstride);
+        }
+        if (LANES > 1) {
+#pragma unroll
+            for (int off = LANES / 2; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+        }
+        if (lane == 0) s.dLdu[(size_t)gi * kP + o] = acc;
+    }
+}

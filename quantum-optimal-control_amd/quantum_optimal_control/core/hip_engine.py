@@ -70,6 +70,8 @@ _SIGNATURES = {
     'qoc_get_pulse': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_member_scalars': (C.c_int, [C.c_void_p, _DP, _DP]),
     'qoc_get_member_final_unitary': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_set_risk': (C.c_int, [C.c_void_p, C.c_double]),
+    'qoc_get_member_weights': (C.c_int, [C.c_void_p, _DP]),
     'qoc_destroy': (C.c_int, [C.c_void_p]),
     'qoc_set_base': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_base': (C.c_int, [C.c_void_p, _DP]),
@@ -306,6 +308,7 @@ class HipEngine(object):
     ensemble (robust GRAPE, include/qoc.h qoc_create_ensemble): a dict with keys `operators`, `offsets`, `amp_scales`, `weights` (see
     ensemble_arrays); every control set is then optimised for the weighted objective over the members, and the read-backs keep their
     per-control-set shapes (member 0 for the final unitary and inter_vecs; member_scalars / member_final_unitary give every member).
+    An optional key `risk` (beta > 0) selects the soft worst case over the members in place of their mean (set_risk, member_weights).
 
     transfer (transfer-function GRAPE, include/qoc.h qoc_create_shaped): a real steps x P response matrix.  The variable, the gradient and
     get_uks are then (n_seeds, k, P) -- the AWG's samples --, get_pulse() gives the (n_seeds, k, steps) pulse the trajectories ran on, and the
@@ -405,6 +408,9 @@ class HipEngine(object):
             _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
         if ens is not None:
             self.members = int(ens.members)
+        self.risk = 0.0
+        if ensemble is not None and float(ensemble.get('risk', 0.0)) > 0:
+            self.set_risk(ensemble['risk'])
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
         buf = C.create_string_buffer(512)
@@ -540,6 +546,18 @@ class HipEngine(object):
         reg = np.empty((self.n_seeds, self.members))
         _check(self._lib.qoc_get_member_scalars(self._h, _dp(loss), _dp(reg)))
         return dict(loss=loss, reg_state=reg)
+
+    def set_risk(self, beta):
+        """Ensemble engines: the risk parameter beta >= 0 of the soft worst-case objective (include/qoc.h qoc_set_risk); 0 is the weighted
+        mean.  Holds from the next evaluation, so a caller may anneal it between evaluations or bursts of iterations."""
+        _check(self._lib.qoc_set_risk(self._h, float(beta)))
+        self.risk = float(beta)
+
+    def member_weights(self):
+        """Ensemble engines: the tilted weights pi_e of the last evaluation, [n_seeds][members] (the members' own weights at risk 0)."""
+        out = np.empty((self.n_seeds, max(self.members, 1)))
+        _check(self._lib.qoc_get_member_weights(self._h, _dp(out)))
+        return out
 
     def member_final_unitary(self):
         """Ensemble engines: every member's final unitary of the last evaluation, [n_seeds][members][n][n]."""

@@ -178,8 +178,10 @@ class run_session(object):
         """Robust GRAPE: one line on the members of the reported control set, and their final losses in the run log."""
         self.member_loss = self.engine.member_scalars()['loss'][self.seed]
         worst = int(np.argmax(self.member_loss))
-        print('Robust ensemble: %d members, weighted mean infidelity %.3e, worst member infidelity %.3e (member %d)' % (
-            len(self.member_loss), self.l, self.member_loss[worst], worst))
+        risk = getattr(self.engine, 'risk', 0.0)
+        what = 'soft worst-case (risk %g)' % risk if risk > 0 else 'weighted mean'
+        print('Robust ensemble: %d members, %s infidelity %.3e, worst member infidelity %.3e (member %d)' % (
+            len(self.member_loss), what, self.l, self.member_loss[worst], worst))
         if self.sys_para.save:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(self.sys_para.file_path) as hf:

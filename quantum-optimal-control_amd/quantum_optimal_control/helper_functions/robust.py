@@ -2,7 +2,8 @@
 
 Member e of an ensemble is an ordinary GRAPE problem with the drift H0 + sum_q offsets[e, q] P_q and the control Hamiltonians
 amp_scales[e, j] H_j; all members share U0, the targets, the states of interest, maxA, the regularisers and the one trainable pulse.
-Grape optimises the weighted mean objective over the members (include/qoc.h, qoc_create_ensemble).
+Grape optimises the weighted mean objective over the members (include/qoc.h, qoc_create_ensemble), or, with a `risk` beta > 0, their soft
+worst case  max_e c_e + log1p(sum_e w_e expm1(beta (c_e - max_e c_e))) / beta  (qoc_set_risk): the mean at beta = 0, the worst member as beta grows.
 """
 import itertools
 
@@ -23,10 +24,11 @@ def _rows(values, width, name):
     return np.array(out, dtype=np.float64).reshape(len(out), width)
 
 
-def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=None):
+def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=None, risk=0.0):
     """Cartesian product of offset rows (each q values, one per operator) and amplitude-scale rows (each k values, or a scalar for
     all k controls).  The nominal point (all offsets 0, all scales 1) comes first when the grid contains it; otherwise the
-    product order is kept (offset rows outer).  weights: one per grid point (default uniform), normalised to sum 1.
+    product order is kept (offset rows outer).  weights: one per grid point (default uniform), normalised to sum 1.  risk: beta >= 0 of the
+    soft worst-case objective (0: the weighted mean).
     Returns the dict Grape(robust=...) takes."""
     operators = [np.asarray(p) for p in operators]
     q = len(operators)
@@ -49,19 +51,25 @@ def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=N
     if nominal:
         order = [nominal[0]] + [i for i in order if i != nominal[0]]
     ens = dict(operators=operators, offsets=np.array([pts[i][0] for i in order]).reshape(len(pts), q),
-               amp_scales=np.array([pts[i][1] for i in order]).reshape(len(pts), k), weights=w[order])
+               amp_scales=np.array([pts[i][1] for i in order]).reshape(len(pts), k), weights=w[order], risk=risk)
     return validate(ens, None, k)
 
 
 def validate(robust, n, k):
-    """Checks a robust dict (keys operators, offsets, amp_scales, weights) against a problem of n levels (None: from the operators) and
+    """Checks a robust dict (keys operators, offsets, amp_scales, weights, risk) against a problem of n levels (None: from the operators) and
     k controls and returns it normalised: operators a list of q complex n x n Hermitian matrices, offsets (E, q), amp_scales (E, k)
-    (default ones), weights (E,) summing to 1 (default uniform).  Raises ValueError."""
+    (default ones), weights (E,) summing to 1 (default uniform), risk a finite float >= 0 (default 0.0: the weighted mean).  Raises ValueError."""
     if not isinstance(robust, dict):
-        raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights')
-    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights'}
+        raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights, risk')
+    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk'}
     if unknown:
         raise ValueError('robust: unknown keys %s' % sorted(unknown))
+    try:
+        risk = float(robust.get('risk', 0.0))
+    except (TypeError, ValueError):
+        raise ValueError('robust: risk must be a number >= 0, got %r' % (robust.get('risk'),))
+    if not (np.isfinite(risk) and risk >= 0):
+        raise ValueError('robust: risk must be finite and >= 0, got %r' % risk)
     ops = [np.asarray(p, dtype=np.complex128) for p in robust.get('operators', [])]
     q = len(ops)
     for i, p in enumerate(ops):
@@ -110,7 +118,7 @@ def validate(robust, n, k):
     if not (np.all(np.isfinite(amp)) and (offsets is None or np.all(np.isfinite(offsets)))):
         raise ValueError('robust: offsets and amp_scales must be finite')
     return dict(operators=ops, offsets=np.zeros((E, 0)) if offsets is None else offsets.reshape(E, q), amp_scales=amp,
-                weights=w / w.sum())
+                weights=w / w.sum(), risk=risk)
 
 
 def member_hamiltonians(H0, Hops, robust, e):

@@ -75,7 +75,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``robust`` (robust GRAPE): a dict with keys ``operators`` (q Hermitian n x n matrices P_q), ``offsets`` (E x q), ``amp_scales``
     (E x k, default ones) and ``weights`` (E, default uniform; normalised to sum 1), e.g. from helper_functions.robust.ensemble_grid.
     Member e has the drift H0 + sum_q offsets[e, q] P_q and the controls amp_scales[e, j] Hops[j]; the pulse is optimised for the
-    weighted mean of the members' objectives.  U_final is member 0's.
+    weighted mean of the members' objectives, or, with an optional key ``risk`` (beta > 0), for their soft worst case (DESIGN.md 6b'):
+    the reported loss and the stop rule then read that soft worst-case infidelity.  U_final is member 0's.
 
     ``transfer`` (transfer-function GRAPE): a helper_functions.transfer.Transfer (or a steps x P matrix): the variable is then the k x P
     samples an AWG plays, and the pulse the Hamiltonian sees is their response ``samples @ T.T``.  ``initial_guess`` is k x P sample
@@ -146,6 +147,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                 hf.add('robust_operators', data=np.array(robust['operators']).reshape(q, len(H0), len(H0)))
                 for key in ('offsets', 'amp_scales', 'weights'):
                     hf.add('robust_' + key, data=robust[key])
+                if robust['risk'] > 0:
+                    hf.add('robust_risk', data=np.array([robust['risk']]))
         if transfer is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
