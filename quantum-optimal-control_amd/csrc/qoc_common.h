@@ -135,6 +135,18 @@ static inline const char* qoc_exp_env(const char* name) {
 }
 static inline bool qoc_exp_is(const char* name, int value) { const char* e = qoc_exp_env(name); return e && atoi(e) == value; }
 
+// every one of `count` n x n generators (-i dt H) exactly anti-Hermitian, entry for entry and without a tolerance: what the state-transfer routes
+// need of their adjoint, and what lets k_mfma_expm_inplace mirror a quarter of its Hermitian products (QocMfmaPlan::expm_hermitian)
+static inline bool qoc_all_antihermitian(const cplx* Hs, int n, int count) {
+    for (int q = 0; q < count; ++q) {
+        const cplx* H = Hs + (size_t)q * n * n;
+        for (int a = 0; a < n; ++a)
+            for (int c = a; c < n; ++c)
+                if (H[a * n + c].x != -H[c * n + a].x || H[a * n + c].y != H[c * n + a].y) return false;
+    }
+    return true;
+}
+
 // Size of an engine's work-buffer arena: a multiple of 64 MB.  With the exact size the allocator recycled blocks freed by earlier
 // engines of the process, and where such a block landed decided the speed (n = 128 x 4 after a dozen other engines: 21 ms per
 // iteration instead of 8.3; three of three long sequences back at 8.3-8.6 ms with the rounded size).

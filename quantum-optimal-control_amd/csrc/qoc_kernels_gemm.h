@@ -454,15 +454,7 @@ static inline bool qoc_gemm_direct_supported(const QocDev& d) { return d.state_t
 static inline bool qoc_gemm_supported(const QocDev& d, bool antiherm) {
     return d.m <= QOC_TW && d.T >= 1 && d.T <= QOC_GEMM_MAXT - 1 && (!d.state_transfer || antiherm || qoc_gemm_direct_supported(d));
 }
-static inline bool qoc_all_antihermitian(const cplx* Hs, int n, int count) {
-    for (int q = 0; q < count; ++q) {
-        const cplx* H = Hs + (size_t)q * n * n;
-        for (int a = 0; a < n; ++a)
-            for (int c = a; c < n; ++c)
-                if (H[a * n + c].x != -H[c * n + a].x || H[a * n + c].y != H[c * n + a].y) return false;
-    }
-    return true;
-}
+// (qoc_all_antihermitian: qoc_common.h)
 
 static inline int qoc_gemm_setup(QocGemm& gm, const QocDev& d, const cplx* Hs_host, bool direct, std::vector<void*>& allocs,
     std::string& msg) {

@@ -227,6 +227,10 @@ int qoc_mfma_setup(QocMfma& mf, QocMfmaPlan& plan, const QocDev& d, int chunks_r
     plan.inter_on_readback = lat_own || mf.updown;
     plan.sweeps = mf.latency ? (mf.lat_sources ? "latency_sources" : "latency")
                   : mf.updown ? "downup" : (split_grad ? (mf.grad_rt ? "row_tile_gradient" : "split") : (mf.variant == 1 || NT == 1 || NT == 4 ? "one_wave" : "pair"));
+    // the guard of the symmetric products, once, on every image the exponential kernel assembles from (the perturbation images of an ensemble are
+    // among the d.k + 1; the scaled copy HsD is the same entries times one real factor).  QOC_EXPERIMENTAL=1 QOC_EXPM_HERM=0: the plain Horner chain
+    // (A/B runs), =2: the even/odd chain, whose results differ from the Horner chain's by rounding
+    plan.expm_hermitian = !qoc_all_antihermitian(Hs_host, d.n, d.k + 1) || qoc_exp_is("QOC_EXPM_HERM", 0) ? 0 : (qoc_exp_is("QOC_EXPM_HERM", 2) ? 2 : 1);
     const char* err = qoc_mfma_resolve_expm(plan, mf, d);
     qoc_mfma_resolve_expm_inplace(plan, mf, d);
     qoc_mfma_resolve_forward(plan, mf, d);

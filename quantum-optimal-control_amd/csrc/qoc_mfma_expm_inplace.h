@@ -37,6 +37,7 @@
 #include "qoc_mfma_frag.h"
 
 #define ILDS (16 * NT + 5)        // image row stride (complex elements): conflict-free strip stores and block reads (as chunk4s)
+#define SLDS 21                   // row stride of the 16 x 16 side buffer of the symmetric products (the same residue mod 8: conflict-free strip stores)
 
 #ifndef QOC_INPLACE_PIPE
 #define QOC_INPLACE_PIPE 0        // 1: combine of group ib - 1 after the first block step of group ib (two accumulator sets) instead of at the group
@@ -92,9 +93,20 @@ __device__ __forceinline__ void load_strip(const cplx* img, const double* imgs, 
 // neither the groups that would complete those rows nor the block steps over those inner indices run -- (QA / 8)^2 of the MFMAs of the padded product
 // at NT = 2.  The ring of left blocks is indexed by step & 3, so a product is NSP = NS rounded up to a multiple of 4 steps long: the steps NS .. NSP - 1
 // are virtual (they exist only as positions of the ring; nothing is fetched for them and nothing multiplies).
-template <int NT, int QA, bool RELOAD_IN, bool RELOAD_OUT, bool PLANES, class Init, class Epi>
-__device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<NT>& ring, Set<NT>& P, Init&& init, Epi&& epi) {
+// SYM (NT = 2, QA = 8): the lower left quarter of the result (rows 16 .., columns 0 .. 15: column block J = 0 of the groups ib >= 4) is mirrored from
+// the upper right one through the wave-private side buffer (side[x SLDS + y] = what belongs at row 16 + x, column y), which the groups 0 .. 3 fill
+// from their J = 1 strips with the strip-store pattern and the groups ib >= 4 read in their second block step.
+//   SYM = 1 (P = the image's matrix, exactly anti-Hermitian, no preset): the accumulators a = sum re re and b = sum im im of entry (i, j) and of entry
+//     (j, i) are sums of the SAME products in the SAME order (re[j][k] re[k][i] = (-re[k][j]) (-re[i][k]), im[j][k] im[k][i] = im[k][j] im[i][k]), so a
+//     and b of the quarter are copied, bit for bit what their MFMAs would give; only c = sum (re + im)(re + im) is multiplied there (2 of 3 MFMAs
+//     saved).  The epilogue is the unchanged one.
+//   SYM = 2: the quarter is not multiplied at all; the epilogue of a group ib >= 4 gets the J = 0 strip as `mir`, which the epilogues of the groups
+//     0 .. 3 have written (side_store: conjugated, or what the result's symmetry asks for).  Equal to the multiplied quarter up to rounding only.
+// The mirrored strip then takes the normal path: pending store into the released image rows, read-back as a right operand.
+template <int NT, int QA, bool RELOAD_IN, bool RELOAD_OUT, bool PLANES, int SYM = 0, class Init, class Epi>
+__device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<NT>& ring, Set<NT>& P, Init&& init, Epi&& epi, cplx* side = nullptr) {
     constexpr int QS = QA, NS = QS * QS, NSP = (NS + 3) & ~3, RA = 3;
+    static_assert(!SYM || (NT == 2 && QA == 8 && !RELOAD_IN && !QOC_INPLACE_PIPE && (SYM == 1 || !PLANES)), "symmetric products: the 16-column split of the full 32 x 32 problem");
     static_assert(QA >= 5 && QA <= 4 * NT, "active strips: the stores of a pending strip and the read-backs need five block steps per group");
     const cplx* base = img + (lane >> 4) * ILDS + (lane & 3);
     const double* bases = imgs + (lane >> 4) * ILDS + (lane & 3);
@@ -115,6 +127,10 @@ __device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<
         double (&b)[NT] = acc[ib & 1][1];
         double (&c)[NT] = acc[ib & 1][2];
         constexpr bool preset = decltype(init(ibc, a, c))::value;
+        constexpr bool half = SYM && ib >= 2 * NT;                              // a group whose J = 0 strip is mirrored
+        constexpr int J0 = (SYM == 2 && half) ? 1 : 0;                          // first column block this group multiplies
+        static_assert(SYM != 1 || !preset, "copied accumulators: a preset is not symmetric");
+        cplx mir = cmake(0.0, 0.0);
         init(ibc, a, c);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -136,17 +152,21 @@ __device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<
                 else wbases[16 * (q >> 1) * ILDS + 4 * pib] = ring.psu[q >> 1];
                 fence();
             }
+            if constexpr (half) {
+                if (kb == 1) { fence(); mir = side[(4 * (ib - 2 * NT) + (lane >> 4)) * SLDS + (lane & 15)]; fence(); }     // complete since group 3's epilogue
+            }
             const cplx v = ring.v[st & 3];
             const double vs = ring.s[st & 3];
 #pragma unroll
-            for (int J = 0; J < NT; ++J) {
+            for (int J = J0; J < NT; ++J) {
+                const bool ab = !(SYM == 1 && half && J == 0);       // (else a and b of this strip are copied from the side buffer)
                 if (kb == 0) {
-                    a[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.x, P.re[J][kb], preset ? a[J] : 0.0, 0, 0, 0);
-                    b[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.y, P.im[J][kb], 0.0, 0, 0, 0);
+                    if (ab) a[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.x, P.re[J][kb], preset ? a[J] : 0.0, 0, 0, 0);
+                    if (ab) b[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.y, P.im[J][kb], 0.0, 0, 0, 0);
                     c[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(vs, P.su[J][kb], preset ? c[J] : 0.0, 0, 0, 0);
                 } else {
-                    a[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.x, P.re[J][kb], a[J], 0, 0, 0);
-                    b[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.y, P.im[J][kb], b[J], 0, 0, 0);
+                    if (ab) a[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.x, P.re[J][kb], a[J], 0, 0, 0);
+                    if (ab) b[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(v.y, P.im[J][kb], b[J], 0, 0, 0);
                     c[J] = __builtin_amdgcn_mfma_f64_4x4x4f64(vs, P.su[J][kb], c[J], 0, 0, 0);
                 }
             }
@@ -179,13 +199,18 @@ __device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<
         // the group's VALU batch stays a batch: a lone wave's VALU instructions cost MFMA issue slots wherever they stand, least in a group
         if constexpr (!QOC_INPLACE_PIPE || ib == QS - 1) {
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (SYM == 1) {
+                if constexpr (half) { a[0] = mir.x; b[0] = mir.y; }
+                else { fence(); side[(lane & 15) * SLDS + 4 * ib + (lane >> 4)] = cmake(a[1], b[1]); fence(); }      // a[j][i] = a[i][j], b likewise
+            }
             if constexpr (PLANES) {
                 epi(ibc, a, b, c, ring.ppl[0], ring.ppl[1], ring.ppl[2]);
                 if constexpr (ib == QS - 1) {                           // the next product stores pairs
 #pragma unroll
                     for (int J = 0; J < NT; ++J) { ring.pri[J] = cmake(ring.ppl[0][J], ring.ppl[1][J]); ring.psu[J] = ring.ppl[2][J]; }
                 }
-            } else epi(ibc, a, b, c, ring.pri, ring.psu);
+            } else if constexpr (SYM == 2) epi(ibc, a, b, c, ring.pri, ring.psu, mir);
+            else epi(ibc, a, b, c, ring.pri, ring.psu);
             __builtin_amdgcn_sched_barrier(0);
         }
     }, std::make_integer_sequence<int, QS>{});
@@ -204,12 +229,28 @@ __device__ __forceinline__ cplx* frag_at(cplx* F, int f) { return F + (f & ~3) *
 // squaring (the last Horner product completes K_t and stores it: a run-time test there splits every Horner product into a basic block per group)
 // QA = active 4-row strips, ceil(n / 4) (see product()): the strips QA .. 7 of K_t are never written (the buffer is cleared once at set-up: zero rows
 // and columns, which is what the sweeps need of a padded propagator), those of the chunk product keep the identity they start from.
-template <int KC, bool EVEN, bool S0, int QA = 8>
+// HERM (QA = 8, Taylor order 5; the host certifies that every Hamiltonian image is exactly anti-Hermitian, so S_t is):
+// HERM = 1: the Horner chain as it is, with the first product S S taken as product<SYM = 1>: 64 of its 384 MFMAs are copies.  Every output bit is
+//   what HERM = 0 computes.  The default where the guard holds.
+// HERM = 2 (QOC_EXPERIMENTAL=1 QOC_EXPM_HERM=2): the polynomial is cut into its even
+// and odd part, p(S) = E(S^2) + S O(S^2), O = S^4 + o1 S^2 + o0 I, E = e2 S^4 + e1 S^2 + e0 I, and taken as three SYMMETRIC products (product<SYM = 2>: the
+// lower left quarter is mirrored, 288 of a padded product's 384 MFMAs each) instead of S S and two Horner products between general matrices -- the
+// same polynomial, other roundings (1e-14 of the entries), which an optimiser loop amplifies like any other perturbation:
+//   P1  S2 = S S               Hermitian                -> image and SB (the mirror: conjugate)
+//   P2  Q  = S2 S2 + o1 S2 = O - o0 I   Hermitian       -> image         (o1 S2 through the accumulators' initial values, from SB)
+//   P3  K0 = Q S + (o0 S + E)  anti-Hermitian + Hermitian -> image, read back into SA for the squarings (the mirror: conjugate of 2 E - K0);
+//       E = e0 I + (e1 - e2 o1) S2 + e2 Q is never stored (o0 I stays out of Q: e2 o0 - e2 o0 on the diagonal would cost E five times the rounding
+//       error of its value 1): strip ib of S2 is in SB, strip ib of Q is read from the image rows group ib
+//       has not released yet, one group ahead, and E enters through the accumulators' initial values.
+// The squarings then run on SA (S is dead after P3; SB stays free for the chunk product), everything behind them is unchanged.
+template <int KC, bool EVEN, bool S0, int QA = 8, int HERM = 0>
 __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma mf) {
     using namespace qoc_inplace;
     constexpr int NT = 2, QS = 4 * NT;
+    static_assert(!HERM || (QA == 8 && !QOC_INPLACE_SWAP && (HERM == 1 || !EVEN)), "symmetric products: the full 32 x 32 problem; even/odd chain: Taylor order 5");
     __shared__ __attribute__((aligned(16))) cplx img[QNP * ILDS];
     __shared__ __attribute__((aligned(16))) double imgs[QNP * ILDS];
+    __shared__ __attribute__((aligned(16))) cplx side[HERM ? 16 * SLDS : 1];         // (referenced by the HERM instances only)
     const int lane = threadIdx.x;
     const unsigned ulane = threadIdx.x;
     const int b = blockIdx.x / mf.C, c = blockIdx.x - b * mf.C;
@@ -291,9 +332,90 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
 
     auto slice = [&](Set<NT>& SB, Set<NT>& R, int t) __attribute__((always_inline)) {
         cplx* Kout = mf.KfD + kitem(mf, d.steps, b, t);
+        Set<NT>& SQ = *(HERM == 2 ? &SA : &SB);               // the squarings' right operand
+        if constexpr (HERM == 2) {
+        const double o0 = mf.pcoef[1], o1 = mf.pcoef[3], e2 = mf.pcoef[4], e0 = mf.pcoef[0], g1 = mf.pcoef[2] - e2 * o1;
+        // mirror source of strip (1, ib), ib < 4: lane (row r, column c) holds the entry (4 ib + r, 16 + c), whose mirror image is (16 + c, 4 ib + r)
+        auto side_store = [&](int ib, double re, double im) { fence(); side[(lane & 15) * SLDS + 4 * ib + (lane >> 4)] = cmake(re, im); fence(); };
+        // ---- P1: S2 = S * S -> image (left operand of P2) and SB (its right operand) ----------------------------------------------------------
+        product<NT, QA, false, false, false, 2>(img, imgs, lane, ring, SA, no_init,
+                                        [&](auto ibc, double (&a)[NT], double (&bq)[NT], double (&cq)[NT], cplx (&ori)[NT], double (&osu)[NT], const cplx& mir) {
+            constexpr int ib = decltype(ibc)::value;
+#pragma unroll
+            for (int J = 0; J < NT; ++J) {
+                double re, im, su;
+                if (ib >= 2 * NT && J == 0) { re = mir.x; im = mir.y; su = re + im; }
+                else combine(a[J], bq[J], cq[J], re, im, su);
+                SB.re[J][ib] = re; SB.im[J][ib] = im; SB.su[J][ib] = su;
+                ori[J] = cmake(re, im); osu[J] = su;
+                if (ib < 2 * NT && J == 1) side_store(ib, re, -im);
+            }
+        }, side);
+        QOC_LAP(1)
+        // ---- P2: Q = S2 * S2 + o1 S2 (= O - o0 I) -> image in place ----------------------------------------------------------------------------------
+        product<NT, QA, false, false, false, 2>(img, imgs, lane, ring, SB,
+                                        [&](auto ibc, double (&a)[NT], double (&cq)[NT]) {
+            constexpr int ib = decltype(ibc)::value;
+#pragma unroll
+            for (int J = ib >= 2 * NT ? 1 : 0; J < NT; ++J) {
+                a[J] = o1 * SB.re[J][ib];
+                cq[J] = o1 * SB.su[J][ib];
+            }
+            return std::true_type{};
+        },
+                                        [&](auto ibc, double (&a)[NT], double (&bq)[NT], double (&cq)[NT], cplx (&ori)[NT], double (&osu)[NT], const cplx& mir) {
+            constexpr int ib = decltype(ibc)::value;
+#pragma unroll
+            for (int J = 0; J < NT; ++J) {
+                double re, im, su;
+                if (ib >= 2 * NT && J == 0) { re = mir.x; im = mir.y; su = re + im; }
+                else combine(a[J], bq[J], cq[J], re, im, su);
+                ori[J] = cmake(re, im); osu[J] = su;
+                if (ib < 2 * NT && J == 1) side_store(ib, re, -im);
+            }
+        }, side);
+        // ---- P3: K0 = Q * S + (o0 S + E) -> image in place (the squarings' operand, or K_t itself) ---------------------------------------------------------
+        double Or[2][NT], Os[2][NT], Er = 0.0, Es = 0.0;              // strips of O (re, re + im), one group ahead; E of the strip whose mirror is due
+        auto load_o = [&](int ib, double (&r)[NT], double (&su)[NT]) {
+            fence();
+#pragma unroll
+            for (int J = ib >= 2 * NT ? 1 : 0; J < NT; ++J) {
+                const int o = (16 * J + (lane & 15)) * ILDS + 4 * ib + (lane >> 4);
+                r[J] = ((const double*)(img + o))[0]; su[J] = imgs[o];
+            }
+            fence();
+        };
+        load_o(0, Or[0], Os[0]);
+        product<NT, QA, false, !S0, false, 2>(img, imgs, lane, ring, SA,
+                                        [&](auto ibc, double (&a)[NT], double (&cq)[NT]) {
+            constexpr int ib = decltype(ibc)::value;
+#pragma unroll
+            for (int J = ib >= 2 * NT ? 1 : 0; J < NT; ++J) {
+                double er = fma(e2, Or[ib & 1][J], g1 * SB.re[J][ib]), es = fma(e2, Os[ib & 1][J], g1 * SB.su[J][ib]);
+                if ((ib >> 2) == J) { er = fma(e0, diag(J, ib), er); es = fma(e0, diag(J, ib), es); }
+                a[J] = fma(o0, SA.re[J][ib], er); cq[J] = fma(o0, SA.su[J][ib], es);          // + o0 S: the anti-Hermitian part with Q S
+                if (ib < 2 * NT && J == 1) { Er = er; Es = es; }
+            }
+            if constexpr (ib + 1 < QA) load_o(ib + 1, Or[(ib + 1) & 1], Os[(ib + 1) & 1]);     // rows 4 (ib + 1) .. still hold O
+            return std::true_type{};
+        },
+                                        [&](auto ibc, double (&a)[NT], double (&bq)[NT], double (&cq)[NT], cplx (&ori)[NT], double (&osu)[NT], const cplx& mir) {
+            constexpr int ib = decltype(ibc)::value;
+#pragma unroll
+            for (int J = 0; J < NT; ++J) {
+                double re, im, su;
+                if (ib >= 2 * NT && J == 0) { re = mir.x; im = mir.y; su = re + im; }
+                else combine(a[J], bq[J], cq[J], re, im, su);
+                ori[J] = cmake(re, im); osu[J] = su;
+                if constexpr (S0) frag_at(Kout, J * QS + ib)[((J * QS + ib) & 3) * 64 + ulane] = ori[J];
+                if (ib < 2 * NT && J == 1) side_store(ib, fma(2.0, Er, -re), fma(-2.0, Es - Er, im));      // conjugate of 2 E - K0
+            }
+        }, side);
+        QOC_LAP(2)
+        } else {
         // ---- S2 = S * S -> SB;  Horner start X = S + c0 I (odd order: the strips of S with a shifted diagonal -- planes, no pairing) or
         //      S2 + c1 S + c0 I (even order) -> image (left operand of the first Horner product) ---------------------------------------------
-        product<NT, QA, false, false, true>(img, imgs, lane, ring, SA, no_init,
+        product<NT, QA, false, false, true, HERM == 1 ? 1 : 0>(img, imgs, lane, ring, SA, no_init,
                                         [&](auto ibc, double (&a)[NT], double (&bq)[NT], double (&cq)[NT], double (&ore)[NT], double (&oim)[NT], double (&osu)[NT]) {
             constexpr int ib = decltype(ibc)::value;
 #pragma unroll
@@ -311,7 +433,7 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
                     ore[J] = SA.re[J][ib]; oim[J] = SA.im[J][ib]; osu[J] = SA.su[J][ib];
                 }
             }
-        });
+        }, HERM == 1 ? side : nullptr);
         QOC_LAP(1)
         // ---- Horner over A2 with the factors commuted: X <- X * A2 + (d0 I + d1 A); the last one is followed by a product that takes its
         //      right operand from the image (squaring) or needs none (s = 0: the result is K_t) ------------------------------------------------
@@ -340,10 +462,11 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
             else product<NT, QA, false, true, false>(img, imgs, lane, ring, SB, init, epi);
         }
         QOC_LAP(2)
-        // ---- squarings: X <- X * X; the right operand is read back from the image into SB strip by strip ---------------------------------
+        }
+        // ---- squarings: X <- X * X; the right operand is read back from the image into SB (HERM: SA) strip by strip ------------------------
         for (int sq = 0; sq < d.s; ++sq) {
             const bool kout = sq == d.s - 1;
-            product<NT, QA, true, true, false>(img, imgs, lane, ring, SB, no_init,
+            product<NT, QA, true, true, false>(img, imgs, lane, ring, SQ, no_init,
                                     [&](auto ibc, double (&a)[NT], double (&bq)[NT], double (&cq)[NT], cplx (&ori)[NT], double (&osu)[NT]) {
                 constexpr int ib = decltype(ibc)::value;
 #pragma unroll

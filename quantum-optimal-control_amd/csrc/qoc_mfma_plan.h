@@ -70,5 +70,8 @@ struct QocMfmaPlan {
     bool inter_on_readback = false;    // inter_vecs too (qoc_mfma_unpack_inter)
     const char* sweeps = "";           // qoc_plan_describe: sweeps=<word> expm=<number>
     int expm_variant = 1;
+    int expm_hermitian = 0;            // in: 0, or with every Hamiltonian image exactly anti-Hermitian (qoc_mfma_setup) 1 / 2 (QOC_EXPM_HERM=2); out: what
+                                       // k_mfma_expm_inplace runs (qoc_mfma_resolve_expm_inplace) -- 1: S S with copied accumulators, bit-identical to 0;
+                                       // 2: the even/odd chain of symmetric products; qoc_plan_describe: expm_hermitian=<0|1|2>
     const char* expm_name = "";        // qoc_profile_read
 };

@@ -15,6 +15,7 @@
 #include <dlfcn.h>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <set>
 #include <string>
@@ -99,7 +100,7 @@ hipError_t qoc_trace_launch(const void* kernel, dim3 grid, dim3 block, size_t ld
 }
 
 struct Problem { int n, k, m, degree, s, st, reg, variant, chunks, B, Bplan, steps; const char* sw; int sw_value; };
-static const char* const SWITCHES[] = {"QOC_UPDOWN", "QOC_GRAD_RT", "QOC_ROWS_QA_FULL", "QOC_LAT_QA8", "QOC_LAT_OFFSETS_IN_SWEEP"};
+static const char* const SWITCHES[] = {"QOC_UPDOWN", "QOC_GRAD_RT", "QOC_ROWS_QA_FULL", "QOC_LAT_QA8", "QOC_LAT_OFFSETS_IN_SWEEP", "QOC_EXPM_HERM"};
 
 static void mf_digest(const QocMfma& mf) {
     line(true, "  mf C=%d L=%d mq=%d NT=%d FR=%d G=%d NG=%d variant=%d store_T=%d updown=%d grad_rt=%d h_in_lds=%d latency=%d lat_sources=%d lat_src_fast=%d lat_dressed=%d "
@@ -114,7 +115,19 @@ static void mf_digest(const QocMfma& mf) {
 }
 
 // -1: not a problem of the MFMA path, else 0
-static int run(const Problem& q, const std::vector<cplx>& Hs) {
+static int run(const Problem& q, const std::vector<cplx>& Hs_table) {
+    // the problems of the QOC_EXPM_HERM switch get exactly anti-Hermitian images (the table's are not: its other problems never pass the guard of the
+    // symmetric exponential products, qoc_all_antihermitian), so that both values of the plan's expm_hermitian axis are traced
+    std::vector<cplx> Hs(Hs_table);
+    if (q.sw && !strcmp(q.sw, "QOC_EXPM_HERM"))
+        for (int i = 0; i <= q.k; ++i)
+            for (int a = 0; a < q.n; ++a)
+                for (int c = 0; c <= a; ++c) {
+                    cplx& lo = Hs[((size_t)i * q.n + a) * q.n + c];
+                    cplx& up = Hs[((size_t)i * q.n + c) * q.n + a];
+                    if (a == c) lo.x = 0.0;
+                    up.x = -lo.x; up.y = lo.y;
+                }
     QocDev d{};
     d.n = q.n; d.k = q.k; d.steps = q.steps; d.m = q.m; d.state_transfer = q.st;
     d.T = q.st ? q.degree + 1 : q.degree;                       // (the caller's taylor_terms)
@@ -145,6 +158,9 @@ static int run(const Problem& q, const std::vector<cplx>& Hs) {
     g_in_setup = false;
     if (q.sw) { unsetenv(q.sw); unsetenv("QOC_EXPERIMENTAL"); }
     line(true, "  setup rc=%d %s", rc, msg.c_str());
+#if __has_include("qoc_mfma_plan.h")
+    if (rc == 0 && plan.expm_variant == 8) line(true, "  expm_hermitian=%d", plan.expm_hermitian);
+#endif
     if (rc == 0) {
         mf_digest(mf);
         const bool lat_own = mf.latency && (!mf.lat_sources || mf.lat_src_fast);
