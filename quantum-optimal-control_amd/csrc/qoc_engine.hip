@@ -293,7 +293,7 @@ static int enqueue_small(qoc_engine* e, const QocAdamDev& ap, int iters) {
 }
 
 // Which kernel runs the tail of an iteration (regularisers, chain rule, stop rule, Adam; qoc_kernels_finish.h): a function of the engine alone,
-// used by enqueue_iteration to launch it, by qoc_create for gm.reduce_in_tail and by qoc_plan_describe to report it
+// used by enqueue_iteration to launch it (and to tell qoc_gemm_backward who sums its gradient partials) and by qoc_plan_describe to report it
 enum TailKind {
     TAIL_IN_LAUNCH,          // workgroup-resident path: inside its own launch
     TAIL_LATENCY_FUSED,      // MFMA latency mode without bandpass: the last-arriving workgroup of a seed in k_mfma_grad_lat* (64 (16 / NT) NT threads)
@@ -313,7 +313,7 @@ static TailKind tail_kind(const qoc_engine* e) {
     if (e->path == QOC_PATH_MFMA && e->mp.tail_fusable && !d.has_band && !(e->skip_mask & (16 | 32)))
         return TAIL_LATENCY_FUSED;
     if (ks > 4 * 1024 && e->fin_part)
-        return e->path == QOC_PATH_GEMM && e->gm.persistent && e->skip_mask == 0 ? TAIL_SPLIT_PARTIALS : TAIL_SPLIT;
+        return e->path == QOC_PATH_GEMM && qoc_gemm_chain_routes(e->gm) && e->skip_mask == 0 ? TAIL_SPLIT_PARTIALS : TAIL_SPLIT;
     return ks <= 8 * 1024 && ks > 4 * 1024 ? TAIL_FINISH8 : TAIL_FINISH4;
 }
 
@@ -336,8 +336,9 @@ static void enqueue_controls(const qoc_engine* e, const QocDev& d, const QocDev&
     }
 }
 // 2. trajectories: exponentials, forward, loss, backward of the engine's path; qoc_profile_read's hipEvent bracket around the dominant one
-static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev& ap, bool fused_tail) {
+static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev& ap, TailKind tail) {
     const int skip = e->skip_mask;
+    const bool fused_tail = tail == TAIL_LATENCY_FUSED;
     if (e->path == QOC_PATH_MFMA) {
         TRY(prof_begin(e));
         if (!(skip & 2)) qoc_mfma_launch_expm(e->mp, e->mf, d, e->stream);
@@ -359,14 +360,14 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
     } else if (e->path == QOC_PATH_GEMM) {
         // the bracket: the exponentials -- or, on the direct state-transfer route (no exponentials: the assembly of the generators is all
         // qoc_gemm_expm does there), the backward half of the iteration, which the backward Taylor chain dominates
-        const bool bracket_bwd = e->gm.direct;
+        const bool bracket_bwd = e->gm.route == QOC_GEMM_DIRECT;
         if (!bracket_bwd) TRY(prof_begin(e));
         qoc_gemm_expm(e->gm, d, e->stream);
         if (!bracket_bwd) TRY(prof_end(e));
         qoc_gemm_forward(e->gm, d, e->stream);
         launch_loss(d, e->stream);
         if (bracket_bwd) TRY(prof_begin(e));
-        qoc_gemm_backward(e->gm, d, e->stream);
+        qoc_gemm_backward(e->gm, d, e->stream, tail == TAIL_SPLIT_PARTIALS);       // (the split tail sums the gradient partials: one launch less)
         if (bracket_bwd) TRY(prof_end(e));
     } else if (e->path == QOC_PATH_LINDBLAD) {                          // open system: forward, backward, reduce (csrc/qoc_lindblad.h)
         TRY(prof_begin(e));
@@ -462,7 +463,7 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     gd.skip_done = d.skip_done;
     const bool fused_tail = tail == TAIL_LATENCY_FUSED;
     enqueue_controls(e, d, gd, own_controls, swap_in);
-    TRY(enqueue_trajectories(e, d, ap, fused_tail));
+    TRY(enqueue_trajectories(e, d, ap, tail));
     if (e->ens_E && !(skip & 32)) enqueue_ens_reduce(e, d, gd);
     if (!fused_tail && !(skip & 32)) enqueue_tail(e, e->ens_E ? gd : d, ap, tail);
     HIP_TRY(hipGetLastError());
@@ -931,8 +932,6 @@ static int setup_path(qoc_engine* e, const double* Hs, bool antiherm, const Auto
         if (rc) return fail(rc, "qoc_create: %s", msg.c_str());
         if (!qoc_gemm_lds_opt_in()) return fail(QOC_ERR_HIP, "qoc_create: cannot reserve LDS for the GEMM-path kernels");
         e->chunks = e->gm.NC;
-        // the split tail sums the gradient partials: one launch less (an ensemble reduces the members' gradients first)
-        e->gm.reduce_in_tail = !e->ens_E && tail_kind(e) == TAIL_SPLIT_PARTIALS;
         if (e->gm.ts_G > 0) {
             std::string why;
             if (!qoc_gemm_ts_supported(e->gm, d, e->gm.ts_G, why))
@@ -1593,7 +1592,7 @@ int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, 
     TRY(prof_collect(e));
     if (kernel_name)
         *kernel_name = e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
-                       : e->path == QOC_PATH_GEMM ? (e->gm.direct ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
+                       : e->path == QOC_PATH_GEMM ? (e->gm.route == QOC_GEMM_DIRECT ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
                            : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
                        : e->path == QOC_PATH_MFMA ? e->mp.expm_name             // (the kernel of the exponentials, by its variant)
                        : e->path == QOC_PATH_ST_FUSED ? "k_st_fwd_fused" : (e->d.state_transfer ? "k_st_fwd_generic" : "k_expm_generic");
@@ -1635,16 +1634,16 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
         if (e->mp.expm_variant == 8) snprintf(tmp + w, sizeof tmp - w, " expm_hermitian=%d", e->mp.expm_hermitian);
     } else if (e->path == QOC_PATH_GEMM) {
         const QocGemm& g = e->gm;
+        const bool direct = g.route == QOC_GEMM_DIRECT;
         int w = snprintf(tmp, sizeof tmp, "path=gemm route=%s chunks=%d slices_per_chunk=%d chains=%s",
-            g.direct ? "direct" : (e->d.state_transfer ? "propagator" : "unitary"),
-                         g.NC, g.S, g.persistent ? "persistent" : "launches");
+                         direct ? "direct" : (e->d.state_transfer ? "propagator" : "unitary"), g.NC, g.S, qoc_gemm_chain_routes(g) ? "persistent" : "launches");
         if (g.ts_G > 0) w += snprintf(tmp + w, sizeof tmp - w, " time_shards=%d time_rank=%d", g.ts_G, g.ts_rank);
         // the kernel of the direct route's Taylor chains: squared (k_gemm_taylor_chain_sq on [B | B^2]), packed / full
         // (k_gemm_taylor_chain_dpp), butterfly (k_gemm_taylor_chain)
-        if (g.direct) snprintf(tmp + w, sizeof tmp - w, " taylor_chain=%s",
-            g.sq_chain ? "squared" : g.dpp_packed ? "packed"
-            : g.dpp_chain ? (g.dpp_cw == 10 ? "columns40" : g.dpp_cw == 12 ? "columns48" : g.dpp_cw == 14 ? "columns56" : "full")
-                : "butterfly");
+        if (direct) snprintf(tmp + w, sizeof tmp - w, " taylor_chain=%s",
+                             g.sq_chain ? "squared" : g.dpp_packed ? "packed"
+                             : g.dpp_chain ? (g.dpp_cw == 10 ? "columns40" : g.dpp_cw == 12 ? "columns48" : g.dpp_cw == 14 ? "columns56" : "full")
+                             : "butterfly");
     } else if (e->path == QOC_PATH_LINDBLAD) {
         snprintf(tmp, sizeof tmp, "path=lindblad collapse=%d pairs=%d lds=%zu", e->lb.c, e->lb.R, e->lb.lds_bytes);
     } else if (e->path == QOC_PATH_SMALL) {

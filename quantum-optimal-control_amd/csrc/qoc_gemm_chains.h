@@ -341,62 +341,6 @@ __global__ void __launch_bounds__((TaylorMap<N, MV>::type::THREADS)) k_gemm_tayl
 #include "qoc_gemm_chain_dpp.h"     // k_gemm_taylor_chain_dpp: N = 64, one vector, generators column-major
 #include "qoc_gemm_chain_sq.h"      // k_gemm_taylor_chain_sq: the same chain on [B | B^2], 1 + ceil(T/2) - 1 dependent mat-vecs per slice
 
-template <int N>
-static inline void qoc_taylor_chain_launch_n(const ChainArgs& a0, const ChainArgs& a1, int nb0, int blocks, hipStream_t s) {
-    const int mv = a0.m <= 1 ? 1 : (a0.m <= 2 ? 2 : (a0.m <= 4 ? 4 : 8));
-    if (mv == 1) hipLaunchKernelGGL((k_gemm_taylor_chain<N, 1>), dim3(blocks), dim3(TaylorMap<N, 1>::type::THREADS), 0, s, a0, a1, nb0);
-    else if (mv == 2) hipLaunchKernelGGL((k_gemm_taylor_chain<N, 2>), dim3(blocks), dim3(TaylorMap<N, 2>::type::THREADS), 0, s, a0, a1, nb0);
-    else if (mv == 4) hipLaunchKernelGGL((k_gemm_taylor_chain<N, 4>), dim3(blocks), dim3(TaylorMap<N, 4>::type::THREADS), 0, s, a0, a1, nb0);
-    else hipLaunchKernelGGL((k_gemm_taylor_chain<N, 8>), dim3(blocks), dim3(TaylorMap<N, 8>::type::THREADS), 0, s, a0, a1, nb0);
-}
-// dpp: 0 = k_gemm_taylor_chain, 1 = k_gemm_taylor_chain_dpp on full generators, 2 = on packed anti-Hermitian generators (qoc_gemm_chain_dpp.h),
-//      3 = k_gemm_taylor_chain_sq on packed [B | B^2] (qoc_gemm_chain_sq.h), 10 / 12 / 14 = k_gemm_taylor_chain_dpp on the first 4 x 10 / 12 / 14
-//      columns of full generators (padded problems of at most 40 / 48 / 56 levels)
-static inline void qoc_taylor_chain_launch(int N, ChainArgs a, const cplx* zeros, int blocks, hipStream_t s, int dpp = 0) {
-    if (!a.E) { a.E = zeros; a.sEb = a.sEc = a.sEs = 0; }
-    if (dpp == 10) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 10>), dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (dpp == 12) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 12>), dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (dpp == 14) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 14>), dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (dpp == 3) { hipLaunchKernelGGL(k_gemm_taylor_chain_sq, dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (dpp == 2) { hipLaunchKernelGGL(k_gemm_taylor_chain_dpp<true>, dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (dpp) { hipLaunchKernelGGL(k_gemm_taylor_chain_dpp<false>, dim3(blocks), dim3(256), 0, s, a, a, blocks); return; }
-    if (N == 32) qoc_taylor_chain_launch_n<32>(a, a, blocks, blocks, s); else qoc_taylor_chain_launch_n<64>(a, a, blocks, blocks, s);
-}
-// two chains side by side: `blocks` workgroups each
-static inline void qoc_taylor_chain_launch2(int N, ChainArgs a0, ChainArgs a1, const cplx* zeros, int blocks, hipStream_t s, int dpp = 0) {
-    if (!a0.E) { a0.E = zeros; a0.sEb = a0.sEc = a0.sEs = 0; }
-    if (!a1.E) { a1.E = zeros; a1.sEb = a1.sEc = a1.sEs = 0; }
-    if (dpp == 10) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 10>), dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (dpp == 12) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 12>), dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (dpp == 14) { hipLaunchKernelGGL((k_gemm_taylor_chain_dpp<false, 14>), dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (dpp == 3) { hipLaunchKernelGGL(k_gemm_taylor_chain_sq, dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (dpp == 2) { hipLaunchKernelGGL(k_gemm_taylor_chain_dpp<true>, dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (dpp) { hipLaunchKernelGGL(k_gemm_taylor_chain_dpp<false>, dim3(2 * blocks), dim3(256), 0, s, a0, a1, blocks); return; }
-    if (N == 32) qoc_taylor_chain_launch_n<32>(a0, a1, blocks, 2 * blocks, s); else qoc_taylor_chain_launch_n<64>(a0, a1, blocks, 2 * blocks, s);
-}
-
-template <int N, bool CONJ, bool HAS_OUT>
-static inline void qoc_chain_fwd_launch_n(const ChainArgs& a, int blocks, hipStream_t s) {
-    const int mv = a.m <= 1 ? 1 : (a.m <= 2 ? 2 : (a.m <= 4 ? 4 : 8));
-    if (mv == 1) hipLaunchKernelGGL((k_gemm_chain_fwd<N, 1, CONJ, HAS_OUT>), dim3(blocks), dim3(256), 0, s, a);
-    else if (mv == 2) hipLaunchKernelGGL((k_gemm_chain_fwd<N, 2, CONJ, HAS_OUT>), dim3(blocks), dim3(256), 0, s, a);
-    else if (mv == 4) hipLaunchKernelGGL((k_gemm_chain_fwd<N, 4, CONJ, HAS_OUT>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_gemm_chain_fwd<N, 8, CONJ, HAS_OUT>), dim3(blocks), dim3(256), 0, s, a);
-}
-// conj = true: y <- conj(M_j) y, used with M_j = K_j^T for the backward chains (K_j^H = conj(K_j^T): the rows of the transposed
-// copy are read with the same coalesced pattern as the forward chains)
-template <int N>
-static inline void qoc_chain_launch_c(bool conj, const ChainArgs& a, int blocks, hipStream_t s) {
-    if (conj) { if (a.Out) qoc_chain_fwd_launch_n<N, true, true>(a, blocks, s); else qoc_chain_fwd_launch_n<N, true, false>(a, blocks, s); }
-    else { if (a.Out) qoc_chain_fwd_launch_n<N, false, true>(a, blocks, s); else qoc_chain_fwd_launch_n<N, false, false>(a, blocks, s); }
-}
-// `zeros` = a zero thin buffer (N x 32) used as the addend when the chain has none
-static inline void qoc_chain_launch(int N, bool conjt, ChainArgs a, const cplx* zeros, int blocks, hipStream_t s) {
-    if (a.len <= 0 && !a.Fin && !a.store_initial) return;
-    if (!a.E) { a.E = zeros; a.sEb = a.sEc = a.sEs = 0; }
-    if (N == 32) qoc_chain_launch_c<32>(conjt, a, blocks, s); else qoc_chain_launch_c<64>(conjt, a, blocks, s);
-}
-
 // ---- chunk-boundary vectors in log depth ----------------------------------------------------------------------------
 // The boundary chains (Psibnd[c+1] = P_c Psibnd[c], Ebnd[c-1] = P_c^H Ebnd[c]) were NC - 1 dependent steps in one workgroup
 // per seed.  The pairwise product tree above the chunk products already exists (unitary mode needs its root for
@@ -495,10 +439,4 @@ __global__ void __launch_bounds__(256) k_gemm_scan_nodes(ScanArgs a) {
     cplx* out = a.Out + (size_t)b * a.sOb + (size_t)c * a.sOc;
     const cplx* xc = xv + cur * N * 8;
     for (int e = tid; e < N * QOC_TW; e += 256) out[e] = (e & (QOC_TW - 1)) < 8 ? xc[(e / QOC_TW) * 8 + (e & (QOC_TW - 1))] : cmake(0.0, 0.0);
-}
-static inline size_t qoc_scan_lds(int N) { return ((size_t)N * (N + 1) + 2 * (size_t)N * 8) * sizeof(cplx); }
-static inline void qoc_scan_launch(int N, const ScanArgs& a, int B, hipStream_t s) {
-    if (a.nchains <= 0) return;
-    if (N == 32) hipLaunchKernelGGL(k_gemm_scan_nodes<32>, dim3(B * a.nchains), dim3(256), qoc_scan_lds(32), s, a);
-    else hipLaunchKernelGGL(k_gemm_scan_nodes<64>, dim3(B * a.nchains), dim3(256), qoc_scan_lds(64), s, a);
 }

@@ -90,8 +90,8 @@ static inline int qoc_gemm_ts_gather_inter(QocGemm& gm, const QocDev& d, hipStre
 static inline bool qoc_gemm_ts_supported(const QocGemm& gm, const QocDev& d, int G, std::string& why) {
     if (d.state_transfer) { why = "unitary mode only"; return false; }
     if (d.B != 1) { why = "one control set (restart batches shard over seeds: parallel_seeds)"; return false; }
-    if (d.n_forb > 0 || d.has_speed) { why = "no state regulariser (the affine costate needs a second exchange)"; return false; }
-    if (gm.persistent || gm.direct || gm.wideW <= 0) { why = "N >= 128 with an even number of 32-row tiles and m <= 8 (the GEMM path's large-matrix route)"; return false; }
+    if (qoc_has_state_sources(d)) { why = "no state regulariser (the affine costate needs a second exchange)"; return false; }
+    if (qoc_gemm_chain_routes(gm) || gm.wideW <= 0) { why = "N >= 128 with an even number of 32-row tiles and m <= 8 (the GEMM path's large-matrix route)"; return false; }
     if (G < 1 || G > gm.NC) { why = "1 <= time_shards <= number of chunks"; return false; }
     return true;
 }
@@ -115,9 +115,7 @@ static inline void qoc_gemm_ts_expm(QocGemm& gm, const QocDev& d, int r, hipStre
         hipLaunchKernelGGL(k_ts_copy, dim3(gemm_grid(NN)), dim3(256), 0, s, out, Pc + (size_t)c0 * NN, NN);
         return;
     }
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.lda = g.ldb = g.ldc = N; g.Kdim = N; g.tiles_m = g.tiles_n = N / 32; g.batch = 1; g.alpha = 1.0;
+    GemmArgs g = qoc_gemm_square_args(N, 1);
     const cplx* cur = Pc + (size_t)c0 * NN;
     for (int c = c0 + 1; c < c1; ++c) {                           // R <- P_c R (later chunk on the left)
         cplx* dst = c == c1 - 1 ? out : gm.ts_Rtmp + (size_t)((c - c0) & 1) * NN;
@@ -132,9 +130,7 @@ static inline void qoc_gemm_ts_prefix(QocGemm& gm, const QocDev& d, int G, hipSt
     const int N = gm.N, xw = N, ld = xw + QOC_TW;
     const size_t NN = (size_t)N * N, yslot = (size_t)N * ld;
     hipLaunchKernelGGL(k_gemm_chain_init, dim3(gemm_grid((size_t)N * ld)), dim3(256), 0, s, d, gm.ts_Yr, gm.Psibnd, N, gm.NC, xw);   // Yr[0], Psibnd[0], inter[0]
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.lda = N; g.ldb = g.ldc = ld; g.Kdim = N; g.tiles_m = N / 32; g.tiles_n = ld / 32; g.batch = 1; g.alpha = 1.0;
+    GemmArgs g = qoc_gemm_boundary_args(N, ld, 1, 0, 0);
     for (int q = 0; q < G; ++q) {
         g.A = gm.ts_Rall + (size_t)q * NN; g.Bm = gm.ts_Yr + (size_t)q * yslot; g.C = gm.ts_Yr + (size_t)(q + 1) * yslot;
         qoc_gemm_launch(gm, false, 0, g, s);
@@ -153,17 +149,13 @@ static inline void qoc_gemm_ts_forward(QocGemm& gm, const QocDev& d, int r, hipS
     // Psi at the start of the rank's chunks: the thin block of Ystart, then Psibnd[c + 1] = P_c Psibnd[c] on the m vectors alone (the wide X beside them is
     // only needed in the prefix over the RANK products, qoc_gemm_ts_prefix; final_state comes from there)
     hipLaunchKernelGGL(k_ts_take_bnd, dim3(gemm_grid(thin)), dim3(256), 0, s, d, (const cplx*)gm.Y0, Ystart, gm.Psibnd, N, xw, c0, 1);
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.lda = N; g.ldb = g.ldc = QOC_TW; g.Kdim = N; g.tiles_m = N / 32; g.tiles_n = 1; g.batch = 1; g.alpha = 1.0;
+    GemmArgs g = qoc_gemm_thin_args(N, 1, false);
     for (int c = c0; c + 1 < c1; ++c) {                           // (the last chunk's end is the next rank's start)
         g.A = Pc + (size_t)c * NN; g.Bm = gm.Psibnd + (size_t)c * thin; g.C = gm.Psibnd + (size_t)(c + 1) * thin;
         qoc_gemm_launch(gm, false, 0, g, s);
     }
-    GemmArgs h;
-    memset(&h, 0, sizeof h);
-    h.lda = N; h.sA = (long long)NN * S; h.ldb = h.ldc = QOC_TW; h.Kdim = N; h.tiles_m = N / 32; h.tiles_n = 1;
-    h.batch = nc; h.alpha = 1.0; h.sC = (long long)thin * S;
+    GemmArgs h = qoc_gemm_thin_args(N, nc, false);
+    h.sA = (long long)NN * S; h.sC = (long long)thin * S;
     const size_t i0 = (size_t)c0 * S;
     for (int j = 0; j < S; ++j) {                                 // Psi_{cS+j} = K_{cS+j} Psi_{cS+j-1}: the rank's chunks together, one launch per j
         h.A = gm.K + (i0 + j) * NN;
@@ -184,9 +176,7 @@ static inline void qoc_gemm_ts_suffix(QocGemm& gm, const QocDev& d, int G, hipSt
     const size_t NN = (size_t)N * N, thin = (size_t)N * QOC_TW;
     hipLaunchKernelGGL(k_gemm_sources, dim3(gemm_grid(thin)), dim3(256), 0, s, d, gm.SrcP, gm.Ebnd, N, gm.SP, NC, QOC_TW);        // Ebnd[NC - 1] = -(2 / m^2) z W
     hipLaunchKernelGGL(k_ts_copy, dim3(gemm_grid(thin)), dim3(256), 0, s, gm.ts_Er + (size_t)G * thin, (const cplx*)(gm.Ebnd + (size_t)(NC - 1) * thin), thin);
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.lda = N; g.ldb = g.ldc = QOC_TW; g.Kdim = N; g.tiles_m = N / 32; g.tiles_n = 1; g.batch = 1; g.alpha = 1.0;
+    GemmArgs g = qoc_gemm_thin_args(N, 1, false);
     for (int q = G - 1; q >= 1; --q) {
         g.A = gm.ts_Rall + (size_t)q * NN; g.Bm = gm.ts_Er + (size_t)(q + 1) * thin; g.C = gm.ts_Er + (size_t)q * thin;
         qoc_gemm_launch(gm, true, 0, g, s);
@@ -200,33 +190,24 @@ static inline void qoc_gemm_ts_backward(QocGemm& gm, const QocDev& d, int r, hip
     const int c0 = gm.ts_cb[r], c1 = gm.ts_cb[r + 1], nc = c1 - c0;
     const cplx* Pc = qoc_gemm_chunk_products(gm);
     hipLaunchKernelGGL(k_ts_copy, dim3(gemm_grid(thin)), dim3(256), 0, s, gm.Ebnd + (size_t)(c1 - 1) * thin, (const cplx*)(gm.ts_Er + (size_t)(r + 1) * thin), thin);
-    GemmArgs g;
-    memset(&g, 0, sizeof g);
-    g.lda = N; g.ldb = g.ldc = QOC_TW; g.Kdim = N; g.tiles_m = N / 32; g.tiles_n = 1; g.batch = 1; g.alpha = 1.0;
+    GemmArgs g = qoc_gemm_thin_args(N, 1, false);
     for (int c = c1 - 1; c > c0; --c) {                           // E_{c-1} = P_c^dagger E_c
         g.A = Pc + (size_t)c * NN; g.Bm = gm.Ebnd + (size_t)c * thin; g.C = gm.Ebnd + (size_t)(c - 1) * thin;
         qoc_gemm_launch(gm, true, 0, g, s);
     }
     hipLaunchKernelGGL(k_ts_set_chunk_ends, dim3(gemm_grid((size_t)nc * thin)), dim3(256), 0, s, gm.LamP, (const cplx*)gm.Ebnd, N, S, c0, nc);
     const size_t i0 = (size_t)c0 * S;
-    GemmArgs w;
-    memset(&w, 0, sizeof w);
-    w.lda = N; w.sA = (long long)NN * S; w.ldb = w.ldc = QOC_TW; w.sB = w.sC = (long long)thin * S;
-    w.Kdim = N; w.tiles_m = N / 32; w.tiles_n = 1; w.batch = nc; w.alpha = 1.0;
+    GemmArgs w = qoc_gemm_thin_args(N, nc, false);
+    w.sA = (long long)NN * S; w.sB = w.sC = (long long)thin * S;
     for (int j = S - 1; j >= 1; --j) {                            // Lambda_{cS+j-1} = K_{cS+j}^dagger Lambda_{cS+j}
         w.A = gm.K + (i0 + j) * NN; w.Bm = gm.LamP + (i0 + j) * thin; w.C = gm.LamP + (i0 + j - 1) * thin;
         qoc_gemm_launch(gm, true, 0, w, s);
     }
-    // gradients of the slices [t0, t1): one wide product for all controls (qoc_kernels_gemm.h, "gradients of large problems")
+    // gradients of the slices [t0, t1): one wide product for all controls (as qoc_gemm_gradient_wide_per_seed, qoc_gemm_routes.h)
     const int t0 = (int)i0, t1 = min((int)(i0 + (size_t)nc * S), d.steps);
     if (t1 <= t0) return;
     const int cnt = t1 - t0, W = (int)((((size_t)cnt * QOC_WIDE_MV + 127) / 128) * 128);
-    GemmArgs h;
-    memset(&h, 0, sizeof h);
-    h.A = gm.HsP + NN; h.sA = (long long)NN; h.lda = N;
-    h.Bm = gm.wideP; h.sB = 0; h.ldb = W;
-    h.C = gm.wideC; h.sC = (long long)N * W; h.ldc = W;
-    h.Kdim = N; h.tiles_m = N / 32; h.tiles_n = W / 32; h.batch = d.k; h.alpha = 1.0;
+    const GemmArgs h = qoc_gemm_controls_args(gm, d, W);
     hipLaunchKernelGGL(k_gemm_to_wide, dim3(gemm_grid((size_t)cnt * N * QOC_WIDE_MV)), dim3(256), 0, s, d, (const cplx*)(gm.interP + (size_t)t0 * thin),
                        (const cplx*)(gm.LamP + (size_t)t0 * thin), gm.wideP, gm.wideL, N, W, cnt);
     qoc_gemm_launch(gm, false, 0, h, s);

@@ -2,7 +2,7 @@
 // dynamic LDS.  qoc_mfma_setup resolves all of it once (one resolver per translation unit, next to the kernels it picks from) and opts the
 // picked kernels in for their LDS; the launchers walk the records.  QocMfma stays the kernels' argument; the plan lives beside it in the engine.
 #pragma once
-#include <type_traits>
+#include "qoc_pick.h"                 // QocOneOf / qoc_pick: the one idiom for the template ladders
 #include "qoc_mfma_frag.h"
 
 // one launch, typed by the kernel's argument list.  fn == nullptr: this engine never makes the launch
@@ -14,15 +14,6 @@ template <class... A> struct QocLaunch {
     void run(hipStream_t s, const A&... a) const { if (fn) hipLaunchKernelGGL(fn, grid, block, lds, s, a...); }
     bool reserve() const { return !fn || !lds || hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }
 };
-
-// the one idiom for the template ladders: qoc_pick(f, QocOneOf<4, 8>{kc}, QocOneOf<8, 7, 6, 5>{qa}) calls f(integral_constant<int, kc>,
-// integral_constant<int, qa>) -- each run-time value as the compile-time constant of its list that equals it, the LAST of the list when none does
-template <int... Vs> struct QocOneOf { int v; };
-template <class F> static inline void qoc_pick(F&& f) { f(); }
-template <class F, int V0, int... Vs, class... Rest> static inline void qoc_pick(F&& f, QocOneOf<V0, Vs...> a, Rest... rest) {
-    if constexpr (sizeof...(Vs) > 0) { if (a.v != V0) { qoc_pick(f, QocOneOf<Vs...>{a.v}, rest...); return; } }
-    qoc_pick([&](auto... c) { f(std::integral_constant<int, V0>{}, c...); }, rest...);
-}
 
 struct QocMfmaPlan {
     using K1 = QocLaunch<QocDev>;

@@ -367,7 +367,7 @@ def test_direct_route_on_the_squared_generator_chain(n, steps, terms, reg):
 @pytest.mark.parametrize('env', [{'QOC_ASM_CUMASK': '0'}, {'QOC_ASM_OVERLAP': '0'}, {'QOC_ASM_CUMASK': '70', 'QOC_ASM_TAIL_WGS': '300', 'QOC_ASM_SPLIT16': '9'}],
                          ids=['shared_cus', 'no_overlap', 'other_mask_and_split'])
 def test_direct_route_assembly_overlap_fallbacks(env, monkeypatch):
-    """The generator assembly beside the forward chain (csrc/qoc_kernels_gemm.h, QocGemm::asm_split) in its other forms: both kernels on shared CUs (what
+    """The generator assembly beside the forward chain (csrc/qoc_gemm_setup.h, QocGemm::asm_split) in its other forms: both kernels on shared CUs (what
     runs when more than 96 control sets leave no room for a CU mask), no overlap at all, another mask / throttle / split -- same results as the default
     form to round-off of nothing (the arithmetic is the same: compared exactly), and against the oracle."""
     c = cases.case_c3(n=64, k=3, steps=150, taylor=(10, 0))

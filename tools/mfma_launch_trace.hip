@@ -1,8 +1,8 @@
 // mfma_launch_trace.hip -- the launches of the MFMA path, traced on the host: for a table of problems, qoc_mfma_setup, every launcher (with and
 // without a fused tail, the pulse regularisers both ways) and every read-back entry point an engine of that problem can call, through the shim
-// mfma_launch_trace.h.  A dispatch edit is checked by building this program against csrc/ before and after it and comparing the two outputs:
+// launch_trace.h.  A dispatch edit is checked by building this program against csrc/ before and after it and comparing the two outputs:
 //
-//   hipcc --offload-arch=gfx950 -O1 -std=c++17 -Wno-unused-value -rdynamic -include tools/mfma_launch_trace.h -I <csrc> -I include \
+//   hipcc --offload-arch=gfx950 -O1 -std=c++17 -Wno-unused-value -rdynamic -include tools/launch_trace.h -I <csrc> -I include \
 //       tools/mfma_launch_trace.hip <csrc>/qoc_mfma_{expm,expm_inplace,forward,backward,latency}.hip -o mfma_launch_trace -ldl
 //   ./mfma_launch_trace > after.txt          one line per problem: its parameters, the number of trace lines, a hash of them
 //   ./mfma_launch_trace -v 1000 > after_v.txt     the trace lines themselves for every 1000th problem (-v 1: all of them), -o <i>: of problem i alone
@@ -73,7 +73,7 @@ hipError_t qoc_trace_reserve(const void* kernel, int bytes) {
     if (g_in_setup && g_reserved[kernel] < bytes) g_reserved[kernel] = bytes;
     return hipSuccess;
 }
-hipError_t qoc_trace_launch(const void* kernel, dim3 grid, dim3 block, size_t lds, const QocTraceArg* args, int count) {
+hipError_t qoc_trace_launch(const void* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t, const QocTraceArg* args, int count) {
     const std::string name = symbol(kernel);
     g_kernels.insert(name);
     std::string a;
