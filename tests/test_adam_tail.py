@@ -185,9 +185,10 @@ def _max_iterations(problem):
     return 11 if _ks(problem) <= 4200 else 7             # (poll every 5: never a divisor)
 
 
-def _choose_target(hists, max_it):
+def _choose_target(hists, max_it, accept=None):
     """A conv_target at which the control sets stop at >= 2 distinct iteration counts, one of them runs to max_iterations, and no loss of any
-    history lies within 1e-8 relative of it (the stop never rests on the last bit).  Midpoints between the losses, the widest margin wins."""
+    history lies within 1e-8 relative of it (the stop never rests on the last bit).  Midpoints between the losses, the widest margin wins.
+    accept(stops): a further condition on the stop counts a caller needs (tests/test_finished_sets_gpu.py)."""
     losses = np.sort(np.unique(np.concatenate([h[:, 0] for h in hists])))
     best = None
     for lo, hi in zip(losses[:-1], losses[1:]):
@@ -199,9 +200,29 @@ def _choose_target(hists, max_it):
         margin = min(np.min(np.abs(h[:, 0] - t)) / abs(t) for h in hists)
         inner = sum(0 < s < max_it for s in stops)
         key = (len(set(stops)), max_it in stops, inner, margin)
-        if max_it in stops and len(set(stops)) >= 2 and (best is None or key > best[0]):
+        if max_it in stops and len(set(stops)) >= 2 and (accept is None or accept(stops)) and (best is None or key > best[0]):
             best = (key, t, stops)
     assert best is not None, 'no conv_target splits the control sets'
+    return best[1], best[2]
+
+
+def _choose_min_grad(hists, max_it, accept=None):
+    """_choose_target for the other stop rule: a min_grad between two grad_squared values of the free runs at which the control sets stop at
+    >= 2 distinct iteration counts and no value of any history lies within 1e-8 relative of it.  The widest margin wins.  accept(stops): as
+    above -- without it the distinct count ranks first, and a problem whose gradients only ever fall gives 0 and max_iterations alone."""
+    values = np.sort(np.unique(np.concatenate([h[:, 2] for h in hists])))
+    best = None
+    for lo, hi in zip(values[:-1], values[1:]):
+        t = 0.5 * (lo + hi)
+        stops = []
+        for h in hists:
+            below = np.nonzero(h[:, 2] < t)[0]
+            stops.append(int(below[0]) if len(below) else max_it)
+        margin = min(np.min(np.abs(h[:, 2] - t)) / abs(t) for h in hists)
+        key = (len(set(stops)), sum(0 < s < max_it for s in stops), margin)
+        if len(set(stops)) >= 2 and margin > 1e-8 and (accept is None or accept(stops)) and (best is None or key > best[0]):
+            best = (key, t, stops)
+    assert best is not None, 'no min_grad splits the control sets'
     return best[1], best[2]
 
 

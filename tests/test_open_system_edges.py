@@ -44,7 +44,7 @@ from quantum_optimal_control.core import hip_engine
 from tests import lindblad_reference as lr
 from tests import test_coexisting_engines as ce
 from tests import test_open_system_gpu as og
-from tests.test_adam_tail import LOOP_ATOL, _choose_target
+from tests.test_adam_tail import LOOP_ATOL, _choose_min_grad, _choose_target          # (_choose_min_grad lived here: the import keeps the name)
 from tests.test_hip_parity import G_RTOL, S_RTOL
 from tests.test_open_system import bases_of, open_case
 from tests.test_open_system_gpu import assert_eval, assert_gradient, assert_scalar, make_engine
@@ -433,25 +433,6 @@ def test_random_open_problem(seed):
 
 
 # ---- 3. the loop, explicit steps, reads between bursts --------------------------------------------------------------------------------------
-
-def _choose_min_grad(hists, max_it):
-    """_choose_target for the other stop rule: a min_grad between two grad_squared values of the free runs at which the control sets stop at
-    >= 2 distinct iteration counts and no value of any history lies within 1e-8 relative of it.  The widest margin wins."""
-    values = np.sort(np.unique(np.concatenate([h[:, 2] for h in hists])))
-    best = None
-    for lo, hi in zip(values[:-1], values[1:]):
-        t = 0.5 * (lo + hi)
-        stops = []
-        for h in hists:
-            below = np.nonzero(h[:, 2] < t)[0]
-            stops.append(int(below[0]) if len(below) else max_it)
-        margin = min(np.min(np.abs(h[:, 2] - t)) / abs(t) for h in hists)
-        key = (len(set(stops)), sum(0 < s < max_it for s in stops), margin)
-        if len(set(stops)) >= 2 and margin > 1e-8 and (best is None or key > best[0]):
-            best = (key, t, stops)
-    assert best is not None, 'no min_grad splits the control sets'
-    return best[1], best[2]
-
 
 def _loop_system(name):
     return og.system('regs') if name == 'regs' else system(name)
