@@ -44,6 +44,9 @@ extern "C" {
 #define QOC_PATH_LINDBLAD 6    /* engines made by qoc_create_open only: n <= 32, density operators of the pairs of states of interest resident in LDS,
                                 * plain complex-fp64 FMAs (csrc/qoc_lindblad.h) */
 
+#define QOC_PATH_SPARSE 7      /* engines made by qoc_create_sparse only: state transfer on sparse operators, any n; ELLPACK mat-vecs, the state vector of a
+                                * (control set, column) resident in the LDS of one compute unit up to n = 5088, in global scratch above (csrc/qoc_sparse.h) */
+
 typedef struct qoc_engine* qoc_handle;
 
 /* Static problem description == what SystemParameters hands to TensorflowState
@@ -236,6 +239,29 @@ int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* H
 int qoc_get_final_density(qoc_handle h, double* rho);
 /* Re rho_ii(tau)[l][l] of the last evaluation, [n_seeds][steps+1][n][m] (tau = 0 is the start): the populations a closed run derives from inter_vecs */
 int qoc_get_populations(qoc_handle h, double* pop);
+
+/* ---- sparse state transfer: the operators are never dense (the reference has sparse_H / sparse_U / sparse_K for systems built from Kronecker products
+ * and switches them off under use_gpu, main_grape/grape.py:28-32) ----------------------------------------------------------------------------
+ * The k + 1 operators -i dt H0, -i dt H_1 .. come as COO entries in any order; duplicates of a position are summed, explicit zeros are kept.  The
+ * engine stores each in ELLPACK with a width of its own (the largest number of entries in one of its rows) and never forms an n x n array, on the
+ * host or on the device: memory is O(sum_j n W_j + n_seeds steps n m), so n = 2^14 and beyond fit where one dense operator would not.
+ * The mathematics is the state-transfer branch of every other engine (matvecexp_op: psi_{t+1} = sum_{j < taylor_terms} B_t^j psi_t / j!, costates with
+ * -B_t, first-order gradient), with loss, unitary_scale, bare forbidden levels, speed_up, every pulse regulariser, the Adam tail, the L-BFGS step and
+ * the stop rule unchanged, so every entry point below works as on any engine; qoc_get_final_unitary returns QOC_ERR_STATE as for state transfer elsewhere.
+ * Operators need not be Hermitian.  Two evaluations are bit-identical, and so are the two vector homes.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: unitary mode; forbid_dressed; gradient = 1; time_shards > 0; an explicit path
+ * other than AUTO or QOC_PATH_SPARSE; taylor_terms < 1 or > 60; m < 1; an index outside 0 .. n-1; a non-finite value; n * W_j (or n * m) past int32;
+ * vector_home outside 0 .. 2, or 1 where the vectors do not fit.  Device memory that does not fit: QOC_ERR_NOMEM. */
+typedef struct qoc_sparse {
+    const int64_t* indptr;      /* [k+2] operator j owns entries indptr[j] .. indptr[j+1] of the three arrays below */
+    const int32_t* row;
+    const int32_t* col;
+    const double* val;          /* complex (re, im): -i dt H_j */
+    int32_t vector_home;        /* where the two vectors of a sweep's Taylor chain live: 0 auto (LDS while 2 n 16 B <= 159 KiB, i.e. n <= 5088),
+                                 * 1 LDS (QOC_ERR_INVALID if it does not fit), 2 global scratch */
+} qoc_sparse;
+int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
+                      const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out);
 
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).

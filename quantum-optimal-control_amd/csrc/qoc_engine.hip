@@ -30,6 +30,8 @@
 #include "qoc_transfer.h"
 #include "qoc_exact_grad.h"
 #include "qoc_lindblad.h"
+#include "qoc_sparse.h"
+#include "qoc_sparse_host.h"
 #include "qoc_lbfgs.h"
 
 #include "qoc_plan_limits.h"            // the measured numbers of AUTO's table (QOC_PLAN_*), shared with tests/test_auto_plan.py
@@ -109,6 +111,9 @@ struct qoc_engine {
     QocExact xg{};
     // open-system GRAPE (qoc_create_open, csrc/qoc_lindblad.h): density operators of the pairs of states of interest under a Lindblad master equation
     QocLb lb{};
+    // sparse state transfer (qoc_create_sparse, csrc/qoc_sparse.h): ELLPACK operators, no n x n array anywhere (d.Hs, d.U0 and d.Xfinal stay null)
+    QocSparse sp{};
+    std::vector<int> sp_widths;     // [k+1] W_j, for qoc_plan_describe
     // device-resident L-BFGS loop (qoc_iterate_lbfgs / qoc_run_lbfgs, csrc/qoc_lbfgs.h): per-set state, allocated by the first call for lq_cap pairs
     QocLbfgsDev lq{};
     int lq_cap = 0;
@@ -374,6 +379,12 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
         qoc_lb_forward(e->lb, d, e->stream);
         TRY(prof_end(e));
         qoc_lb_backward(e->lb, d, e->stream);
+    } else if (e->path == QOC_PATH_SPARSE) {                            // sparse state transfer: forward, loss, costates + gradient (csrc/qoc_sparse.h)
+        TRY(prof_begin(e));
+        qoc_sp_forward(e->sp, d, e->stream);
+        TRY(prof_end(e));
+        launch_loss(d, e->stream);
+        qoc_sp_backward(e->sp, d, e->stream);
     } else if (e->path == QOC_PATH_ST_FUSED) {
         TRY(prof_begin(e));
         st_fused_launch(d, e->stream, true);
@@ -622,13 +633,20 @@ struct EnsArgs {
     const ShapeHost* shape;          // qoc_create_shaped: the response matrix and its windows, else null
 };
 
-// the caller's arrays of qoc_create (include/qoc.h), passed on together
+// the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
+struct SparseHost {
+    std::vector<QocEllOp> ops;       // [k+1]
+    int vector_home;
+};
+
+// the caller's arrays of qoc_create (include/qoc.h), passed on together (sparse: the operators of qoc_create_sparse in place of Hs, else null)
 struct Problem {
     const double *Hs, *U0, *V, *W, *maxA, *one_minus_gauss; const int32_t* forbidden_states; const double *forbidden_coeffs, *Vs;
+    const SparseHost* sparse;
 };
 
 static int check_create_args(const qoc_config* cfg, const Problem& p, qoc_handle* out) {
-    if (!cfg || !p.Hs || !p.V || !p.W || !p.maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create: null argument");
+    if (!cfg || (!p.Hs && !p.sparse) || !p.V || !p.W || !p.maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create: null argument");
     if (cfg->plan_seeds < 0)
         return fail(QOC_ERR_INVALID, "qoc_create: plan_seeds = %d (0 = plan for n_seeds, > 0 = the batch AUTO plans for)", cfg->plan_seeds);
     if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->m < 1 || cfg->n_seeds < 1)
@@ -723,10 +741,13 @@ static int build_trajectory_view(qoc_engine* e, const Problem& p) {
     QocDev& d = e->d;
     const size_t B = (size_t)d.B, pts = B * (d.steps + 1), nn = (size_t)d.n * d.n, nm = (size_t)d.n * d.m;
     const std::vector<double> psi0 = start_vectors(c, p.U0, p.V);
-    std::vector<double> ident(p.U0 ? 0 : 2 * nn, 0.0);             // (state transfer without a start unitary)
-    if (!p.U0) for (int a = 0; a < c.n; ++a) ident[2 * (a * c.n + a)] = 1.0;
-    TRY(dev_upload(e, &d.Hs, (const cplx*)p.Hs, (size_t)(c.k + 1) * nn));
-    TRY(dev_upload(e, &d.U0, (const cplx*)(p.U0 ? p.U0 : ident.data()), nn));
+    // a sparse engine holds no n x n array, on the host or on the device: d.Hs, d.U0 and d.Xfinal stay null (no kernel of its path reads them)
+    if (!p.sparse) {
+        std::vector<double> ident(p.U0 ? 0 : 2 * nn, 0.0);         // (state transfer without a start unitary)
+        if (!p.U0) for (int a = 0; a < c.n; ++a) ident[2 * (a * c.n + a)] = 1.0;
+        TRY(dev_upload(e, &d.Hs, (const cplx*)p.Hs, (size_t)(c.k + 1) * nn));
+        TRY(dev_upload(e, &d.U0, (const cplx*)(p.U0 ? p.U0 : ident.data()), nn));
+    }
     TRY(dev_upload(e, &d.V, (const cplx*)p.V, nm)); TRY(dev_upload(e, &d.W, (const cplx*)p.W, nm));
     TRY(dev_upload(e, &d.Psi0, (const cplx*)psi0.data(), nm));
     if (d.forbid_dressed) TRY(dev_upload(e, &d.Vs, (const cplx*)p.Vs, nn));
@@ -739,7 +760,9 @@ static int build_trajectory_view(qoc_engine* e, const Problem& p) {
         TRY(dev_upload(e, &d.forb_a, (const double*)fa.data(), (size_t)c.n_forbidden));
     }
     TRY(alloc_set_arrays(e, d, "qoc_create", !e->ens_E));         // (an ensemble runs the tail on its group view)
-    TRY(dev_alloc(e, &d.inter, pts * nm)); TRY(dev_zalloc(e, &d.Xfinal, B * nn, "qoc_create")); TRY(dev_alloc(e, &d.ztau, pts));
+    TRY(dev_alloc(e, &d.inter, pts * nm));
+    if (!p.sparse) TRY(dev_zalloc(e, &d.Xfinal, B * nn, "qoc_create"));
+    TRY(dev_alloc(e, &d.ztau, pts));
     if (d.n_forb > 0) TRY(dev_alloc(e, &d.Fpop, pts * d.n_forb * d.m));
     if (d.forbid_dressed && d.n_forb > 0) TRY(dev_alloc(e, &d.Fd, pts * d.n_forb * d.m));
     TRY(dev_alloc(e, &d.zfin, B)); TRY(dev_zalloc(e, &d.su_resid, B, "qoc_create"));
@@ -1027,6 +1050,38 @@ static int setup_lindblad(qoc_engine* e, const Problem& p, const qoc_open* op) {
     return QOC_OK;
 }
 
+// the buffers of a sparse engine: the ELLPACK blocks in one pool, the costates of every slice, the vectors' scratch when they do not live in LDS
+static int setup_sparse(qoc_engine* e, const SparseHost& h) {
+    const QocDev& d = e->d;
+    QocSparse& sp = e->sp;
+    // QOC_EXPERIMENTAL=1 QOC_SP_THREADS=256|1024: the sweeps' workgroup size, for the A/B runs behind QOC_SP_WIDE_FROM
+    int threads = 0;
+    if (const char* t = qoc_exp_env("QOC_SP_THREADS")) threads = atoi(t) == 1024 ? 1024 : (atoi(t) == 256 ? 256 : 0);
+    if (const char* why = qoc_sp_plan(sp, d, h.vector_home, threads)) return fail(QOC_ERR_INVALID, "qoc_create_sparse: %s (n = %d)", why, d.n);
+    const size_t n = (size_t)d.n, K = h.ops.size();
+    std::vector<int> W(K);
+    std::vector<long long> off(K);
+    size_t total = 0;
+    for (size_t j = 0; j < K; ++j) { W[j] = h.ops[j].W; off[j] = (long long)total; total += n * (size_t)W[j]; sp.stored += h.ops[j].stored; }
+    int* col = nullptr;
+    cplx* val = nullptr;
+    TRY(dev_alloc(e, &col, total));
+    TRY(dev_alloc(e, &val, total));
+    for (size_t j = 0; j < K; ++j) {
+        if (!W[j]) continue;
+        HIP_TRY(hipMemcpy(col + off[j], h.ops[j].col.data(), n * W[j] * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(val + off[j], h.ops[j].val.data(), n * W[j] * sizeof(cplx), hipMemcpyHostToDevice));
+    }
+    sp.col = col; sp.val = val;
+    e->sp_widths = W;
+    TRY(dev_upload(e, &sp.W, (const int*)W.data(), K));
+    TRY(dev_upload(e, &sp.off, (const long long*)off.data(), K));
+    TRY(dev_alloc(e, &sp.Lam, (size_t)d.B * d.steps * n * d.m));
+    if (sp.home == 2) TRY(dev_alloc(e, &sp.scratch, (size_t)d.B * d.m * 2 * n));
+    HIP_TRY_MSG(qoc_sp_lds_opt_in(sp), "qoc_create_sparse: cannot reserve %zu bytes of LDS for the sparse sweeps", sp.lds_bytes);
+    return QOC_OK;
+}
+
 static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out, const qoc_open* open = nullptr) {
     TRY(check_create_args(cfg, p, out));
     HIP_TRY(hipSetDevice(cfg->device));
@@ -1049,11 +1104,12 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
     HIP_TRY_MSG(hipEventCreate(&e->t0), "hipEventCreate failed");
     HIP_TRY_MSG(hipEventCreate(&e->t1), "hipEventCreate failed");
     TRY(build_trajectory_view(e, p));
-    const bool antiherm = cfg->state_transfer ? qoc_all_antihermitian((const cplx*)p.Hs, cfg->n, cfg->k + 1) : true;
+    const bool antiherm = p.sparse ? false : cfg->state_transfer ? qoc_all_antihermitian((const cplx*)p.Hs, cfg->n, cfg->k + 1) : true;
     AutoPlan plan{};
     // (an open engine has been through build_trajectory_view like every engine: d.inter, d.Xfinal, d.ztau and zfin are allocated there and never
     // touched by the open path -- (steps + 1) n m + n^2 numbers per control set, small beside its history; left so as not to fork that helper)
     if (open) plan.path = QOC_PATH_LINDBLAD;                     // (one home, as the exact gradient has: no table to consult)
+    else if (p.sparse) plan.path = QOC_PATH_SPARSE;
     else TRY(choose_path(*cfg, d, antiherm, ens != nullptr, plan));
     e->path = plan.path; e->chunks = 1;
 #ifdef QOC_DEBUG     // timing experiments only (tools/skip_timing.py builds its own library with -DQOC_DEBUG): never in the product library
@@ -1064,6 +1120,7 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
     }
 #endif
     if (open) TRY(setup_lindblad(e, p, open));
+    else if (p.sparse) TRY(setup_sparse(e, *p.sparse));
     else TRY(setup_path(e, p.Hs, antiherm, plan));
     if (cfg->gradient == 1) TRY(setup_exact_gradient(e));
     if (ens) TRY(setup_group_view(e, *ens));
@@ -1134,6 +1191,41 @@ int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* H
     for (size_t i = 0; i < 2 * (size_t)c * n * n; ++i)
         if (!std::isfinite(open->C[i])) return fail(QOC_ERR_INVALID, "qoc_create_open: a collapse operator is not finite");
     return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, open);
+}
+
+int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
+                      const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out) {
+    if (!cfg || !ops || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_sparse: null argument");
+    if (!cfg->state_transfer) return fail(QOC_ERR_INVALID, "qoc_create_sparse: sparse operators run in state-transfer mode only (unitary mode propagates an n x n matrix)");
+    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "qoc_create_sparse: forbid_dressed needs the n x n matrix of dressed states; forbidden levels are bare on a sparse engine");
+    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "qoc_create_sparse: the exact gradient is not available on sparse operators (gradient = %d)", cfg->gradient);
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_sparse: a sparse engine cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_SPARSE)
+        return fail(QOC_ERR_INVALID, "qoc_create_sparse: sparse operators run on QOC_PATH_SPARSE (or AUTO), not on path %d", cfg->path);
+    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1) return fail(QOC_ERR_INVALID, "qoc_create_sparse: n, k, steps, n_seeds must be >= 1");
+    if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_SP_MAX_T)
+        return fail(QOC_ERR_INVALID, "qoc_create_sparse: taylor_terms = %d (1 .. %d)", cfg->taylor_terms, QOC_SP_MAX_T);
+    if (cfg->m < 1) return fail(QOC_ERR_INVALID, "qoc_create_sparse: m = %d states of interest (>= 1)", cfg->m);
+    if ((long long)cfg->n * cfg->m > (long long)INT32_MAX) return fail(QOC_ERR_INVALID, "qoc_create_sparse: n * m = %d * %d does not fit 32-bit indices", cfg->n, cfg->m);
+    if (ops->vector_home < 0 || ops->vector_home > 2) return fail(QOC_ERR_INVALID, "qoc_create_sparse: vector_home = %d (0 auto, 1 LDS, 2 global scratch)", ops->vector_home);
+    if (ops->vector_home == 1 && 2 * (size_t)cfg->n * sizeof(cplx) > QOC_SP_LDS_LIMIT)
+        return fail(QOC_ERR_INVALID, "qoc_create_sparse: vector_home = 1 (LDS) needs 2 n 16 bytes <= 159 KiB (n = %d, at most 5088)", cfg->n);
+    if (!ops->indptr) return fail(QOC_ERR_INVALID, "qoc_create_sparse: indptr is missing");
+    const int K = cfg->k + 1;
+    for (int j = 0; j < K; ++j)
+        if (ops->indptr[j] < 0 || ops->indptr[j + 1] < ops->indptr[j]) return fail(QOC_ERR_INVALID, "qoc_create_sparse: indptr[%d .. %d] does not ascend from 0", j, j + 1);
+    if (ops->indptr[K] > 0 && (!ops->row || !ops->col || !ops->val)) return fail(QOC_ERR_INVALID, "qoc_create_sparse: entry arrays missing");
+    // COO -> ELLPACK on the host, before any device is touched: indices in range, values finite, n W_j within int32
+    SparseHost sh;
+    sh.vector_home = ops->vector_home;
+    sh.ops.resize((size_t)K);
+    std::string why;
+    for (int j = 0; j < K; ++j) {
+        const int64_t a = ops->indptr[j], cnt = ops->indptr[j + 1] - a;
+        if (!qoc_ell_build(cfg->n, cnt, ops->row + a, ops->col + a, ops->val + 2 * a, sh.ops[(size_t)j], why))
+            return fail(QOC_ERR_INVALID, "qoc_create_sparse: operator %d: %s", j, why.c_str());
+    }
+    return create_engine(cfg, Problem{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh}, nullptr, out);
 }
 
 // qoc_create_ensemble and qoc_create_shaped (`who` names the caller in the messages; shape: the prepared response of the latter, else null)
@@ -1591,7 +1683,7 @@ int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, 
     CHECK_H(e);
     TRY(prof_collect(e));
     if (kernel_name)
-        *kernel_name = e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
+        *kernel_name = e->path == QOC_PATH_SPARSE ? "k_sp_forward" : e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
                        : e->path == QOC_PATH_GEMM ? (e->gm.route == QOC_GEMM_DIRECT ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
                            : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
                        : e->path == QOC_PATH_MFMA ? e->mp.expm_name             // (the kernel of the exponentials, by its variant)
@@ -1623,6 +1715,8 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
 //   open engines (qoc_create_open): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
+//   sparse engines (qoc_create_sparse): path=sparse nnz=<stored entries> ell=<W_0,..,W_k> vector_home=<lds|global> lds=<bytes of dynamic LDS> threads=<256|1024 of a sweep>
+//   grad_grid=<workgroups of k_sp_grad>
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
 // exact engines add exact_variant=<lds|global> exact_lds=<bytes of dynamic LDS, 0 in the global variant> exact_grid=<workgroups of k_exact_grad>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
@@ -1646,6 +1740,11 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
                              : "butterfly");
     } else if (e->path == QOC_PATH_LINDBLAD) {
         snprintf(tmp, sizeof tmp, "path=lindblad collapse=%d pairs=%d lds=%zu", e->lb.c, e->lb.R, e->lb.lds_bytes);
+    } else if (e->path == QOC_PATH_SPARSE) {
+        const QocSparse& sp = e->sp;
+        int w = snprintf(tmp, sizeof tmp, "path=sparse nnz=%lld ell=", sp.stored);
+        for (size_t j = 0; j < e->sp_widths.size() && w < (int)sizeof tmp - 64; ++j) w += snprintf(tmp + w, sizeof tmp - w, j ? ",%d" : "%d", e->sp_widths[j]);
+        snprintf(tmp + w, sizeof tmp - w, " vector_home=%s lds=%zu threads=%d grad_grid=%d", sp.home == 1 ? "lds" : "global", sp.lds_bytes, sp.threads, sp.grad_grid);
     } else if (e->path == QOC_PATH_SMALL) {
         snprintf(tmp, sizeof tmp, "path=small n_pad=%d rows=%d slices_per_row=%d workgroups=%d state_sources=%d lds_kb=%d", e->sm.N, e->sm.R, e->sm.L, e->sm.G,
             e->sm.src ? 1 : 0, (int)((e->sm.lds_bytes + 1023) / 1024));

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('QOC_HIP_LIBRARY') or os.path.normpath(os.path.join(_H
 
 PATH_AUTO, PATH_GENERIC, PATH_MFMA, PATH_ST_FUSED, PATH_GEMM, PATH_SMALL = 0, 1, 2, 3, 4, 5
 PATH_LINDBLAD = 6          # open engines only (HipEngine(collapse_ops=...))
+PATH_SPARSE = 7            # sparse engines only (HipEngine(sparse_ops=...))
 
 
 class QocConfig(C.Structure):
@@ -44,6 +45,11 @@ class QocOpen(C.Structure):
     _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double))]
 
 
+class QocSparse(C.Structure):
+    _fields_ = [('indptr', C.POINTER(C.c_int64)), ('row', C.POINTER(C.c_int32)), ('col', C.POINTER(C.c_int32)), ('val', C.POINTER(C.c_double)),
+                ('vector_home', C.c_int32)]
+
+
 class QocAdamParams(C.Structure):
     _fields_ = [('rate', C.c_double), ('learning_rate_decay', C.c_double), ('conv_target', C.c_double),
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
@@ -65,6 +71,7 @@ _SIGNATURES = {
     'qoc_create_shaped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP,
                                     _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_open': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocOpen), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_populations': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_pulse': (C.c_int, [C.c_void_p, _DP]),
@@ -302,6 +309,27 @@ def ensemble_arrays(ensemble, n, k, dt):
     return P, off, amp, wt
 
 
+VECTOR_HOME = {None: 0, 'auto': 0, 'lds': 1, 'global': 2}
+
+
+def sparse_arrays(sparse_ops):
+    """The C ABI's qoc_sparse arrays from a list of k + 1 scipy.sparse matrices (already -i dt H_j): (n, indptr, row, col, val), the entries of the
+    operators one after the other in COO form.  No operator is densified; duplicates and explicit zeros go through as they are (the library sums the
+    former and keeps the latter)."""
+    import scipy.sparse as sps
+    coos = [sps.coo_matrix(a) for a in sparse_ops]
+    n = coos[0].shape[0]
+    for a in coos:
+        if a.shape != (n, n):
+            raise ValueError('HipEngine: sparse operators must all be (%d, %d), got %s' % (n, n, a.shape))
+    indptr = np.zeros(len(coos) + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum([a.nnz for a in coos])
+    row = np.ascontiguousarray(np.concatenate([a.row for a in coos]).astype(np.int32))
+    col = np.ascontiguousarray(np.concatenate([a.col for a in coos]).astype(np.int32))
+    val = np.ascontiguousarray(np.concatenate([a.data for a in coos]).astype(np.complex128))
+    return n, indptr, row, col, val
+
+
 class HipEngine(object):
     """Device-resident GRAPE problem: constants in HBM, n_seeds control sets, one HIP stream.
 
@@ -322,11 +350,31 @@ class HipEngine(object):
     rates (helper_functions/open_system.py builds the usual ones; an empty list is the closed limit).  The engine then propagates the operators
     psi_i psi_j^dagger of the states of interest under the Lindblad master equation, with degree taylor_terms and 2^scaling sub-steps per slice in
     both modes; loss, gradient and the optimiser entry points keep their shapes, get_final_density() and get_populations() take the place of
-    get_final_unitary() and get_inter_vecs().  Combines with none of ensemble, transfer, exact_gradient or time sharding (ValueError)."""
+    get_final_unitary() and get_inter_vecs().  Combines with none of ensemble, transfer, exact_gradient or time sharding (ValueError).
+
+    sparse_ops (sparse state transfer, include/qoc.h qoc_create_sparse): a list of k + 1 scipy.sparse matrices -i dt H0, -i dt H_1 .. in place of Hs
+    (pass Hs=None, U0=None).  State transfer only; the engine keeps every operator in ELLPACK and never forms an n x n array, so n = 2^14 and more
+    fit.  vector_home: None / 'auto', 'lds' or 'global' (where the Taylor chain's two vectors live; A/B runs and tests).  Every other entry point
+    works as on a dense state-transfer engine.  Combines with none of ensemble, transfer, exact_gradient, collapse_ops, Vs or time sharding, and
+    only with path AUTO or PATH_SPARSE (ValueError, before the library is loaded)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
-                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None):
+                 time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
+                 sparse_ops=None, vector_home=None):
+        sparse = None
+        if sparse_ops is not None:
+            for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
+                                ('collapse_ops', collapse_ops is not None), ('time sharding', time_comm is not None or int(time_shards) > 0),
+                                ('Vs (dressed forbidden levels)', Vs is not None), ('a dense Hs', Hs is not None), ('U0', U0 is not None),
+                                ('path %s' % (path,), int(path) not in (PATH_AUTO, PATH_SPARSE))):
+                if given:
+                    raise ValueError('HipEngine: sparse_ops (sparse state transfer) does not combine with %s' % name)
+            if not state_transfer:
+                raise ValueError('HipEngine: sparse_ops needs state_transfer=True (unitary mode propagates an n x n matrix)')
+            if vector_home not in VECTOR_HOME:
+                raise ValueError("HipEngine: vector_home is None, 'auto', 'lds' or 'global', got %r" % (vector_home,))
+            sparse = sparse_arrays(sparse_ops)
         if collapse_ops is not None:
             for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
@@ -337,9 +385,12 @@ class HipEngine(object):
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
-        Hs = np.ascontiguousarray(np.asarray(Hs, dtype=np.complex128))
-        k = Hs.shape[0] - 1
-        n = Hs.shape[1]
+        if sparse is None:
+            Hs = np.ascontiguousarray(np.asarray(Hs, dtype=np.complex128))
+            k = Hs.shape[0] - 1
+            n = Hs.shape[1]
+        else:
+            k, n = len(sparse_ops) - 1, sparse[0]
         V = np.ascontiguousarray(np.asarray(V, dtype=np.complex128))
         m = V.shape[1]
         self.n, self.k, self.m, self.steps, self.n_seeds = n, k, m, int(steps), int(n_seeds)
@@ -373,7 +424,7 @@ class HipEngine(object):
             omg = np.ascontiguousarray(np.asarray(one_minus_gauss, dtype=np.float64))
             assert omg.shape == (k, int(steps))
         Vsa = _c128(Vs, (n, n)) if use_vs else None
-        args = (_dp(Hs.view(np.float64)), None if U0a is None else _dp(U0a.view(np.float64)), _dp(V.view(np.float64)), _dp(W.view(np.float64)),
+        args = (None if sparse is not None else _dp(Hs.view(np.float64)), None if U0a is None else _dp(U0a.view(np.float64)), _dp(V.view(np.float64)), _dp(W.view(np.float64)),
                 _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
                 C.byref(self._h))
         self.members = 0
@@ -388,7 +439,13 @@ class HipEngine(object):
             ens.offsets = _dp(off) if P.shape[0] else None
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
-        if collapse_ops is not None:
+        if sparse is not None:
+            _, indptr, row, col, val = sparse
+            sp = QocSparse()
+            sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
+            sp.val, sp.vector_home = _dp(val.view(np.float64)), VECTOR_HOME[vector_home]
+            _check(lib.qoc_create_sparse(C.byref(cfg), C.byref(sp), *(args[2:8] + args[-1:])))
+        elif collapse_ops is not None:
             # D_j = sqrt(dt) C_j; the state regularisers and Vs stay behind (the library refuses them by name)
             D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
             op = QocOpen()

@@ -41,14 +41,16 @@ class HipState(object):
         if needs_inter and not sp.state_transfer and not sp.use_inter_vecs:
             raise TypeError("'NoneType' object is not iterable")         # tfs.inter_vecs is None (:71, :381)
         Hs, U0, V, W, Vs = sp.engine_inputs()
+        # the sparse route (core/sparse_parameters.py): Hs is then the list of scipy.sparse operators, and no dense array stands in for it
+        sparse_ops = Hs if getattr(sp, 'sparse_route', False) else None
         self.engine = hip_engine.HipEngine(
-            Hs, U0, V, W, sp.ops_max_amp, sp.dt, sp.total_time, sp.steps, sp.exp_terms, sp.scaling,
+            None if sparse_ops is not None else Hs, U0, V, W, sp.ops_max_amp, sp.dt, sp.total_time, sp.steps, sp.exp_terms, sp.scaling,
             state_transfer=sp.state_transfer, reg_coeffs=rc,
             one_minus_gauss=sp.one_minus_gauss if 'envelope' in rc else None, Vs=Vs,
             n_seeds=self.n_seeds, device=self.device, path=self.path, chunks=self.chunks, plan_seeds=self.plan_seeds,
             time_shards=0 if self.time_comm is None else self.time_comm.world, time_rank=-1 if self.time_comm is None else self.time_comm.rank,
             time_comm=self.time_comm, ensemble=self.ensemble, transfer=self.transfer, exact_gradient=self.exact_gradient,
-            collapse_ops=self.collapse_ops)
+            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops)
         base = np.asarray(sp.ops_weight_base, dtype=np.float64)
         if base.ndim == 2 and (self.n_seeds > 1 or self.first_seed > 0):
             # global restart 0 = the reference's own starting point; restart g > 0 = the reproducible stream of index g,

@@ -41,3 +41,38 @@ def case_c3(n=64, k=6, steps=1000, taylor=(10, 0), seed=3):
                 reg_coeffs={'dwdt': 1e-3, 'forbidden_coeff_list': [100, 100], 'states_forbidden_list': [n - 2, n - 1]},
                 Taylor_terms=list(taylor) if taylor is not None else None, state_transfer=True, initial_guess=None,
                 dressed_info=None, U0=None, np_seed=seed)
+
+
+def xx_chain(spins, coupling=1.0, control_sites=None):
+    """An XX spin chain as scipy.sparse operators built from Kronecker products (n = 2^spins; the sparse state-transfer route):
+    H0 = (coupling / 2) sum_i (X_i X_{i+1} + Y_i Y_{i+1}), one control Z_i / 2 per site of `control_sites` (default: every site).
+    Returns (H0, Hops, Hnames, excitation) with excitation(i) the basis state that has spin i up and the others down.  Site 0 is the
+    leftmost Kronecker factor; no dense n x n array is formed."""
+    import scipy.sparse as sps
+    X = sps.csr_matrix(np.array([[0, 1], [1, 0]], dtype=np.complex128))
+    Y = sps.csr_matrix(np.array([[0, -1j], [1j, 0]], dtype=np.complex128))
+    Z = sps.csr_matrix(np.array([[1, 0], [0, -1]], dtype=np.complex128))
+
+    def at(ops):
+        """kron of identities with ops[i] at site i"""
+        out = sps.identity(1, dtype=np.complex128, format='csr')
+        for i in range(spins):
+            out = sps.kron(out, ops.get(i, sps.identity(2, dtype=np.complex128, format='csr')), format='csr')
+        return out
+
+    n = 2 ** spins
+    H0 = sps.csr_matrix((n, n), dtype=np.complex128)
+    for i in range(spins - 1):
+        H0 = H0 + (coupling / 2.0) * (at({i: X, i + 1: X}) + at({i: Y, i + 1: Y}))
+    H0 = sps.csr_matrix(H0)
+    H0.eliminate_zeros()                       # XX + YY cancels on the aligned pairs
+    sites = list(range(spins)) if control_sites is None else list(control_sites)
+    Hops = [sps.csr_matrix(0.5 * at({i: Z})) for i in sites]
+    Hnames = ['z%d' % i for i in sites]
+
+    def excitation(i):
+        v = np.zeros(n, dtype=np.complex128)
+        v[2 ** (spins - 1 - i)] = 1.0
+        return v
+
+    return H0, Hops, Hnames, excitation

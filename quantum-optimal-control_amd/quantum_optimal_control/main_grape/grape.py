@@ -29,10 +29,20 @@ def _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_conce
                  sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info):
     from quantum_optimal_control.helper_functions.data_management import H5File
     with H5File(file_path) as hf:
+        if _is_sparse(H0, Hops):
+            # the sparse route: every operator as CSR arrays <name>_data / _indices / _indptr, never as an n x n dataset
+            import scipy.sparse as sps
+            for name, op in [('H0', H0)] + [('Hops_%d' % i, h) for i, h in enumerate(Hops)]:
+                csr = sps.csr_matrix(op)
+                for part in ('data', 'indices', 'indptr'):
+                    hf.add(name + '_' + part, data=getattr(csr, part))
+            hf.add('state_num', data=sps.csr_matrix(H0).shape[0])
+            H0 = Hops = None
         for key, val in (('H0', H0), ('Hops', Hops), ('Hnames', Hnames), ('U', U), ('total_time', total_time),
                          ('steps', steps), ('states_concerned_list', states_concerned_list), ('use_gpu', use_gpu),
                          ('sparse_H', sparse_H), ('sparse_U', sparse_U), ('sparse_K', sparse_K)):
-            hf.add(key, data=val)
+            if val is not None:
+                hf.add(key, data=val)
         if maxA is not None:
             hf.add('maxA', data=maxA)
         if initial_guess is not None:
@@ -46,6 +56,19 @@ def _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_conce
                 group = hf.create_group(name)
                 for key, val in mapping.items():
                     group.create_dataset(key, data=val)
+
+
+def _is_sparse(H0, Hops):
+    """The drift or a control operator is a scipy.sparse matrix: the call takes the sparse state-transfer route."""
+    from quantum_optimal_control.core.sparse_parameters import is_sparse_problem
+    return is_sparse_problem(H0, Hops)
+
+
+def _sparse_call(args, kwargs):
+    """Whether a Grape call, by its positional and keyword arguments, takes the sparse route."""
+    H0 = kwargs['H0'] if 'H0' in kwargs else (args[0] if len(args) > 0 else None)
+    Hops = kwargs['Hops'] if 'Hops' in kwargs else (args[1] if len(args) > 1 else [])
+    return H0 is not None and _is_sparse(H0, Hops)
 
 
 def _is_lbfgs(args, kwargs):
@@ -88,6 +111,13 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     It pays for few, long slices and for the scipy drivers, whose line searches assume exactly that; it costs more per evaluation
     (DESIGN.md).  Works with every ``method``, with ``restarts``, ``robust``, ``transfer`` and GrapeSharded; not with ``time_comm``.
 
+    scipy.sparse Hamiltonians (sparse state transfer): when ``H0`` or any of ``Hops`` is a scipy.sparse matrix the call takes the sparse route --
+    ``state_transfer=True`` is required (ValueError otherwise), every operator is kept sparse from here to the GPU (no n x n array is formed: spin chains
+    and cavity arrays of n = 2^10 .. 2^14 levels run at their natural size), the Taylor order comes from the reference's rule for n >= 10 on the stored
+    entries, and ``save=True`` logs the operators as ``<name>_data / _indices / _indptr``.  Works with every ``method`` and with ``restarts``; not with
+    ``robust``, ``transfer``, ``exact_gradient``, ``collapse_ops``, ``time_comm``, ``dressed_info``, ``U0`` or the sharded entry points.  Dense inputs
+    behave as before (``sparse_H`` / ``sparse_U`` / ``sparse_K`` stay ignored under ``use_gpu``).
+
     ``collapse_ops`` (open-system GRAPE): a list of n x n collapse operators that carry the square root of their rates, e.g. from
     helper_functions.open_system (``relaxation``, ``dephasing``).  The pulse is then scored and optimised under the Lindblad master equation
     d rho/dt = -i [H, rho] + sum_j (C_j rho C_j^dagger - 1/2 {C_j^dagger C_j, rho}): the loss is 1 - (1/m^2) sum_ij Re Tr(sigma_ij^dagger rho_ij(T)) over
@@ -99,6 +129,19 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``transfer``, ``exact_gradient``, ``time_comm``, forbidden-level / ``speed_up`` regularisers, ``dressed_info`` or the sharded entry points."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
+    sparse = _is_sparse(H0, Hops)
+    if sparse:
+        # the sparse state-transfer route: refused before anything is built (and before the library is loaded)
+        if not state_transfer:
+            raise ValueError('Grape: scipy.sparse Hamiltonians need state_transfer=True (unitary mode propagates an n x n matrix)')
+        for name, given in (('robust', robust is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
+                            ('collapse_ops', collapse_ops is not None), ('time_comm', time_comm is not None), ('dressed_info', dressed_info is not None)):
+            if given:
+                raise ValueError('Grape: scipy.sparse Hamiltonians (sparse state transfer) do not combine with %s' % name)
+        if U0 is not None:
+            raise ValueError('Grape: scipy.sparse Hamiltonians take no U0 (state transfer starts from the given vectors)')
+        if _first_seed != 0 or plan_seeds is not None:
+            raise ValueError('Grape: scipy.sparse Hamiltonians do not run sharded (GrapeSharded)')
     if collapse_ops is not None:
         from quantum_optimal_control.helper_functions import open_system as _open
         for name, given in (('robust', robust is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
@@ -162,7 +205,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             with H5File(file_path) as hf:
                 hf.add('collapse_ops', data=np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), len(H0), len(H0)))
 
-    if U0 is None:
+    if U0 is None and not sparse:
         U0 = np.identity(len(H0))
     if convergence is None:
         convergence = {'rate': 0.01, 'update_step': 100, 'max_iterations': 5000, 'conv_target': 1e-8,
@@ -195,10 +238,15 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                 raise ValueError('Initial guess has strength > max_amp for op %d' % (row))
         sample_base = np.arcsin(ratio)
 
-    sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
-                                maxAmp, draw, None if transfer is not None else initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
-                                reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, sparse_H, sparse_U,
-                                sparse_K)
+    if sparse:
+        from quantum_optimal_control.core.sparse_parameters import SparseSystemParameters
+        sys_para = SparseSystemParameters(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, maxAmp, draw, initial_guess, show_plots,
+                                          unitary_error, reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs)
+    else:
+        sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
+                                    maxAmp, draw, None if transfer is not None else initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
+                                    reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, sparse_H, sparse_U,
+                                    sparse_K)
     # plan_seeds (extension): the batch size the engine plans its path / kernels / chunking for instead of `restarts` (None: its own batch,
     # the fastest choice for this process).  GrapeSharded passes hip_engine.plan_seeds_for(all restarts), so that a restart evolves
     # bit-identically under any rank count; Grape(restarts=R, plan_seeds=hip_engine.plan_seeds_for(R)) reproduces a sharded run in one process.
@@ -253,6 +301,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
         raise ValueError("GrapeTimeSharded: method='LBFGS' is not supported; run Grape(method='LBFGS') on one GPU")
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
+    if _sparse_call(args, kwargs):
+        raise ValueError('GrapeTimeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(...) on one GPU')
     if comm is None:
         return Grape(*args, **kwargs)
     from quantum_optimal_control.core import hip_engine
@@ -291,6 +341,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
         raise ValueError('GrapeSharded: transfer functions are not supported; run Grape(transfer=..., restarts=R) on one GPU')
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=..., restarts=R) on one GPU')
+    if _sparse_call(args, kwargs):
+        raise ValueError('GrapeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(..., restarts=R) on one GPU')
     if comm is not None:
         world, rank = comm.world, comm.rank
     elif dist is not None:
