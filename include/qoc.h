@@ -176,7 +176,7 @@ int qoc_get_member_final_unitary(qoc_handle h, double* Uf);
  *   reg_state = sum_e pi_e (forbidden levels + speed_up)_e;  loss = J - reg_state  (the value the stop rule tests: J itself without state
  *   regularisers);  reg_loss = J + the pulse regularisers;  unitary_scale stays the weights' mean.
  * With sum weights = 1, mean <= J <= max; beta = 0 (the default) is the weighted mean of qoc_create_ensemble, bit for bit, and beta -> infinity
- * the hard worst case (exp underflows to 0 on every member but the worst).  Valid on engines made by qoc_create_ensemble or qoc_create_shaped
+ * the hard worst case (exp underflows to 0 on every member but the worst).  Valid on engines made by qoc_create_ensemble, qoc_create_shaped or qoc_create_mapped
  * (QOC_ERR_STATE on any other); beta negative, NaN or infinite: QOC_ERR_INVALID.  May be called between evaluations (annealing): it waits for
  * the enqueued work and holds from the next evaluation.  The first call with beta > 0 allocates the [n_seeds][E] weights. */
 int qoc_set_risk(qoc_handle h, double beta);
@@ -208,6 +208,37 @@ int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
 /* u_f of the last evaluation, [n_seeds][k][steps] (the nominal pulse, before any member's amplitude scale).  QOC_ERR_STATE on an engine
  * not made by qoc_create_shaped. */
 int qoc_get_pulse(qoc_handle h, double* u);
+
+/* ---- control maps: the coefficients of the Hamiltonian as functions of the pulses (no counterpart in the reference, whose model is
+ * H(t) = H0 + sum_k u_k(t) H_k: each pulse multiplies exactly one operator, linearly) ---------------------------------------------------------
+ * For control set g and member e, v_j[t] is the pulse the member runs on without a map: amp_scales[e][j] maxA_j sin(base_g[j][t]), or the
+ * filtered u_f of a transfer function, j < k = cfg->k.  The trajectory's coefficient of operator i = 1 .. r is
+ *   c_i[t] = fixed[i][t] + sum_{j < k} mix[i][j][t] p_ij(v_j[t]),      p_ij(x) = sum_{d = 1 .. D} poly[i][j][d] x^d
+ * and H(t) = H0 + sum_i c_i(t) G_i plus the member's frozen perturbation rows.  This covers crosstalk (a mixing matrix), carriers and frames (a
+ * mixing matrix per slice), fixed drives and time-dependent drifts (fixed), and a nonlinear response of each line (poly); r need not equal k.
+ *   grad: dJ/dv_j[t] = sum_i dJ/dc_i[t] mix[i][j][t] p_ij'(v_j[t]), with dJ/dc the trajectories' gradient (first order, or exact with
+ *   qoc_config.gradient = 1), then the members' and the line's reduction and the tail as on every ensemble engine.
+ * The variable, maxA, the pulse regularisers, qoc_get_uks, qoc_get_pulse and both optimiser loops stay on the k pulses; loss, unitary_scale and the
+ * state regularisers are the trajectories'.  ens and transfer may each be NULL: one nominal member, no line.  Everything that works on an ensemble
+ * engine works here (qoc_set_risk, the member read-backs, gradient = 1, qoc_run_adam, qoc_run_lbfgs); AUTO plans as for an ensemble whose
+ * trajectories have r + q controls; qoc_plan_describe appends terms=r degree=D.  The identity map (r = k, D = 1, poly = I, no mix, no fixed)
+ * computes the values of the same engine without a map, bit for bit.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: a NULL map or poly; n_terms outside 1 .. 64; degree outside 1 .. 8; a
+ * non-finite entry; a pulse that reaches no operator (poly[i][j][:] or mix[i][j][:] zero for every i); and the exclusions of qoc_create_ensemble /
+ * qoc_create_shaped, with r + q in place of k + q on the paths limited to 8 controls. */
+typedef struct qoc_control_map {
+    int32_t n_terms;        /* r >= 1: Hs holds H0', G_1' .. G_r' (r + 1 operators, -i dt G_i) */
+    int32_t degree;         /* D, 1 .. 8 */
+    const double* poly;     /* [r][k][D]: alpha, powers 1 .. D */
+    const double* mix;      /* [r][k][steps] or NULL (ones) */
+    const double* fixed;    /* [r][steps] or NULL (zeros) */
+} qoc_control_map;
+/* cfg->k is the number of pulses; after map come exactly qoc_create_shaped's remaining arguments (Hs with r + 1 operators). */
+int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* transfer, const qoc_control_map* map,
+                      const double* Hs, const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out);
+/* c of member 0 of every control set at the last evaluation, [n_seeds][r][steps].  QOC_ERR_STATE on an engine not made by qoc_create_mapped. */
+int qoc_get_coefficients(qoc_handle h, double* c);
 
 /* ---- open-system GRAPE: the pulse is scored and optimised under a Lindblad master equation (no counterpart in the reference, whose graph
  * propagates state vectors) ----------------------------------------------------------------------------------------------------------------

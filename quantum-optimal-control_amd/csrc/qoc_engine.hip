@@ -28,6 +28,7 @@
 #include "qoc_small.h"
 #include "qoc_ensemble.h"
 #include "qoc_transfer.h"
+#include "qoc_control_map.h"
 #include "qoc_exact_grad.h"
 #include "qoc_lindblad.h"
 #include "qoc_sparse.h"
@@ -107,6 +108,11 @@ struct qoc_engine {
     // control in place of the time slices) and whose glue kernels apply the response matrix
     bool shaped = false;
     QocShape sh{};
+    // control map (qoc_create_mapped, csrc/qoc_control_map.h): an ensemble engine whose member glue works on the PULSE view pv (k + q rows, staging
+    // arrays for u / dLdu, the trajectories' own loss / reg_state / done); k_map_expand / k_map_reduce join it and the trajectory view (r + q rows)
+    bool mapped = false;
+    QocMap cm{};
+    QocDev pv;
     // exact gradient (qoc_config.gradient = 1, csrc/qoc_exact_grad.h): the generic path's forward, a costate-storing sweep and k_exact_grad
     QocExact xg{};
     // open-system GRAPE (qoc_create_open, csrc/qoc_lindblad.h): density operators of the pairs of states of interest under a Lindblad master equation
@@ -473,9 +479,16 @@ static int enqueue_iteration(qoc_engine* e, const QocAdamDev& ap) {
     QocDev gd = e->g;
     gd.skip_done = d.skip_done;
     const bool fused_tail = tail == TAIL_LATENCY_FUSED;
-    enqueue_controls(e, d, gd, own_controls, swap_in);
+    // a control map: the member glue reads and writes the pulse view; k_map_expand / k_map_reduce join it and the trajectories
+    QocDev pd = e->pv;
+    pd.skip_done = d.skip_done;
+    const QocDev& mv = e->mapped ? pd : d;
+    const dim3 mapg_e(grid_for((size_t)d.B * d.k * d.steps, QOC_BLOCK, 2048)), mapg_r(grid_for((size_t)d.B * e->cm.k * d.steps, QOC_BLOCK, 2048));
+    enqueue_controls(e, mv, gd, own_controls, swap_in);
+    if (e->mapped && !(skip & 1)) hipLaunchKernelGGL(k_map_expand, mapg_e, dim3(QOC_BLOCK), 0, e->stream, d, pd, e->cm);
     TRY(enqueue_trajectories(e, d, ap, tail));
-    if (e->ens_E && !(skip & 32)) enqueue_ens_reduce(e, d, gd);
+    if (e->mapped && !(skip & 32)) hipLaunchKernelGGL(k_map_reduce, mapg_r, dim3(QOC_BLOCK), 0, e->stream, d, pd, e->cm);
+    if (e->ens_E && !(skip & 32)) enqueue_ens_reduce(e, mv, gd);
     if (!fused_tail && !(skip & 32)) enqueue_tail(e, e->ens_E ? gd : d, ap, tail);
     HIP_TRY(hipGetLastError());
     e->evaluated = true;
@@ -631,6 +644,7 @@ struct EnsArgs {
     const double* one_minus_gauss;   // [k][steps] or null
     const qoc_ensemble* ens;
     const ShapeHost* shape;          // qoc_create_shaped: the response matrix and its windows, else null
+    const qoc_control_map* map;      // qoc_create_mapped: the checked map, else null
 };
 
 // the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
@@ -1017,6 +1031,23 @@ static int setup_group_view(qoc_engine* e, const EnsArgs& a) {
         TRY(dev_alloc(e, &sh.uf, (size_t)G * kg * steps));
         e->shaped = true;
     }
+    if (const qoc_control_map* cm = a.map) {
+        // the pulse view and the map's arrays: the trajectories have r + q rows, the members' pulses k + q
+        const int r = cm->n_terms, D = cm->degree;
+        const size_t stage = (size_t)G * E * (kg + q) * steps;
+        QocDev& pv = e->pv;
+        pv = e->d;
+        pv.k = kg + q;
+        pv.u = nullptr; pv.dLdu = nullptr;
+        TRY(dev_zalloc(e, &pv.u, stage, "qoc_create_mapped"));
+        TRY(dev_zalloc(e, &pv.dLdu, stage, "qoc_create_mapped"));
+        pv.w = pv.w2 = pv.u2 = pv.grad = pv.base = nullptr;
+        e->cm = QocMap{r, D, kg, q, nullptr, nullptr, nullptr};
+        TRY(dev_upload(e, &e->cm.alpha, cm->poly, (size_t)r * kg * D));
+        if (cm->mix) TRY(dev_upload(e, &e->cm.M, cm->mix, (size_t)r * kg * steps));
+        if (cm->fixed) TRY(dev_upload(e, &e->cm.F, cm->fixed, (size_t)r * steps));
+        e->mapped = true;
+    }
     return QOC_OK;
 }
 
@@ -1228,9 +1259,10 @@ int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double
     return create_engine(cfg, Problem{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh}, nullptr, out);
 }
 
-// qoc_create_ensemble and qoc_create_shaped (`who` names the caller in the messages; shape: the prepared response of the latter, else null)
+// qoc_create_ensemble, qoc_create_shaped and qoc_create_mapped (`who` names the caller in the messages; shape: the prepared response of a line,
+// else null; map: the checked control map of the last, else null -- the trajectories then run its r operators in place of the k pulses')
 static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, Problem p,
-                          qoc_handle* out) {
+                          qoc_handle* out, const qoc_control_map* map = nullptr) {
     if (!cfg || !ens || !p.Hs || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int E = ens->members, q = ens->n_perturb;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
@@ -1250,23 +1282,26 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
         "inside its launch, where the members' gradients cannot be reduced first", who);
     if (cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
         "%s: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail", who);
-    if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && cfg->k + q > 8) return fail(QOC_ERR_INVALID,
-        "%s: path %d is limited to 8 controls; the ensemble's trajectories have k + q = %d", who, cfg->path, cfg->k + q);
+    // (a control map: the trajectories run the r operators the map feeds)
+    const int kt = map ? map->n_terms : cfg->k;
+    if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && kt + q > 8) return fail(QOC_ERR_INVALID,
+        "%s: path %d is limited to 8 controls; the ensemble's trajectories have %s + q = %d", who, cfg->path, map ? "r" : "k", kt + q);
     // the trajectories: G E of them, k + q controls (the perturbations are frozen control rows), no pulse regulariser (the group view has them)
     qoc_config tc = *cfg;
     const int n = cfg->n, k = cfg->k;
     const size_t nn = (size_t)n * n;
-    tc.k = k + q;
+    tc.k = kt + q;
     tc.n_seeds = cfg->n_seeds * E;
     tc.plan_seeds = cfg->plan_seeds > 0 ? cfg->plan_seeds * E : 0;
     tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
     tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
-    std::vector<double> Hst(2 * nn * (size_t)(k + q + 1));
-    memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(k + 1) * sizeof(double));
-    if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(k + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
-    std::vector<double> maxAt(p.maxA, p.maxA + k);
-    maxAt.resize((size_t)(k + q), 1.0);
-    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape};
+    std::vector<double> Hst(2 * nn * (size_t)(kt + q + 1));
+    memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(kt + 1) * sizeof(double));
+    if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(kt + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
+    // (no trajectory kernel of an ensemble forms controls from maxA: the rows of a mapped engine carry ones)
+    std::vector<double> maxAt(p.maxA, p.maxA + (map ? 0 : k));
+    maxAt.resize((size_t)(kt + q), 1.0);
+    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape, map};
     p.Hs = Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
     return create_engine(&tc, p, &ea, out);
 }
@@ -1278,42 +1313,86 @@ int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const do
     return create_members("qoc_create_ensemble", nullptr, cfg, ens, p, out);
 }
 
-int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
-                      const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                      const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    if (!cfg || !tr || !maxA) return fail(QOC_ERR_INVALID, "qoc_create_shaped: null argument");
-    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "qoc_create_shaped: k, steps must be >= 1");
-    const int P = tr->n_samples, steps = cfg->steps, k = cfg->k;
-    if (P < 1) return fail(QOC_ERR_INVALID, "qoc_create_shaped: n_samples = %d (>= 1)", P);
-    if (!tr->T) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the response matrix is missing");
-    if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "qoc_create_shaped: the envelope regulariser is defined per time slice, not per sample");
+// qoc_create_shaped and qoc_create_mapped (`who`): the response matrix prepared (tr may be null under a map: no line), one nominal member
+// where there is no ensemble, the checked control map handed on
+static int create_shaped(const char* who, const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map,
+                         const Problem& p, qoc_handle* out) {
+    if (!cfg || (!tr && !map) || !p.maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "%s: k, steps must be >= 1", who);
+    const int steps = cfg->steps, k = cfg->k;
+    // no ensemble: one nominal member
+    const std::vector<double> ones((size_t)k + 1, 1.0);
+    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
+    if (!tr) return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out, map);
+    const int P = tr->n_samples;
+    if (P < 1) return fail(QOC_ERR_INVALID, "%s: n_samples = %d (>= 1)", who, P);
+    if (!tr->T) return fail(QOC_ERR_INVALID, "%s: the response matrix is missing", who);
+    if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "%s: the envelope regulariser is defined per time slice, not per sample", who);
     // the response: finite, every sample reaches the pulse; the nonzero window of every row and column and the transposed copy
     ShapeHost sh{P, 0, 0, std::vector<double>((size_t)P * steps), std::vector<int2>((size_t)steps, make_int2(0, 0)),
                  std::vector<int2>((size_t)P, make_int2(0, 0))};
     for (int t = 0; t < steps; ++t)
-        for (int p = 0; p < P; ++p) {
-            const double v = tr->T[(size_t)t * P + p];
-            if (!std::isfinite(v)) return fail(QOC_ERR_INVALID, "qoc_create_shaped: T[%d][%d] is not finite", t, p);
-            sh.Tt[(size_t)p * steps + t] = v;
+        for (int s = 0; s < P; ++s) {
+            const double v = tr->T[(size_t)t * P + s];
+            if (!std::isfinite(v)) return fail(QOC_ERR_INVALID, "%s: T[%d][%d] is not finite", who, t, s);
+            sh.Tt[(size_t)s * steps + t] = v;
             if (v != 0.0) {
                 int2& r = sh.row_win[t];
-                int2& c = sh.col_win[p];
-                if (r.x == r.y) r.x = p;
-                r.y = p + 1;
+                int2& c = sh.col_win[s];
+                if (r.x == r.y) r.x = s;
+                r.y = s + 1;
                 if (c.x == c.y) c.x = t;
                 c.y = t + 1;
             }
         }
-    for (int p = 0; p < P; ++p) {
-        if (sh.col_win[p].x == sh.col_win[p].y) return fail(QOC_ERR_INVALID, "qoc_create_shaped: column %d of T is zero (the sample never reaches the pulse)", p);
-        sh.col_band = std::max(sh.col_band, sh.col_win[p].y - sh.col_win[p].x);
+    for (int s = 0; s < P; ++s) {
+        if (sh.col_win[s].x == sh.col_win[s].y) return fail(QOC_ERR_INVALID, "%s: column %d of T is zero (the sample never reaches the pulse)", who, s);
+        sh.col_band = std::max(sh.col_band, sh.col_win[s].y - sh.col_win[s].x);
     }
     for (int t = 0; t < steps; ++t) sh.band = std::max(sh.band, sh.row_win[t].y - sh.row_win[t].x);
-    // no ensemble: one nominal member
-    const std::vector<double> ones((size_t)k + 1, 1.0);
-    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
-    return create_members("qoc_create_shaped", &sh, cfg, ens ? ens : &nominal, p, out);
+    return create_members(who, &sh, cfg, ens ? ens : &nominal, p, out, map);
+}
+
+int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
+                      const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                      const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!tr) return fail(QOC_ERR_INVALID, "qoc_create_shaped: null argument");
+    return create_shaped("qoc_create_shaped", cfg, ens, tr, nullptr, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs},
+                         out);
+}
+
+// the map is checked here, on the host and before any device is touched: ranges, finite entries, every pulse reaches an operator
+int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs,
+                      const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    const char* who = "qoc_create_mapped";
+    if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    if (!map) return fail(QOC_ERR_INVALID, "%s: the control map is missing", who);
+    if (!map->poly) return fail(QOC_ERR_INVALID, "%s: the map's polynomial coefficients (poly) are missing", who);
+    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "%s: k, steps must be >= 1", who);
+    const int r = map->n_terms, D = map->degree, k = cfg->k, steps = cfg->steps;
+    if (r < 1 || r > QOC_MAP_MAX_TERMS) return fail(QOC_ERR_INVALID, "%s: n_terms = %d (1 .. %d operators)", who, r, QOC_MAP_MAX_TERMS);
+    if (D < 1 || D > QOC_MAP_MAX_DEGREE) return fail(QOC_ERR_INVALID, "%s: degree = %d (1 .. %d)", who, D, QOC_MAP_MAX_DEGREE);
+    for (size_t i = 0; i < (size_t)r * k * D; ++i)
+        if (!std::isfinite(map->poly[i])) return fail(QOC_ERR_INVALID, "%s: poly[%zu][%zu][%zu] is not finite", who, i / ((size_t)k * D), (i / D) % k, i % D);
+    if (map->mix)
+        for (size_t i = 0; i < (size_t)r * k * steps; ++i)
+            if (!std::isfinite(map->mix[i]))
+                return fail(QOC_ERR_INVALID, "%s: mix[%zu][%zu][%zu] is not finite", who, i / ((size_t)k * steps), (i / steps) % k, i % steps);
+    if (map->fixed)
+        for (size_t i = 0; i < (size_t)r * steps; ++i)
+            if (!std::isfinite(map->fixed[i])) return fail(QOC_ERR_INVALID, "%s: fixed[%zu][%zu] is not finite", who, i / steps, i % steps);
+    for (int j = 0; j < k; ++j) {
+        bool reaches = false;
+        for (int i = 0; i < r && !reaches; ++i) {
+            bool poly = false, mix = !map->mix;
+            for (int d = 0; d < D; ++d) poly = poly || map->poly[((size_t)i * k + j) * D + d] != 0.0;
+            for (int t = 0; t < steps && !mix; ++t) mix = map->mix[((size_t)i * k + j) * steps + t] != 0.0;
+            reaches = poly && mix;
+        }
+        if (!reaches) return fail(QOC_ERR_INVALID, "%s: pulse %d reaches no operator (poly[i][%d] or mix[i][%d] is zero for every i)", who, j, j, j);
+    }
+    return create_shaped(who, cfg, ens, tr, map, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1535,6 +1614,18 @@ int qoc_get_pulse(qoc_handle e, double* u) {
     // (k_shape_expand stores the nominal pulse of every evaluation beside the trajectories' scaled copies)
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(u, e->sh.uf, (size_t)e->g.B * e->g.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
+int qoc_get_coefficients(qoc_handle e, double* c) {
+    CHECK_H(e);
+    if (!e->mapped) return fail(QOC_ERR_STATE, "qoc_get_coefficients: not a mapped engine (qoc_create_mapped)");
+    if (!c) return fail(QOC_ERR_INVALID, "qoc_get_coefficients: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_coefficients: nothing evaluated yet");
+    // (the first r rows of member 0's trajectory: what k_map_expand wrote for the last evaluation)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t row = (size_t)e->cm.r * e->d.steps * sizeof(double), pitch = (size_t)e->ens_E * e->d.k * e->d.steps * sizeof(double);
+    HIP_TRY(hipMemcpy2D(c, row, e->d.u, pitch, row, (size_t)e->g.B, hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1766,6 +1857,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     // ensemble engines only (the plain engines' line stays as it was)
     if (e->ens_E) add(" members=%d perturbations=%d", e->ens_E, e->en.q);
     if (e->shaped) add(" samples=%d band=%d", e->sh.P, e->sh.band);
+    if (e->mapped) add(" terms=%d degree=%d", e->cm.r, e->cm.D);
     add(" gradient=%s", e->xg.on ? "exact" : "first_order");
     // exact engines only: where k_exact_grad keeps its generator and vector blocks, its dynamic LDS and its grid (qoc_exact_plan)
     if (e->xg.on) add(" exact_variant=%s exact_lds=%zu exact_grid=%d", e->xg.lds ? "lds" : "global", e->xg.lds_bytes, e->xg.grid);

@@ -41,6 +41,11 @@ class QocTransfer(C.Structure):
     _fields_ = [('n_samples', C.c_int32), ('T', C.POINTER(C.c_double))]
 
 
+class QocControlMap(C.Structure):
+    _fields_ = [('n_terms', C.c_int32), ('degree', C.c_int32), ('poly', C.POINTER(C.c_double)), ('mix', C.POINTER(C.c_double)),
+                ('fixed', C.POINTER(C.c_double))]
+
+
 class QocOpen(C.Structure):
     _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double))]
 
@@ -70,6 +75,9 @@ _SIGNATURES = {
                                       C.POINTER(C.c_void_p)]),
     'qoc_create_shaped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP,
                                     _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_mapped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), C.POINTER(QocControlMap), _DP, _DP, _DP,
+                                    _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_get_coefficients': (C.c_int, [C.c_void_p, _DP]),
     'qoc_create_open': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocOpen), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
@@ -356,13 +364,26 @@ class HipEngine(object):
     (pass Hs=None, U0=None).  State transfer only; the engine keeps every operator in ELLPACK and never forms an n x n array, so n = 2^14 and more
     fit.  vector_home: None / 'auto', 'lds' or 'global' (where the Taylor chain's two vectors live; A/B runs and tests).  Every other entry point
     works as on a dense state-transfer engine.  Combines with none of ensemble, transfer, exact_gradient, collapse_ops, Vs or time sharding, and
-    only with path AUTO or PATH_SPARSE (ValueError, before the library is loaded)."""
+    only with path AUTO or PATH_SPARSE (ValueError, before the library is loaded).
+
+    control_map (include/qoc.h qoc_create_mapped): a helper_functions.control_map.ControlMap (or a dict alpha / mix / fixed).  Hs then holds the drift
+    and the r operators the map feeds, maxA (and one_minus_gauss, the variable, the gradient, get_uks) the k pulses: self.k is the number of pulses,
+    self.terms the number of operators.  get_coefficients() gives the (n_seeds, r, steps) coefficients the nominal member's trajectories ran on.
+    Composes with ensemble, transfer and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is
+    loaded)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
-                 sparse_ops=None, vector_home=None):
+                 sparse_ops=None, vector_home=None, control_map=None):
         sparse = None
+        if control_map is not None:
+            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
+                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
+                if given:
+                    raise ValueError('HipEngine: control_map does not combine with %s' % name)
+            from quantum_optimal_control.helper_functions import control_map as _cmap
+            control_map = _cmap.validate(control_map, k=np.shape(maxA)[0], r=np.shape(Hs)[0] - 1, steps=steps)
         if sparse_ops is not None:
             for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
                                 ('collapse_ops', collapse_ops is not None), ('time sharding', time_comm is not None or int(time_shards) > 0),
@@ -387,13 +408,14 @@ class HipEngine(object):
         self._h = C.c_void_p()
         if sparse is None:
             Hs = np.ascontiguousarray(np.asarray(Hs, dtype=np.complex128))
-            k = Hs.shape[0] - 1
+            k = Hs.shape[0] - 1 if control_map is None else control_map.n_pulses
             n = Hs.shape[1]
         else:
             k, n = len(sparse_ops) - 1, sparse[0]
         V = np.ascontiguousarray(np.asarray(V, dtype=np.complex128))
         m = V.shape[1]
         self.n, self.k, self.m, self.steps, self.n_seeds = n, k, m, int(steps), int(n_seeds)
+        self.terms = k if control_map is None else control_map.n_terms      # operators beside the drift (a control map: what it feeds)
         self.state_transfer = bool(state_transfer)
         W = _c128(W, (n, m))
         U0a = None if U0 is None else _c128(U0, (n, n))
@@ -439,7 +461,21 @@ class HipEngine(object):
             ens.offsets = _dp(off) if P.shape[0] else None
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
-        if sparse is not None:
+        tr = None
+        if transfer is not None and control_map is not None:
+            T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
+            if T.ndim != 2 or T.shape[0] != int(steps):
+                raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
+            tr = QocTransfer()
+            tr.n_samples, tr.T = T.shape[1], _dp(T)
+        if control_map is not None:
+            cmap = QocControlMap()
+            cmap.n_terms, cmap.degree = control_map.n_terms, control_map.degree
+            cmap.poly, cmap.mix, cmap.fixed = _dp(control_map.alpha), _dp(control_map.mix), _dp(control_map.fixed)
+            _check(lib.qoc_create_mapped(C.byref(cfg), None if ens is None else C.byref(ens), None if tr is None else C.byref(tr), C.byref(cmap), *args))
+            if tr is not None:
+                self.samples = int(tr.n_samples)
+        elif sparse is not None:
             _, indptr, row, col, val = sparse
             sp = QocSparse()
             sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
@@ -578,6 +614,12 @@ class HipEngine(object):
         """Transfer-function engines: the (n_seeds, k, steps) pulse u_f = maxA T sin(base) the last evaluation ran on."""
         out = np.empty((self.n_seeds, self.k, self.steps))
         _check(self._lib.qoc_get_pulse(self._h, _dp(out)))
+        return out
+
+    def get_coefficients(self):
+        """Mapped engines: the (n_seeds, r, steps) coefficients c of the operators, as member 0's trajectories ran them in the last evaluation."""
+        out = np.empty((self.n_seeds, self.terms, self.steps))
+        _check(self._lib.qoc_get_coefficients(self._h, _dp(out)))
         return out
 
     def get_final_unitary(self):

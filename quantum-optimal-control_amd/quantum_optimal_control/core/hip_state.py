@@ -12,7 +12,7 @@ from quantum_optimal_control.core import hip_engine
 class HipState(object):
 
     def __init__(self, sys_para, n_seeds=1, device=0, path=hip_engine.PATH_AUTO, chunks=0, first_seed=0, plan_seeds=0, time_comm=None, ensemble=None, transfer=None,
-                 exact_gradient=False, collapse_ops=None):
+                 exact_gradient=False, collapse_ops=None, control_map=None):
         self.sys_para = sys_para
         self.n_seeds = n_seeds
         self.first_seed = first_seed      # global index of this engine's first restart (seed-sharded runs)
@@ -25,6 +25,7 @@ class HipState(object):
         self.transfer = transfer          # transfer-function GRAPE: the steps x P response matrix, or None (sys_para.ops_weight_base is then k x P)
         self.exact_gradient = bool(exact_gradient)   # qoc_config.gradient: the derivative of the computed propagators instead of the first-order formula
         self.collapse_ops = collapse_ops  # open-system GRAPE: the validated list of collapse operators (helper_functions/open_system.py), or None
+        self.control_map = control_map    # control map: the validated helper_functions.control_map.ControlMap, or None (sys_para.ops_c are then the r operators it feeds)
         self.engine = None
 
     def build_graph(self):
@@ -50,7 +51,7 @@ class HipState(object):
             n_seeds=self.n_seeds, device=self.device, path=self.path, chunks=self.chunks, plan_seeds=self.plan_seeds,
             time_shards=0 if self.time_comm is None else self.time_comm.world, time_rank=-1 if self.time_comm is None else self.time_comm.rank,
             time_comm=self.time_comm, ensemble=self.ensemble, transfer=self.transfer, exact_gradient=self.exact_gradient,
-            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops)
+            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops, control_map=self.control_map)
         base = np.asarray(sp.ops_weight_base, dtype=np.float64)
         if base.ndim == 2 and (self.n_seeds > 1 or self.first_seed > 0):
             # global restart 0 = the reference's own starting point; restart g > 0 = the reproducible stream of index g,

@@ -232,7 +232,7 @@ class run_session(object):
 
     # ---- scipy drivers ------------------------------------------------------------------------------------------
     def minimize_opt_fun(self, x):
-        k = len(self.sys_para.ops_c)
+        k = self.engine.k                                  # (the pulses: with a control map not the number of operators)
         self.l, self.rl, self.grads, self.metric, self.g_squared = self.get_error(np.reshape(x, (k, len(x) // k)))
         if self.l < self.conv.conv_target:
             self.conv_time = time.time() - self.start_time
@@ -262,7 +262,7 @@ class run_session(object):
         else:
             options = {'gtol': self.conv.min_grad, 'disp': False, 'maxiter': self.conv.max_iterations}
         res = minimize(self.minimize_opt_fun, x0, method=method, jac=jac, options=options)
-        k = len(self.sys_para.ops_c)
+        k = self.engine.k                                  # (the pulses: with a control map not the number of operators)
         self.l, self.rl, self.grads, self.metric, self.g_squared = self.get_error(np.reshape(res['x'], (k, len(res['x']) // k)))
         print(self.method + ' optimization done')
         if not self.sys_para.show_plots:

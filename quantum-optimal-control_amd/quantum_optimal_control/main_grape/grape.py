@@ -26,7 +26,7 @@ def _next_free_log(data_path, file_name):
 
 
 def _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_concerned_list, use_gpu, sparse_H,
-                 sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info):
+                 sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info, control_map=None):
     from quantum_optimal_control.helper_functions.data_management import H5File
     with H5File(file_path) as hf:
         if _is_sparse(H0, Hops):
@@ -48,6 +48,12 @@ def _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_conce
         if initial_guess is not None:
             hf.add('initial_guess', data=initial_guess)
         hf.add('method', method)
+        if control_map is not None:
+            # a control map (Hops are then the operators it feeds): alpha always, mix and fixed where the map has them
+            hf.add('control_map_alpha', data=control_map.alpha)
+            for key in ('mix', 'fixed'):
+                if getattr(control_map, key) is not None:
+                    hf.add('control_map_' + key, data=getattr(control_map, key))
         group = hf.create_group('convergence')
         for key, val in convergence.items():          # like the reference this needs a dict when save=True
             group.create_dataset(key, data=val)
@@ -81,7 +87,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, control_map=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -126,7 +132,15 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ends in, ``rho_final[i, j]`` the propagated coherence psi_i psi_j^dagger.  Taylor order and sub-steps come from
     open_system.choose_taylor unless ``Taylor_terms=(T, s)`` is given (degree T, 2^s sub-steps per slice, in both modes).  Works with every
     ``method`` (``'EVOLVE'`` with ``initial_guess=uks`` scores an existing pulse under decay) and with ``restarts``; not with ``robust``,
-    ``transfer``, ``exact_gradient``, ``time_comm``, forbidden-level / ``speed_up`` regularisers, ``dressed_info`` or the sharded entry points."""
+    ``transfer``, ``exact_gradient``, ``time_comm``, forbidden-level / ``speed_up`` regularisers, ``dressed_info`` or the sharded entry points.
+
+    ``control_map`` (control maps): a helper_functions.control_map.ControlMap -- the coefficients of the Hamiltonian as functions of the pulses,
+    c_i[t] = F[i, t] + sum_j M[i, j, t] p_ij(v_j[t]) with polynomials p_ij: crosstalk between lines, carriers, fixed drives, a compressing amplifier
+    (``linear``, ``carriers``, ``fixed``, ``polynomial`` and their combinations).  ``Hops`` are then the r operators the map feeds, while ``Hnames``,
+    ``maxA`` and ``initial_guess`` have one entry per pulse (k of them, r need not equal k) and the returned uks is k x steps; afterwards
+    ``control_map.coefficients`` holds the r x steps coefficients the nominal Hamiltonian ran on.  The pulse regularisers act on the pulses, the
+    Taylor order is chosen for the largest coefficients the map can deliver.  Works with every ``method``, with ``restarts``, ``robust``,
+    ``transfer`` and ``exact_gradient``; not with ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm`` or the sharded entry points."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     sparse = _is_sparse(H0, Hops)
@@ -154,6 +168,22 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if _first_seed != 0 or plan_seeds is not None:
             raise ValueError('Grape: collapse_ops (open-system GRAPE) does not run sharded (GrapeSharded)')
         collapse_ops = _open.validate(collapse_ops, len(H0))
+    n_pulses = len(Hops)
+    if control_map is not None:
+        # control maps: refused before anything is built (and before the library is loaded)
+        from quantum_optimal_control.helper_functions import control_map as _cmap
+        for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('scipy.sparse Hamiltonians (sparse state transfer)', sparse),
+                            ('time_comm', time_comm is not None)):
+            if given:
+                raise ValueError('Grape: control_map does not combine with %s' % name)
+        if _first_seed != 0 or plan_seeds is not None:
+            raise ValueError('Grape: control_map does not run sharded (GrapeSharded)')
+        _given_map = control_map                       # (validate returns a normalised copy: the caller's object gets .coefficients)
+        control_map = _cmap.validate(control_map, r=len(Hops), steps=steps)
+        n_pulses = control_map.n_pulses
+        for name, seq in (('Hnames', Hnames), ('maxA', maxA), ('initial_guess', None if transfer is not None else initial_guess)):
+            if seq is not None and len(seq) != n_pulses:
+                raise ValueError('Grape: with a control map %s has one entry per pulse (%d), got %d' % (name, n_pulses, len(seq)))
     if str(method).upper() == 'LBFGS' and time_comm is not None:
         raise ValueError("Grape: method='LBFGS' cannot be time-sharded (time_comm)")
     if exact_gradient and time_comm is not None:
@@ -162,7 +192,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         from quantum_optimal_control.helper_functions import robust as _robust
         if time_comm is not None:
             raise ValueError('Grape: robust ensembles cannot be time-sharded (time_comm)')
-        robust = _robust.validate(robust, len(H0), len(Hops))
+        robust = _robust.validate(robust, len(H0), n_pulses)
     if transfer is not None:
         from quantum_optimal_control.helper_functions import transfer as _transfer
         if time_comm is not None:
@@ -182,7 +212,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         file_path = _next_free_log(data_path, file_name)
         print("data saved at: " + str(file_path))
         _dump_inputs(file_path, H0, Hops, Hnames, U, total_time, steps, states_concerned_list, use_gpu, sparse_H,
-                     sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info)
+                     sparse_U, sparse_K, maxA, initial_guess, method, convergence, reg_coeffs, dressed_info, control_map=control_map)
         if robust is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -212,11 +242,15 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                        'learning_rate_decay': 2500}
     if maxA is None:
         if initial_guess is None:
-            maxAmp = 4 * np.ones(len(Hops))
+            maxAmp = 4 * np.ones(n_pulses)
         else:
-            maxAmp = 1.5 * np.max(np.abs(initial_guess)) * np.ones(len(Hops))
+            maxAmp = 1.5 * np.max(np.abs(initial_guess)) * np.ones(n_pulses)
     else:
         maxAmp = maxA
+
+    if control_map is not None and Taylor_terms is None:
+        # the chooser on (H0, Hops, cmax): the largest coefficients the map can deliver stand where maxA stands (every member's, with a robust ensemble)
+        Taylor_terms = _cmap.choose_taylor(control_map, H0, Hops, robust, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
 
     if robust is not None and Taylor_terms is None:
         # the largest Taylor order and squaring count any member's own problem would get (both only lower the truncation error)
@@ -229,9 +263,9 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     if transfer is not None and initial_guess is not None:
         # sample amplitudes -> the variable, by the reference's rule for a pulse (core/system_parameters.py: base = arcsin(u / maxA))
         guess = np.asarray(initial_guess, dtype=np.float64)
-        if guess.shape != (len(Hops), transfer.n_samples):
+        if guess.shape != (n_pulses, transfer.n_samples):
             raise ValueError('Grape: with a transfer function the initial guess is (%d, %d) sample amplitudes, got %s'
-                             % (len(Hops), transfer.n_samples, guess.shape))
+                             % (n_pulses, transfer.n_samples, guess.shape))
         ratio = guess / np.asarray(maxAmp, dtype=np.float64)[:, None]
         for row in range(len(ratio)):
             if max(ratio[row]) > 1.0:
@@ -242,6 +276,19 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         from quantum_optimal_control.core.sparse_parameters import SparseSystemParameters
         sys_para = SparseSystemParameters(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, maxAmp, draw, initial_guess, show_plots,
                                           unitary_error, reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs)
+    elif control_map is not None:
+        # SystemParameters counts controls by the operators; with a map the variable, maxA, the envelope and the names belong to the k pulses.  It is
+        # built for the r operators (Taylor order fixed above, no guess, the NumPy RNG left where it was) and the pulse side is then set in its place
+        rng_state = np.random.get_state()
+        sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
+                                    _cmap.coefficient_bounds(control_map, maxAmp), draw, None, show_plots, unitary_error, state_transfer, no_scaling,
+                                    reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, sparse_H, sparse_U, sparse_K)
+        np.random.set_state(rng_state)
+        sys_para.ops_max_amp = maxAmp
+        sys_para.ops_len = n_pulses
+        sys_para._build_envelope()
+        sys_para._transform_guess(None if transfer is not None else initial_guess)
+        sys_para._build_guess()
     else:
         sys_para = SystemParameters(H0, Hops, Hnames, U, U0, total_time, steps, states_concerned_list, dressed_info,
                                     maxAmp, draw, None if transfer is not None else initial_guess, show_plots, unitary_error, state_transfer, no_scaling,
@@ -255,19 +302,21 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         # the variable is k x P; drawn after SystemParameters' own draw, so that calls without a transfer keep their RNG stream
         P = transfer.n_samples
         if sample_base is None:
-            sample_base = np.random.normal(0, 1. / np.sqrt(P), [len(Hops), P])
+            sample_base = np.random.normal(0, 1. / np.sqrt(P), [n_pulses, P])
         sys_para.ops_weight_base = sample_base
         sys_para.raw_shape = np.shape(sample_base)
     tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
                    plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust,
                    transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient),
-                   collapse_ops=collapse_ops)   # constants -> HBM
+                   collapse_ops=collapse_ops, control_map=control_map)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
         SS = run_session(tfs, graph, conv, sys_para, method, show_plots=sys_para.show_plots, use_gpu=use_gpu)
         if transfer is not None:
             transfer.samples = np.array(SS.samples)
+        if control_map is not None:
+            _given_map.coefficients = control_map.coefficients = np.array(tfs.engine.get_coefficients()[int(SS.seed)])
         if _restart_info is not None:
             # (a dict to fill: every control set's final scalars and variable, read before the engine goes -- examples/lbfgs_restarts.py)
             _restart_info.update(tfs.engine.scalars(), base=tfs.engine.get_base(), best=int(SS.seed))
@@ -301,6 +350,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
         raise ValueError("GrapeTimeSharded: method='LBFGS' is not supported; run Grape(method='LBFGS') on one GPU")
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
+    if kwargs.get('control_map') is not None:
+        raise ValueError('GrapeTimeSharded: control_map (control maps) is not supported; run Grape(control_map=...) on one GPU')
     if _sparse_call(args, kwargs):
         raise ValueError('GrapeTimeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(...) on one GPU')
     if comm is None:
@@ -341,6 +392,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
         raise ValueError('GrapeSharded: transfer functions are not supported; run Grape(transfer=..., restarts=R) on one GPU')
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=..., restarts=R) on one GPU')
+    if kwargs.get('control_map') is not None:
+        raise ValueError('GrapeSharded: control_map (control maps) is not supported; run Grape(control_map=..., restarts=R) on one GPU')
     if _sparse_call(args, kwargs):
         raise ValueError('GrapeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(..., restarts=R) on one GPU')
     if comm is not None:
