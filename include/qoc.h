@@ -240,6 +240,28 @@ int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
 /* c of member 0 of every control set at the last evaluation, [n_seeds][r][steps].  QOC_ERR_STATE on an engine not made by qoc_create_mapped. */
 int qoc_get_coefficients(qoc_handle h, double* c);
 
+/* ---- device fleets: one pulse per device, for F devices that differ in their member tables (no counterpart in the reference) ------------------
+ * Device f is an ensemble of E members: member e has the drift H0 + sum_q offsets[f][e][q] P_q and the controls amp_scales[f][e][j] H_j.  The
+ * devices share P, the weights, the risk, U0, V, W, maxA, the regularisers, the line and the control map.  cfg->n_seeds = F R control sets,
+ * device-major: control set g belongs to device g / R and is its restart g % R.  Per control set every quantity -- loss, reg_loss, grad,
+ * unitary_scale, the risk objective and its tilted weights, the stop rule -- is what qoc_create_ensemble, qoc_create_shaped or qoc_create_mapped
+ * (whichever transfer and map select) defines for an ensemble with that device's rows; nothing couples control sets.  ens supplies members,
+ * n_perturb, P and weights (its offsets and amp_scales are not read); ens NULL: one member per device, no perturbation.  Every read-back keeps
+ * its [n_seeds] shape, the member read-backs and qoc_set_risk work as on an ensemble, and qoc_plan_describe appends devices=F.  AUTO plans as
+ * for n_seeds x E trajectories.  A fleet of one device computes the values of the ensemble engine with the same rows, bit for bit.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: a NULL fleet or amp_scales; NULL offsets with n_perturb > 0;
+ * devices < 1; n_seeds no multiple of devices; a non-finite entry; and every exclusion of the ensemble's entry points. */
+typedef struct qoc_fleet {
+    int32_t devices;            /* F >= 1; cfg->n_seeds must be a multiple of it */
+    const double* offsets;      /* [F][E][q] (may be NULL when q = 0) */
+    const double* amp_scales;   /* [F][E][k] */
+} qoc_fleet;
+/* transfer and map may each be NULL; after map come exactly qoc_create_mapped's remaining arguments. */
+int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* transfer,
+                     const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
+                     const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs,
+                     qoc_handle* out);
+
 /* ---- open-system GRAPE: the pulse is scored and optimised under a Lindblad master equation (no counterpart in the reference, whose graph
  * propagates state vectors) ----------------------------------------------------------------------------------------------------------------
  * Collapse operators C_j are n x n and carry the square root of their rates; the caller passes D_j = sqrt(dt) C_j.  With H' = -i dt H as in Hs:

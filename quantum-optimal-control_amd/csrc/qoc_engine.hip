@@ -98,6 +98,7 @@ struct qoc_engine {
     // robust ensemble (qoc_create_ensemble, csrc/qoc_ensemble.h): d is then the TRAJECTORY view (G E trajectories, k + q controls, read by
     // the heavy kernels) and g the GROUP view (G control sets, k controls: variable, Adam slots, stop rule, pulse regularisers, the tail)
     int ens_E = 0;
+    int fleet_F = 0;                // qoc_create_fleet: devices, each with its own member table (en.R control sets per device); else 0
     QocDev g;
     QocEns en{};
     std::vector<double> ens_wt;     // host copy of the weights (unitary_scale of a group is formed on read-back)
@@ -645,6 +646,7 @@ struct EnsArgs {
     const qoc_ensemble* ens;
     const ShapeHost* shape;          // qoc_create_shaped: the response matrix and its windows, else null
     const qoc_control_map* map;      // qoc_create_mapped: the checked map, else null
+    const qoc_fleet* fleet;          // qoc_create_fleet: the checked member tables of the F devices (in place of ens' offsets and amp_scales), else null
 };
 
 // the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
@@ -1017,10 +1019,13 @@ static int setup_group_view(qoc_engine* e, const EnsArgs& a) {
     TRY(alloc_set_arrays(e, gv, "qoc_create_ensemble", true));
     TRY(alloc_set_scalars(e, gv, "qoc_create_ensemble", "qoc_create_ensemble: the bandpass phase table could not be formed"));
     const double* da = nullptr; const double* dd = nullptr; const double* dw = nullptr;
-    TRY(dev_upload(e, &da, en.amp_scales, (size_t)E * kg));
-    if (q > 0) TRY(dev_upload(e, &dd, en.offsets, (size_t)E * q));
+    // the member tables: one block per device of a fleet, else one block that every control set reads
+    const int F = a.fleet ? a.fleet->devices : 1;
+    TRY(dev_upload(e, &da, a.fleet ? a.fleet->amp_scales : en.amp_scales, (size_t)F * E * kg));
+    if (q > 0) TRY(dev_upload(e, &dd, a.fleet ? a.fleet->offsets : en.offsets, (size_t)F * E * q));
     TRY(dev_upload(e, &dw, en.weights, (size_t)E));
-    e->en = QocEns{E, q, da, dd, dw};
+    e->en = QocEns{E, q, G / F, da, dd, dw};
+    e->fleet_F = a.fleet ? F : 0;
     e->ens_wt.assign(en.weights, en.weights + E);
     if (const ShapeHost* shp = a.shape) {
         QocShape& sh = e->sh;
@@ -1261,12 +1266,13 @@ int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double
 
 // qoc_create_ensemble, qoc_create_shaped and qoc_create_mapped (`who` names the caller in the messages; shape: the prepared response of a line,
 // else null; map: the checked control map of the last, else null -- the trajectories then run its r operators in place of the k pulses')
+// (fleet: the checked tables of qoc_create_fleet, read in place of ens' offsets and amp_scales)
 static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, Problem p,
-                          qoc_handle* out, const qoc_control_map* map = nullptr) {
+                          qoc_handle* out, const qoc_control_map* map = nullptr, const qoc_fleet* fleet = nullptr) {
     if (!cfg || !ens || !p.Hs || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int E = ens->members, q = ens->n_perturb;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
-    if (!ens->amp_scales || !ens->weights || (q > 0 && (!ens->P || !ens->offsets)))
+    if ((!fleet && !ens->amp_scales) || !ens->weights || (q > 0 && (!ens->P || (!fleet && !ens->offsets))))
         return fail(QOC_ERR_INVALID, "%s: ensemble arrays missing", who);
     if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
         return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
@@ -1301,7 +1307,7 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
     // (no trajectory kernel of an ensemble forms controls from maxA: the rows of a mapped engine carry ones)
     std::vector<double> maxAt(p.maxA, p.maxA + (map ? 0 : k));
     maxAt.resize((size_t)(kt + q), 1.0);
-    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape, map};
+    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape, map, fleet};
     p.Hs = Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
     return create_engine(&tc, p, &ea, out);
 }
@@ -1316,14 +1322,14 @@ int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const do
 // qoc_create_shaped and qoc_create_mapped (`who`): the response matrix prepared (tr may be null under a map: no line), one nominal member
 // where there is no ensemble, the checked control map handed on
 static int create_shaped(const char* who, const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map,
-                         const Problem& p, qoc_handle* out) {
+                         const Problem& p, qoc_handle* out, const qoc_fleet* fleet = nullptr) {
     if (!cfg || (!tr && !map) || !p.maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "%s: k, steps must be >= 1", who);
     const int steps = cfg->steps, k = cfg->k;
     // no ensemble: one nominal member
     const std::vector<double> ones((size_t)k + 1, 1.0);
     const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    if (!tr) return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out, map);
+    if (!tr) return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out, map, fleet);
     const int P = tr->n_samples;
     if (P < 1) return fail(QOC_ERR_INVALID, "%s: n_samples = %d (>= 1)", who, P);
     if (!tr->T) return fail(QOC_ERR_INVALID, "%s: the response matrix is missing", who);
@@ -1350,7 +1356,7 @@ static int create_shaped(const char* who, const qoc_config* cfg, const qoc_ensem
         sh.col_band = std::max(sh.col_band, sh.col_win[s].y - sh.col_win[s].x);
     }
     for (int t = 0; t < steps; ++t) sh.band = std::max(sh.band, sh.row_win[t].y - sh.row_win[t].x);
-    return create_members(who, &sh, cfg, ens ? ens : &nominal, p, out, map);
+    return create_members(who, &sh, cfg, ens ? ens : &nominal, p, out, map, fleet);
 }
 
 int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
@@ -1361,11 +1367,9 @@ int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
                          out);
 }
 
-// the map is checked here, on the host and before any device is touched: ranges, finite entries, every pulse reaches an operator
-int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs,
-                      const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
-                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    const char* who = "qoc_create_mapped";
+// the map of qoc_create_mapped and qoc_create_fleet (`who`), checked on the host and before any device is touched: ranges, finite entries, every
+// pulse reaches an operator
+static int check_map(const char* who, const qoc_config* cfg, const qoc_control_map* map, const double* maxA) {
     if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     if (!map) return fail(QOC_ERR_INVALID, "%s: the control map is missing", who);
     if (!map->poly) return fail(QOC_ERR_INVALID, "%s: the map's polynomial coefficients (poly) are missing", who);
@@ -1392,7 +1396,49 @@ int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
         }
         if (!reaches) return fail(QOC_ERR_INVALID, "%s: pulse %d reaches no operator (poly[i][%d] or mix[i][%d] is zero for every i)", who, j, j, j);
     }
+    return QOC_OK;
+}
+
+int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs,
+                      const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    const char* who = "qoc_create_mapped";
+    TRY(check_map(who, cfg, map, maxA));
     return create_shaped(who, cfg, ens, tr, map, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
+}
+
+// the fleet's own checks, on the host and before any device is touched; then the ensemble's entry point that transfer and map select, with the
+// fleet's tables in place of the ensemble's (ens: members, n_perturb, P and weights only; null: one member per device, no perturbation)
+int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map,
+                     const double* Hs, const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                     const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    const char* who = "qoc_create_fleet";
+    if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    if (!fleet) return fail(QOC_ERR_INVALID, "%s: the fleet is missing", who);
+    if (!fleet->amp_scales) return fail(QOC_ERR_INVALID, "%s: the fleet's amp_scales are missing", who);
+    if (cfg->k < 1 || cfg->n_seeds < 1) return fail(QOC_ERR_INVALID, "%s: k, n_seeds must be >= 1", who);
+    const int F = fleet->devices, k = cfg->k;
+    if (F < 1) return fail(QOC_ERR_INVALID, "%s: devices = %d (>= 1)", who, F);
+    if (cfg->n_seeds % F != 0) return fail(QOC_ERR_INVALID, "%s: n_seeds = %d is no multiple of devices = %d", who, cfg->n_seeds, F);
+    const std::vector<double> ones((size_t)k + 1, 1.0);
+    qoc_ensemble members{1, 0, nullptr, nullptr, nullptr, ones.data()};
+    if (ens) members = *ens;
+    const int E = members.members, q = members.n_perturb;
+    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
+    if (q > 0 && !fleet->offsets) return fail(QOC_ERR_INVALID, "%s: the fleet's offsets are missing (n_perturb = %d)", who, q);
+    const size_t per_a = (size_t)E * k, per_d = (size_t)E * q;
+    for (size_t i = 0; i < (size_t)F * per_a; ++i)
+        if (!std::isfinite(fleet->amp_scales[i]))
+            return fail(QOC_ERR_INVALID, "%s: amp_scales[%zu][%zu][%zu] is not finite", who, i / per_a, (i / k) % E, i % k);
+    for (size_t i = 0; i < (size_t)F * per_d; ++i)
+        if (!std::isfinite(fleet->offsets[i]))
+            return fail(QOC_ERR_INVALID, "%s: offsets[%zu][%zu][%zu] is not finite", who, i / per_d, (i / q) % E, i % q);
+    // (the ensemble's own tables are not read on a fleet)
+    members.offsets = nullptr; members.amp_scales = nullptr;
+    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
+    if (map) TRY(check_map(who, cfg, map, maxA));
+    if (tr || map) return create_shaped(who, cfg, &members, tr, map, p, out, fleet);
+    return create_members(who, nullptr, cfg, &members, p, out, nullptr, fleet);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1856,6 +1902,7 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     }
     // ensemble engines only (the plain engines' line stays as it was)
     if (e->ens_E) add(" members=%d perturbations=%d", e->ens_E, e->en.q);
+    if (e->fleet_F) add(" devices=%d", e->fleet_F);
     if (e->shaped) add(" samples=%d band=%d", e->sh.P, e->sh.band);
     if (e->mapped) add(" terms=%d degree=%d", e->cm.r, e->cm.D);
     add(" gradient=%s", e->xg.on ? "exact" : "first_order");

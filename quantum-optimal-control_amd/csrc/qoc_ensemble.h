@@ -10,11 +10,14 @@
 #pragma once
 #include "qoc_common.h"
 
+// A fleet (qoc_create_fleet) has F devices with a member table each: control set g belongs to device g / R and reads the block (g / R) E k of a,
+// (g / R) E q of delta.  The three older entry points make F = 1, R = the number of control sets: block 0 for every control set.
 struct QocEns {
     int E, q;
-    const double* a;       // [E][k]  amplitude scale of each control
-    const double* delta;   // [E][q]  value of each frozen perturbation row
-    const double* wt;      // [E]     member weights
+    int R;                 // control sets per device
+    const double* a;       // [F][E][k]  amplitude scale of each control
+    const double* delta;   // [F][E][q]  value of each frozen perturbation row
+    const double* wt;      // [E]        member weights
 };
 
 // Trajectory controls from the group's: thread per (group, row j < k', slice), a loop over the members.  from_base: the group's controls
@@ -30,7 +33,9 @@ __global__ void __launch_bounds__(256) k_ens_expand(QocDev t, QocDev g, QocEns e
         const int gi = (int)(i / ((size_t)steps * kp));
         double* tu = t.u + ((size_t)gi * E * kp + j) * steps + tt;
         const size_t tstride = (size_t)kp * steps;
+        const size_t dev = (size_t)(gi / en.R) * E;                  // the first member row of this control set's device
         if (j < k) {
+            const double* a = en.a + dev * k;
             const size_t go = ((size_t)gi * k + j) * steps + tt;
             double gu;
             if (from_base) {
@@ -41,9 +46,10 @@ __global__ void __launch_bounds__(256) k_ens_expand(QocDev t, QocDev g, QocEns e
             } else {
                 gu = g.u[go];
             }
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = en.a[(size_t)e * k + j] * gu;
+            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = a[(size_t)e * k + j] * gu;
         } else {
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = en.delta[(size_t)e * en.q + (j - k)];
+            const double* delta = en.delta + dev * en.q;
+            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
         }
         if (j == 0 && tt == 0)
             for (int e = 0; e < E; ++e) t.done[(size_t)gi * E + e] = g.done[gi];
@@ -63,8 +69,9 @@ __global__ void __launch_bounds__(256) k_ens_reduce(QocDev t, QocDev g, QocEns e
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o < ks) {
         const int j = o / steps;
-        double acc = (en.wt[0] * en.a[j]) * src[o];
-        for (int e = 1; e < E; ++e) acc = acc + (en.wt[e] * en.a[(size_t)e * k + j]) * src[(size_t)e * tstride + o];
+        const double* a = en.a + (size_t)(gi / en.R) * E * k;
+        double acc = (en.wt[0] * a[j]) * src[o];
+        for (int e = 1; e < E; ++e) acc = acc + (en.wt[e] * a[(size_t)e * k + j]) * src[(size_t)e * tstride + o];
         g.dLdu[(size_t)gi * ks + o] = acc;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -149,8 +156,9 @@ __global__ void __launch_bounds__(256) k_ens_reduce_risk(QocDev t, QocDev g, Qoc
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o < ks) {
         const int j = o / steps;
-        double acc = (pi[0] * en.a[j]) * src[o];
-        for (int e = 1; e < E; ++e) acc = acc + (pi[e] * en.a[(size_t)e * k + j]) * src[(size_t)e * tstride + o];
+        const double* a = en.a + (size_t)(gi / en.R) * E * k;
+        double acc = (pi[0] * a[j]) * src[o];
+        for (int e = 1; e < E; ++e) acc = acc + (pi[e] * a[(size_t)e * k + j]) * src[(size_t)e * tstride + o];
         g.dLdu[(size_t)gi * ks + o] = acc;
     }
 }

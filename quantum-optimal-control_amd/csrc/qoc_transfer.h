@@ -43,6 +43,7 @@ __global__ void __launch_bounds__(256) k_shape_expand(QocDev t, QocDev s, QocEns
         const int gi = (int)(i / ((size_t)steps * kp));
         double* tu = t.u + ((size_t)gi * E * kp + j) * steps + tt;
         const size_t tstride = (size_t)kp * steps;
+        const size_t dev = (size_t)(gi / en.R) * E;                  // the first member row of this control set's device
         if (j < k) {
             // (row tt of T from the transposed copy: neighbouring threads are neighbouring slices, whose windows overlap)
             const int2 win = sh.row_win[tt];
@@ -55,20 +56,24 @@ __global__ void __launch_bounds__(256) k_shape_expand(QocDev t, QocDev s, QocEns
             }
             const double gu = s.maxA[j] * wf;
             sh.uf[((size_t)gi * k + j) * steps + tt] = gu;
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = en.a[(size_t)e * k + j] * gu;
+            const double* a = en.a + dev * k;
+            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = a[(size_t)e * k + j] * gu;
         } else {
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = en.delta[(size_t)e * en.q + (j - k)];
+            const double* delta = en.delta + dev * en.q;
+            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
         }
         if (j == 0 && tt == 0)
             for (int e = 0; e < E; ++e) t.done[(size_t)gi * E + e] = s.done[gi];
     }
 }
 
-// the members' weighted gradient of one (j, t) element: members summed 0 .. E-1 from member 0's term (k_ens_reduce's arithmetic)
-__device__ __forceinline__ double shape_member_sum(const double* __restrict__ src, const QocEns& en, int j, int k, size_t tstride) {
+// the members' weighted gradient of one (j, t) element: members summed 0 .. E-1 from member 0's term (k_ens_reduce's arithmetic); a: the
+// amplitude rows of the control set's device
+__device__ __forceinline__ double shape_member_sum(const double* __restrict__ src, const QocEns& en, const double* __restrict__ a, int j, int k,
+                                                   size_t tstride) {
 #pragma clang fp contract(off)
-    double acc = (en.wt[0] * en.a[j]) * src[0];
-    for (int e = 1; e < en.E; ++e) acc = acc + (en.wt[e] * en.a[(size_t)e * k + j]) * src[(size_t)e * tstride];
+    double acc = (en.wt[0] * a[j]) * src[0];
+    for (int e = 1; e < en.E; ++e) acc = acc + (en.wt[e] * a[(size_t)e * k + j]) * src[(size_t)e * tstride];
     return acc;
 }
 
@@ -90,11 +95,12 @@ __global__ void __launch_bounds__(256) k_shape_reduce(QocDev t, QocDev s, QocEns
         const int2 win = sh.col_win[p];
         const double* col = sh.Tt + (size_t)p * steps;
         const double* src = t.dLdu + (size_t)gi * E * tstride + (size_t)j * steps;
+        const double* a = en.a + (size_t)(gi / en.R) * E * k;
         double acc = 0.0;
         int tt = win.x + lane;
         if (tt < win.y) {
-            acc = col[tt] * shape_member_sum(src + tt, en, j, k, tstride);
-            for (tt += LANES; tt < win.y; tt += LANES) acc = acc + col[tt] * shape_member_sum(src + tt, en, j, k, tstride);
+            acc = col[tt] * shape_member_sum(src + tt, en, a, j, k, tstride);
+            for (tt += LANES; tt < win.y; tt += LANES) acc = acc + col[tt] * shape_member_sum(src + tt, en, a, j, k, tstride);
         }
         if (LANES > 1) {
 #pragma unroll
@@ -128,11 +134,12 @@ __global__ void __launch_bounds__(256) k_shape_reduce_risk(QocDev t, QocDev s, Q
         const int2 win = sh.col_win[p];
         const double* col = sh.Tt + (size_t)p * steps;
         const double* src = t.dLdu + (size_t)gi * E * tstride + (size_t)j * steps;
+        const double* a = en.a + (size_t)(gi / en.R) * E * k;
         double acc = 0.0;
         int tt = win.x + lane;
         if (tt < win.y) {
-            acc = col[tt] * shape_member_sum(src + tt, er, j, k, tstride);
-            for (tt += LANES; tt < win.y; tt += LANES) acc = acc + col[tt] * shape_member_sum(src + tt, er, j, k, tstride);
+            acc = col[tt] * shape_member_sum(src + tt, er, a, j, k, tstride);
+            for (tt += LANES; tt < win.y; tt += LANES) acc = acc + col[tt] * shape_member_sum(src + tt, er, a, j, k, tstride);
         }
         if (LANES > 1) {
 #pragma unroll

@@ -46,6 +46,10 @@ class QocControlMap(C.Structure):
                 ('fixed', C.POINTER(C.c_double))]
 
 
+class QocFleet(C.Structure):
+    _fields_ = [('devices', C.c_int32), ('offsets', C.POINTER(C.c_double)), ('amp_scales', C.POINTER(C.c_double))]
+
+
 class QocOpen(C.Structure):
     _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double))]
 
@@ -78,6 +82,8 @@ _SIGNATURES = {
     'qoc_create_mapped': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocTransfer), C.POINTER(QocControlMap), _DP, _DP, _DP,
                                     _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_coefficients': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_create_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocFleet), C.POINTER(QocTransfer),
+                                   C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_open': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocOpen), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
@@ -317,6 +323,21 @@ def ensemble_arrays(ensemble, n, k, dt):
     return P, off, amp, wt
 
 
+def fleet_arrays(fleet, E, q, k):
+    """The C ABI's qoc_fleet arrays from a helper_functions.fleet.Fleet or a dict with keys `offsets` (F x E x q, optional when q = 0) and
+    `amp_scales` (F x E x k): (offsets, amp_scales), both C-contiguous."""
+    get = fleet.get if isinstance(fleet, dict) else lambda key, default=None: getattr(fleet, key, default)
+    amp = np.ascontiguousarray(np.asarray(get('amp_scales'), dtype=np.float64))
+    if amp.ndim != 3 or amp.shape[1:] != (E, k):
+        raise ValueError('HipEngine: fleet amp_scales have shape %s, expected (F, %d, %d)' % (amp.shape, E, k))
+    F = amp.shape[0]
+    off = get('offsets')
+    off = np.zeros((F, E, q)) if off is None or (q == 0 and np.size(off) == 0) else np.ascontiguousarray(np.asarray(off, dtype=np.float64))
+    if off.shape != (F, E, q):
+        raise ValueError('HipEngine: fleet offsets have shape %s, expected (%d, %d, %d)' % (off.shape, F, E, q))
+    return off, amp
+
+
 VECTOR_HOME = {None: 0, 'auto': 0, 'lds': 1, 'global': 2}
 
 
@@ -370,13 +391,26 @@ class HipEngine(object):
     and the r operators the map feeds, maxA (and one_minus_gauss, the variable, the gradient, get_uks) the k pulses: self.k is the number of pulses,
     self.terms the number of operators.  get_coefficients() gives the (n_seeds, r, steps) coefficients the nominal member's trajectories ran on.
     Composes with ensemble, transfer and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is
-    loaded)."""
+    loaded).
+
+    fleet (device fleets, include/qoc.h qoc_create_fleet): a helper_functions.fleet.Fleet, or a dict with keys `offsets` (F x E x q) and `amp_scales`
+    (F x E x k).  n_seeds = F R control sets, device-major: control set g is optimised on device g // R's members.  `ensemble` then supplies the
+    operators, the weights and the risk (its offsets and amp_scales are not read; a Fleet brings its own when `ensemble` is None; neither: one
+    member per device, no perturbation).  self.devices is F; every read-back keeps its (n_seeds, ...) shape.  Composes with transfer, control_map
+    and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is loaded)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
-                 sparse_ops=None, vector_home=None, control_map=None):
+                 sparse_ops=None, vector_home=None, control_map=None, fleet=None):
         sparse = None
+        if fleet is not None:
+            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
+                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
+                if given:
+                    raise ValueError('HipEngine: fleet does not combine with %s' % name)
+            if ensemble is None and not isinstance(fleet, dict):
+                ensemble = fleet.device(0)
         if control_map is not None:
             for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
@@ -462,16 +496,28 @@ class HipEngine(object):
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
         tr = None
-        if transfer is not None and control_map is not None:
+        self.devices = 0                              # device fleets: F, the devices the n_seeds control sets are spread over
+        if transfer is not None and (control_map is not None or fleet is not None):
             T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
             if T.ndim != 2 or T.shape[0] != int(steps):
                 raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
             tr = QocTransfer()
             tr.n_samples, tr.T = T.shape[1], _dp(T)
+        cmap = None
         if control_map is not None:
             cmap = QocControlMap()
             cmap.n_terms, cmap.degree = control_map.n_terms, control_map.degree
             cmap.poly, cmap.mix, cmap.fixed = _dp(control_map.alpha), _dp(control_map.mix), _dp(control_map.fixed)
+        if fleet is not None:
+            foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
+            fl = QocFleet()
+            fl.devices, fl.offsets, fl.amp_scales = famp.shape[0], (_dp(foff) if foff.shape[2] else None), _dp(famp)
+            _check(lib.qoc_create_fleet(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(fl), None if tr is None else C.byref(tr),
+                                        None if cmap is None else C.byref(cmap), *args))
+            if tr is not None:
+                self.samples = int(tr.n_samples)
+            self.devices = int(fl.devices)
+        elif cmap is not None:
             _check(lib.qoc_create_mapped(C.byref(cfg), None if ens is None else C.byref(ens), None if tr is None else C.byref(tr), C.byref(cmap), *args))
             if tr is not None:
                 self.samples = int(tr.n_samples)
@@ -501,6 +547,8 @@ class HipEngine(object):
             _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
         if ens is not None:
             self.members = int(ens.members)
+        elif fleet is not None:
+            self.members = 1
         self.risk = 0.0
         if ensemble is not None and float(ensemble.get('risk', 0.0)) > 0:
             self.set_risk(ensemble['risk'])

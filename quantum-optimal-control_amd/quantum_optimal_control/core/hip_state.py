@@ -12,7 +12,7 @@ from quantum_optimal_control.core import hip_engine
 class HipState(object):
 
     def __init__(self, sys_para, n_seeds=1, device=0, path=hip_engine.PATH_AUTO, chunks=0, first_seed=0, plan_seeds=0, time_comm=None, ensemble=None, transfer=None,
-                 exact_gradient=False, collapse_ops=None, control_map=None):
+                 exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, fleet_base=None):
         self.sys_para = sys_para
         self.n_seeds = n_seeds
         self.first_seed = first_seed      # global index of this engine's first restart (seed-sharded runs)
@@ -26,6 +26,8 @@ class HipState(object):
         self.exact_gradient = bool(exact_gradient)   # qoc_config.gradient: the derivative of the computed propagators instead of the first-order formula
         self.collapse_ops = collapse_ops  # open-system GRAPE: the validated list of collapse operators (helper_functions/open_system.py), or None
         self.control_map = control_map    # control map: the validated helper_functions.control_map.ControlMap, or None (sys_para.ops_c are then the r operators it feeds)
+        self.fleet = fleet                # device fleet: the validated helper_functions.fleet.Fleet, or None; n_seeds is then F x restarts, device-major
+        self.fleet_base = fleet_base      # ... and each device's own first start point (F, k, P), or None: sys_para.ops_weight_base for every device
         self.engine = None
 
     def build_graph(self):
@@ -51,9 +53,21 @@ class HipState(object):
             n_seeds=self.n_seeds, device=self.device, path=self.path, chunks=self.chunks, plan_seeds=self.plan_seeds,
             time_shards=0 if self.time_comm is None else self.time_comm.world, time_rank=-1 if self.time_comm is None else self.time_comm.rank,
             time_comm=self.time_comm, ensemble=self.ensemble, transfer=self.transfer, exact_gradient=self.exact_gradient,
-            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops, control_map=self.control_map)
+            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops, control_map=self.control_map, fleet=self.fleet)
         base = np.asarray(sp.ops_weight_base, dtype=np.float64)
-        if base.ndim == 2 and (self.n_seeds > 1 or self.first_seed > 0):
+        if self.fleet is not None:
+            # control set (f, r) starts where control set r of the same call without a fleet starts (or, r = 0, from device f's own point)
+            from quantum_optimal_control.helper_functions.fleet import tile_bases
+            from quantum_optimal_control.parallel_seeds import restart_guesses
+            F = self.fleet.n_devices
+            R = self.n_seeds // F
+            extra = restart_guesses(base.shape[0], base.shape[1], 1, R - 1)
+            if self.fleet_base is None:
+                base = tile_bases(np.concatenate([base[None], extra], axis=0), F)
+            else:
+                first = np.asarray(self.fleet_base, dtype=np.float64).reshape((F, 1) + base.shape)
+                base = tile_bases(np.concatenate([first, np.broadcast_to(extra[None], (F,) + extra.shape)], axis=1), F)
+        elif base.ndim == 2 and (self.n_seeds > 1 or self.first_seed > 0):
             # global restart 0 = the reference's own starting point; restart g > 0 = the reproducible stream of index g,
             # whatever rank / batch it lands in
             from quantum_optimal_control.parallel_seeds import restart_guesses
@@ -65,6 +79,7 @@ class HipState(object):
         elif base.ndim == 2:
             base = base[None]
         self.engine.set_base(base)
+        self.start_base = base            # (n_seeds, k, P): where every control set starts
         print("Graph built!")
         return self.engine
 

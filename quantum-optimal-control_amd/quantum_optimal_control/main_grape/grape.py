@@ -87,7 +87,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, control_map=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -140,10 +140,36 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``maxA`` and ``initial_guess`` have one entry per pulse (k of them, r need not equal k) and the returned uks is k x steps; afterwards
     ``control_map.coefficients`` holds the r x steps coefficients the nominal Hamiltonian ran on.  The pulse regularisers act on the pulses, the
     Taylor order is chosen for the largest coefficients the map can deliver.  Works with every ``method``, with ``restarts``, ``robust``,
-    ``transfer`` and ``exact_gradient``; not with ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm`` or the sharded entry points."""
+    ``transfer`` and ``exact_gradient``; not with ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm`` or the sharded entry points.
+
+    ``fleet`` (device fleets): a helper_functions.fleet.Fleet (``fleet.devices``, ``fleet.around``) -- F devices that differ in their drift offsets and
+    drive scales, each an ensemble of E members (E = 1: one Hamiltonian per device).  One engine then optimises a pulse for every device, ``restarts=R``
+    control sets each, and the call returns ``(uks, U_final)`` with a leading device axis: ``uks[f]`` is the k x steps pulse of device f's best control
+    set (the smallest loss of its R, the first of equals), ``U_final[f]`` member 0's final unitary under it.  Control set (f, r) starts where control
+    set r of the same call without a fleet starts; ``initial_guess`` may also be (F, k, steps), one guess per device.  Afterwards the fleet carries
+    ``losses`` (F,), ``best`` (F,), ``member_losses`` (F, E) and ``iterations`` (F,); ``transfer.samples`` is (F, k, P) and ``control_map.coefficients``
+    (F, r, steps).  The Taylor order is the largest any member of any device would get.  ``method`` is ``'Adam'``, ``'LBFGS'`` or ``'EVOLVE'`` (the
+    scan of one pulse over the devices).  Works with ``transfer``, ``control_map`` and ``exact_gradient``; not with ``robust`` (a fleet carries its own
+    members: ``fleet.around``), ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm``, ``plan_seeds`` or the sharded entry points."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     sparse = _is_sparse(H0, Hops)
+    fleet_guess = None
+    if fleet is not None:
+        # device fleets: refused before anything is built (and before the library is loaded)
+        for name, given in (('robust (a fleet carries its own members: fleet.around)', robust is not None),
+                            ('scipy.sparse Hamiltonians (sparse state transfer)', sparse), ('collapse_ops (open-system GRAPE)', collapse_ops is not None),
+                            ('time_comm', time_comm is not None)):
+            if given:
+                raise ValueError('Grape: fleet does not combine with %s' % name)
+        if _first_seed != 0 or plan_seeds is not None:
+            raise ValueError('Grape: fleet does not run sharded (plan_seeds, _first_seed, GrapeSharded)')
+        if str(method).upper() not in ('ADAM', 'LBFGS', 'EVOLVE'):
+            raise ValueError("Grape: fleet runs under method='Adam', 'LBFGS' or 'EVOLVE'; %r is scipy's, one control set" % (method,))
+        if initial_guess is not None and np.ndim(initial_guess) == 3:
+            # one guess per device: device 0's goes the way of every guess, the others follow it below
+            fleet_guess = np.asarray(initial_guess, dtype=np.float64)
+            initial_guess = fleet_guess[0]
     if sparse:
         # the sparse state-transfer route: refused before anything is built (and before the library is loaded)
         if not state_transfer:
@@ -184,6 +210,12 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         for name, seq in (('Hnames', Hnames), ('maxA', maxA), ('initial_guess', None if transfer is not None else initial_guess)):
             if seq is not None and len(seq) != n_pulses:
                 raise ValueError('Grape: with a control map %s has one entry per pulse (%d), got %d' % (name, n_pulses, len(seq)))
+    if fleet is not None:
+        from quantum_optimal_control.helper_functions import fleet as _fleet
+        _given_fleet = fleet                           # (validate returns a normalised copy: the caller's object gets the results)
+        fleet = _fleet.validate(fleet, len(H0), n_pulses)
+        if fleet_guess is not None and (fleet_guess.shape[0] != fleet.n_devices or fleet_guess.shape[1] != n_pulses):
+            raise ValueError('Grape: a per-device initial guess of a fleet is (%d, %d, ...), got %s' % (fleet.n_devices, n_pulses, fleet_guess.shape))
     if str(method).upper() == 'LBFGS' and time_comm is not None:
         raise ValueError("Grape: method='LBFGS' cannot be time-sharded (time_comm)")
     if exact_gradient and time_comm is not None:
@@ -230,6 +262,11 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
                 hf.add('exact_gradient', data=np.array(1))
+        if fleet is not None:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                hf.add('fleet_offsets', data=fleet.offsets)
+                hf.add('fleet_amp_scales', data=fleet.amp_scales)
         if collapse_ops is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -244,9 +281,13 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if initial_guess is None:
             maxAmp = 4 * np.ones(n_pulses)
         else:
-            maxAmp = 1.5 * np.max(np.abs(initial_guess)) * np.ones(n_pulses)
+            maxAmp = 1.5 * np.max(np.abs(initial_guess if fleet_guess is None else fleet_guess)) * np.ones(n_pulses)
     else:
         maxAmp = maxA
+
+    if fleet is not None and Taylor_terms is None:
+        # the largest Taylor order and squaring count any member of any device would get
+        Taylor_terms = _fleet.choose_taylor(fleet, H0, Hops, control_map, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
 
     if control_map is not None and Taylor_terms is None:
         # the chooser on (H0, Hops, cmax): the largest coefficients the map can deliver stand where maxA stands (every member's, with a robust ensemble)
@@ -305,14 +346,30 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             sample_base = np.random.normal(0, 1. / np.sqrt(P), [n_pulses, P])
         sys_para.ops_weight_base = sample_base
         sys_para.raw_shape = np.shape(sample_base)
-    tfs = HipState(sys_para, n_seeds=max(1, int(restarts)), device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
-                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust,
+    fleet_base = None
+    if fleet_guess is not None:
+        # every device's own first start point, by the rule its guess alone would go through (base = arcsin(u / maxA))
+        width = steps if transfer is None else transfer.n_samples
+        if fleet_guess.shape[2] != width:
+            raise ValueError('Grape: a per-device initial guess of this fleet is (%d, %d, %d), got %s' % (fleet.n_devices, n_pulses, width, fleet_guess.shape))
+        ratio = fleet_guess / np.asarray(maxAmp, dtype=np.float64)[None, :, None]
+        for row in range(n_pulses):
+            if np.max(ratio[:, row]) > 1.0:
+                raise ValueError('Initial guess has strength > max_amp for op %d' % (row))
+        fleet_base = np.arcsin(ratio)
+    n_sets = max(1, int(restarts)) * (1 if fleet is None else fleet.n_devices)
+    tfs = HipState(sys_para, n_seeds=n_sets, device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
+                   plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust if fleet is None else fleet.device(0),
                    transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient),
-                   collapse_ops=collapse_ops, control_map=control_map)   # constants -> HBM
+                   collapse_ops=collapse_ops, control_map=control_map, fleet=fleet, fleet_base=fleet_base)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
         SS = run_session(tfs, graph, conv, sys_para, method, show_plots=sys_para.show_plots, use_gpu=use_gpu)
+        if fleet is not None:
+            return _fleet_results(tfs.engine, sys_para, fleet, _given_fleet, transfer, control_map, _given_map if control_map is not None else None,
+                                  tfs.start_base if str(method).upper() == 'EVOLVE' and fleet_base is not None else None, save, file_path,
+                                  grape_start_time)
         if transfer is not None:
             transfer.samples = np.array(SS.samples)
         if control_map is not None:
@@ -339,6 +396,36 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         tfs.close()
 
 
+def _fleet_results(engine, sys_para, fleet, given_fleet, transfer, control_map, given_map, own_points, save, file_path, start_time):
+    """The per-device selection after run_session: every device's best control set (helper_functions.fleet.select_best on the final losses), its pulse
+    and member 0's final unitary, and the fleet's result fields (on the caller's object too)."""
+    from quantum_optimal_control.helper_functions.fleet import select_best
+    if own_points is not None:
+        # method='EVOLVE' scored one shared point; with a guess per device every device is scored at its own
+        engine.set_base(own_points)
+        engine.evaluate(want_grad=False)
+    s = engine.scalars()
+    best, sets = select_best(s['loss'], fleet.n_devices)
+    evaluated = engine.get_uks(evaluated=True)[sets]
+    uks = engine.get_pulse()[sets] if engine.samples is not None else evaluated
+    Uf = [[] for _ in sets] if sys_para.state_transfer else engine.get_final_unitary()[sets]
+    member_losses = engine.member_scalars()['loss'][sets]
+    for fl in (fleet, given_fleet):
+        fl.losses, fl.best, fl.member_losses, fl.iterations = np.array(s['loss'][sets]), np.array(best), np.array(member_losses), np.array(s['iterations'][sets])
+    if transfer is not None:
+        transfer.samples = np.array(evaluated)
+    if control_map is not None:
+        given_map.coefficients = control_map.coefficients = np.array(engine.get_coefficients()[sets])
+    if save:
+        from quantum_optimal_control.helper_functions.data_management import H5File
+        with H5File(file_path) as hf:
+            hf.add('fleet_uks', data=np.array(uks))
+            hf.add('fleet_losses', data=np.array(fleet.losses))
+            hf.add('wall_clock_time', data=np.array(time.time() - start_time))
+        print("data saved at: " + str(file_path))
+    return uks, Uf
+
+
 def GrapeTimeSharded(*args, comm=None, **kwargs):
     """`Grape(...)` for ONE large control problem (hundreds of levels, thousands of slices: BASELINE config 5) on all GPUs of a node: the pulse is
     cut along the TIME axis, rank r of `comm` (parallel_seeds.open_comm(): RCCL over xGMI behind the C ABI) forms the propagators, sweeps and
@@ -352,6 +439,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
         raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
     if kwargs.get('control_map') is not None:
         raise ValueError('GrapeTimeSharded: control_map (control maps) is not supported; run Grape(control_map=...) on one GPU')
+    if kwargs.get('fleet') is not None:
+        raise ValueError('GrapeTimeSharded: fleet (device fleets) is not supported; run Grape(fleet=...) on one GPU')
     if _sparse_call(args, kwargs):
         raise ValueError('GrapeTimeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(...) on one GPU')
     if comm is None:
@@ -394,6 +483,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
         raise ValueError('GrapeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=..., restarts=R) on one GPU')
     if kwargs.get('control_map') is not None:
         raise ValueError('GrapeSharded: control_map (control maps) is not supported; run Grape(control_map=..., restarts=R) on one GPU')
+    if kwargs.get('fleet') is not None:
+        raise ValueError('GrapeSharded: fleet (device fleets) is not supported; run Grape(fleet=..., restarts=R) on one GPU')
     if _sparse_call(args, kwargs):
         raise ValueError('GrapeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(..., restarts=R) on one GPU')
     if comm is not None:
