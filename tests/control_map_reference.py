@@ -99,7 +99,8 @@ def tilt(costs, w, beta):
 
 def evaluate(c, cm, ens, x, T=None, exact=False, beta=0.0, want_grad=True):
     """The mapped engine's expected values at the variable x (k x steps, or k x P behind the line T (steps x P)) for the members of `ens` (a validated
-    robust dict): loss, reg_loss, grad, grad_squared, unitary_scale, member_loss, coefficients / inter_vecs / U_final of member 0, pulse, uks."""
+    robust dict): loss, reg_loss, grad, grad_squared, unitary_scale, member_loss, coefficients / inter_vecs / U_final of member 0, member_U (every
+    member's final unitary; None in state-transfer mode), pulse, uks."""
     maxA = np.asarray(c['maxA'], dtype=np.float64)
     k = len(maxA)
     x = np.asarray(x, dtype=np.float64).reshape(k, -1)
@@ -135,7 +136,8 @@ def evaluate(c, cm, ens, x, T=None, exact=False, beta=0.0, want_grad=True):
         pi = w
         loss, reg_loss = float(np.sum(w * loss_e)), float(np.sum(w * (loss_e + state_e))) + val
     out = dict(loss=loss, reg_loss=reg_loss, unitary_scale=float(np.sum(w * np.array([r['unitary_scale'] for r in rs]))), member_loss=loss_e,
-               weights=pi, pulse=u, uks=maxA[:, None] * ws, coefficients=cmap.apply(cm, vs[0]), U_final=rs[0]['U_final'])
+               weights=pi, pulse=u, uks=maxA[:, None] * ws, coefficients=cmap.apply(cm, vs[0]), U_final=rs[0]['U_final'],
+               member_U=None if c['state_transfer'] else np.stack([r['U_final'] for r in rs]))
     if not want_grad:
         return out
     dJdu = sum(pi[e] * ens['amp_scales'][e][:, None] * cmap.pullback(cm, vs[e], rs[e]['dL_du']) for e in range(E))

@@ -23,6 +23,10 @@ The stop values are chosen on the oracle alone (CPU, cached per problem): free r
 accept_min_grad with a relative margin above 1e-8.  test_stop_values_meet_the_conditions asserts that without a device, for every row;
 test_rows_cover_every_family that the table names every plan a plain engine can report.
 
+check_row reads a row through an Adapter (build, loop, at, snapshot): plain_adapter is the one of this module's rows -- the oracle's run_adam and
+evaluate --, and tests/test_finished_sets_glue_gpu.py runs the same five checks on ensembles, lines, maps, fleets, the exact gradient, sparse and
+open engines with the references of those kinds.
+
 Shapes: the smallest at which the named kernel runs, pulses of 7 .. 24 slices at 0.04 per slice -- except where the kernel under test needs
 more: the split tail (k steps > 4096), the windowed assembly overlap of the direct route (csrc/qoc_gemm_setup.h: from 64 slices on) and the
 several workgroups per control set AUTO gives the workgroup-resident path at n = 9.
@@ -243,19 +247,67 @@ def accept_min_grad(stops):
     return len(set(stops)) >= 2 and any(0 < s < MAX_IT and any(t > s for t in stops) for s in stops)
 
 
-@functools.lru_cache(maxsize=None)
-def free_runs(problem, B):
-    build, rate = PROBLEMS[problem]
-    sp = oracle_system(build())
-    bases = start_bases(sp, B)
-    conv = dict(rate=rate, max_iterations=MAX_IT, learning_rate_decay=100, conv_target=-1.0, min_grad=-1.0)
-    return sp, bases, conv, [go.run_adam(sp, conv, base=b, history=True) for b in bases]
+class Adapter(object):
+    """What check_row needs of a row, whatever kind of engine it runs (tests/test_finished_sets_glue_gpu.py supplies the kinds that are not plain):
+
+      build(n_sets)       the engine, the row's plan words asserted;
+      loop(conv, x0, b)   the reference loop of control set b from x0: dict(base, iterations, history (columns loss, reg_loss, grad_squared),
+                          vectors {read-back: expected}, scalars {name: expected}) -- the loop's outcome, held to `loop_tol`;
+      at(base, b)         the reference evaluation of control set b at `base`: {read-back: expected}, held to `read_tol[read-back]` relative to
+                          max(1, largest expected entry);
+      snapshot(eng)       the kind's read-backs, the lazily formed ones first.
+
+    key: what the references are cached under (rows that share a problem share them); starts(): the control sets' starting points; conv: the loop's
+    parameters without a stop value; loop_tol: dict(vectors=, scalars=, strict=) -- strict: `<` as the kind's own loop test writes it, else `<=`;
+    full_again: check 5 compares the whole snapshot, not base and scalars alone."""
+
+    def __init__(self, key, batch, starts, conv, build, loop, at, snapshot, loop_tol, read_tol, full_again=False):
+        self.key, self.batch, self.starts, self.conv, self.build, self.loop, self.at, self.snapshot = key, batch, starts, conv, build, loop, at, snapshot
+        self.loop_tol, self.read_tol, self.full_again = loop_tol, read_tol, full_again
 
 
 @functools.lru_cache(maxsize=None)
-def reference(problem, B, rule):
-    """The oracle's loop per control set under the stop value chosen for `rule`: (sp, bases, conv, refs, stops, margin)."""
-    sp, bases, conv, free = free_runs(problem, B)
+def plain_system(problem):
+    return oracle_system(PROBLEMS[problem][0]())
+
+
+def plain_adapter(r):
+    """A plain engine against oracle.grape_oracle: run_adam for the loop, evaluate for the read-backs."""
+    problem, B = r['problem'], r['batch']
+
+    def loop(conv, x0, b):
+        res = go.run_adam(plain_system(problem), conv, base=x0, history=True)
+        return dict(base=res['base'], iterations=res['iterations'], history=res['history'],
+                    vectors=dict(base=res['base'], uks=res['uks'], evaluated=res['uks']),
+                    scalars={key: res[key] for key in ('loss', 'reg_loss', 'grad_squared', 'unitary_scale')})
+
+    def at(base, b):
+        sp = plain_system(problem)
+        o = go.evaluate(sp, base, want_grad=False, want_inter=True)
+        return dict(inter=o['inter_vecs']) if sp.state_transfer else dict(inter=o['inter_vecs'], final=o['U_final'])
+
+    return Adapter(key=('plain', problem, B), batch=B, starts=lambda: start_bases(plain_system(problem), B),
+                   conv=dict(rate=PROBLEMS[problem][1], max_iterations=MAX_IT, learning_rate_decay=100, conv_target=-1.0, min_grad=-1.0),
+                   build=lambda n_sets: engine(r, plain_system(problem), n_sets), loop=loop, at=at,
+                   snapshot=lambda eng: snapshot(eng, not plain_system(problem).state_transfer),
+                   loop_tol=dict(vectors=LOOP_ATOL, scalars=LOOP_ATOL, strict=False), read_tol=dict(inter=U_ATOL, final=U_ATOL))
+
+
+_FREE, _REFERENCE = {}, {}
+
+
+def free_runs(a):
+    if a.key not in _FREE:
+        bases = a.starts()
+        _FREE[a.key] = (bases, [a.loop(a.conv, x0, b) for b, x0 in enumerate(bases)])
+    return _FREE[a.key]
+
+
+def reference(a, rule):
+    """The reference loop per control set under the stop value chosen for `rule`: (bases, conv, refs, stops, margin), cached under the adapter's key."""
+    if (a.key, rule) in _REFERENCE:
+        return _REFERENCE[(a.key, rule)]
+    bases, free = free_runs(a)
     hists = [r['history'] for r in free]
     if rule == 'conv_target':
         value, stops = _choose_target(hists, MAX_IT, accept_conv_target)
@@ -264,14 +316,24 @@ def reference(problem, B, rule):
         value, stops = _choose_min_grad(hists, MAX_IT, accept_min_grad)
         column = 2
     margin = min(np.min(np.abs(h[:, column] - value)) for h in hists) / abs(value)
-    conv = dict(conv, **{rule: value})
-    refs = [go.run_adam(sp, conv, base=b) if s < MAX_IT else r for b, r, s in zip(bases, free, stops)]
+    conv = dict(a.conv, **{rule: value})
+    refs = [a.loop(conv, x0, b) if s < MAX_IT else r for b, (x0, r, s) in enumerate(zip(bases, free, stops))]
     assert [r['iterations'] for r in refs] == stops, (stops, [r['iterations'] for r in refs])
-    return sp, bases, conv, refs, stops, margin
+    _REFERENCE[(a.key, rule)] = (bases, conv, refs, stops, margin)
+    return _REFERENCE[(a.key, rule)]
 
 
 def row_id(r):
     return r['name']
+
+
+def check_stop_values(name, a, rule):
+    """The adapter's reference loops admit a stop value that meets the rule's conditions with a relative margin above 1e-8, and a polling period."""
+    _, conv, _, stops, margin = reference(a, rule)
+    print('%s: %s = %.6e stops the control sets after %s iterations, margin %.2e' % (name, rule, conv[rule], stops, margin))
+    assert margin > 1e-8, margin
+    assert (accept_conv_target if rule == 'conv_target' else accept_min_grad)(stops), stops
+    assert next((p for p in POLLS if all(s % p for s in stops if s)), None) is not None, stops
 
 
 @pytest.mark.parametrize('rule', RULES)
@@ -279,20 +341,19 @@ def row_id(r):
 def test_stop_values_meet_the_conditions(r, rule):
     """CPU: the row's problem admits a stop value that meets the rule's conditions with a relative margin above 1e-8 (otherwise another seed, rate or
     start is to be chosen HERE, not on the device)."""
-    _, _, conv, _, stops, margin = reference(r['problem'], r['batch'], rule)
-    print('%s: %s = %.6e stops the control sets after %s iterations, margin %.2e' % (r['name'], rule, conv[rule], stops, margin))
-    assert margin > 1e-8, margin
-    assert (accept_conv_target if rule == 'conv_target' else accept_min_grad)(stops), stops
-    assert next((p for p in POLLS if all(s % p for s in stops if s)), None) is not None, stops
+    check_stop_values(r['name'], plain_adapter(r), rule)
 
 
 # ---- the device ---------------------------------------------------------------------------------------------------------------------------------
 
-FROZEN = ('inter', 'final', 'final_again', 'evaluated', 'loss', 'reg_loss', 'grad_squared', 'unitary_scale', 'base')
+# what check 3 compares bit for bit, where the kind's snapshot holds it: the plain read-backs, then those that exist only on ensemble, risk, mapped,
+# shaped and open engines (tests/test_finished_sets_glue_gpu.py)
+FROZEN = ('inter', 'final', 'final_again', 'evaluated', 'loss', 'reg_loss', 'grad_squared', 'unitary_scale', 'base',
+          'member_loss', 'member_reg_state', 'member_final', 'weights', 'coefficients', 'pulse', 'density', 'populations')
 
 
-def engine(r, sp):
-    eng = make_engine(sp, n_seeds=r['batch'], path=r['path'], chunks=r['chunks'], variant=r['variant'])
+def engine(r, sp, n_sets=None):
+    eng = make_engine(sp, n_seeds=r['batch'] if n_sets is None else n_sets, path=r['path'], chunks=r['chunks'], variant=r['variant'])
     got = {key: (int(v) if v.lstrip('-').isdigit() else v) for key, v in eng.plan.items()}
     for key, want in r['plan'].items():
         assert got.get(key) == want, (r['name'], key, want, got)
@@ -313,42 +374,53 @@ def poll_for(stops):
     return next(p for p in POLLS if all(s % p for s in stops if s))
 
 
-def check_row(r, rule):
-    sp, bases, conv, refs, stops, margin = reference(r['problem'], r['batch'], rule)
-    B, unitary = r['batch'], not sp.state_transfer
+def relative_error(got, want):
+    """max |got - want| / max(1, max |want|): how the parity tests of every kind measure a read-back (scalars too)."""
+    want = np.asarray(want)
+    assert np.shape(got) == want.shape, (np.shape(got), want.shape)
+    return float(np.max(np.abs(np.asarray(got) - want))) / max(1.0, float(np.max(np.abs(want)))) if want.size else 0.0
+
+
+def check_row(name, a, rule):
+    """The five checks of this module's docstring on the row `name` through its adapter `a` (Adapter), under the stop rule `rule`."""
+    bases, conv, refs, stops, margin = reference(a, rule)
+    B = a.batch
     poll = poll_for(stops)
-    eng = engine(r, sp)
+    tol = a.loop_tol
+    within = (lambda err, bound: err < bound) if tol['strict'] else (lambda err, bound: err <= bound)
+    eng = a.build(B)
     try:
-        print('%s [%s]: plan %s' % (r['name'], rule, ' '.join('%s=%s' % kv for kv in eng.plan.items())))
+        print('%s [%s]: plan %s' % (name, rule, ' '.join('%s=%s' % kv for kv in eng.plan.items())))
         print('  %s = %.6e (margin %.2e): stops %s, poll every %d' % (rule, conv[rule], margin, stops, poll))
         # 1. the loop's outcome
         eng.set_base(bases)
         p = eng.adam_params(poll_every=poll, **conv)
         its = eng.run_adam(p)
-        first = snapshot(eng, unitary)
+        first = a.snapshot(eng)
+        unitary = 'final' in first
         assert list(its) == stops, (list(its), stops)
         assert list(first['iterations']) == stops and list(first['done']) == [1] * B, (first['iterations'], first['done'])
-        worst = dict(base=0.0, uks=0.0, evaluated=0.0, scalars=0.0, inter=0.0, final=0.0)
+        worst = {}
         for b, ref in enumerate(refs):
-            for key, want in (('base', ref['base']), ('uks', ref['uks']), ('evaluated', ref['uks'])):
-                worst[key] = max(worst[key], np.max(np.abs(first[key][b] - want)))
-                np.testing.assert_allclose(first[key][b], want, rtol=0, atol=LOOP_ATOL, err_msg='%s of set %d (stopped at %d)' % (key, b, stops[b]))
-            for key in ('loss', 'reg_loss', 'grad_squared', 'unitary_scale'):
-                err = abs(first[key][b] - ref[key]) / max(1.0, abs(ref[key]))
-                worst['scalars'] = max(worst['scalars'], err)
-                assert err <= LOOP_ATOL, (key, b, stops[b], first[key][b], ref[key])
+            for key, want in ref['vectors'].items():
+                err = float(np.max(np.abs(first[key][b] - want)))
+                worst[key] = max(worst.get(key, 0.0), err)
+                assert np.shape(first[key][b]) == np.shape(want) and within(err, tol['vectors']), '%s of set %d (stopped at %d): %.3e' % (key, b, stops[b], err)
+            for key, want in ref['scalars'].items():
+                err = abs(first[key][b] - want) / max(1.0, abs(want))
+                worst['scalars'] = max(worst.get('scalars', 0.0), err)
+                assert within(err, tol['scalars']), (key, b, stops[b], first[key][b], want)
+        print('  worst |device - reference| of the loop: %s (bounds %.0e, scalars %.0e)' % (
+            ', '.join('%s %.2e' % kv for kv in worst.items()), tol['vectors'], tol['scalars']))
         # 2. the read-backs belong to each set's own last evaluation
+        worst = {}
         for b in range(B):
-            o = go.evaluate(sp, first['base'][b], want_grad=False, want_inter=True)
-            err = np.max(np.abs(first['inter'][b] - o['inter_vecs'])) / max(1.0, np.max(np.abs(o['inter_vecs'])))
-            worst['inter'] = max(worst['inter'], err)
-            assert err <= U_ATOL, ('inter_vecs', b, stops[b], err)
-            if unitary:
-                err = np.max(np.abs(first['final'][b] - o['U_final'])) / max(1.0, np.max(np.abs(o['U_final'])))
-                worst['final'] = max(worst['final'], err)
-                assert err <= U_ATOL, ('final unitary', b, stops[b], err)
-        print('  worst |device - oracle|: loop %s (bound %.0e); read-backs inter_vecs %.2e, final unitary %.2e (bound %.0e)' % (
-            ', '.join('%s %.2e' % (key, worst[key]) for key in ('base', 'uks', 'evaluated', 'scalars')), LOOP_ATOL, worst['inter'], worst['final'], U_ATOL))
+            for key, want in a.at(first['base'][b], b).items():
+                err = relative_error(first[key][b], want)
+                worst[key] = max(worst.get(key, 0.0), err)
+                assert err <= a.read_tol[key], (key, b, stops[b], err, a.read_tol[key])
+        print('  worst |device - reference| of the read-backs at each set\'s own final base: %s' % ', '.join(
+            '%s %.2e (bound %.0e)' % (key, v, a.read_tol[key]) for key, v in worst.items()))
         # 3. frozen, bit for bit: the same row with every set ended at s by max_iterations, polled as the first run.  Workgroup-resident rows with
         # several workgroups find the stop one exchange late and UNDO the step taken past it (csrc/qoc_small_kernel.h, "undo the step taken past the
         # stop") by copying the saved base, moments, controls and counters back, not by arithmetic: the base is compared bit for bit there as
@@ -362,28 +434,33 @@ def check_row(r, rule):
         if unitary and not tree_or_generic:
             np.testing.assert_array_equal(first['final_again'], first['final'], err_msg='the final unitary, read again after inter_vecs')
         for s in sorted(set(stops) - {MAX_IT}):
-            other = engine(r, sp)
+            other = a.build(B)
             try:
                 other.set_base(bases)
                 its2 = other.run_adam(other.adam_params(poll_every=poll, **dict(conv, conv_target=-1.0, min_grad=-1.0, max_iterations=s)))
                 assert list(its2) == [s] * B, (s, list(its2))
-                second = snapshot(other, unitary)
+                second = a.snapshot(other)
             finally:
                 other.close()
             for b in (b for b in range(B) if stops[b] == s):
                 for key in FROZEN:
                     if key in first and not (key == 'final' and tree_or_generic):
                         np.testing.assert_array_equal(first[key][b], second[key][b], err_msg='%s of set %d, finished at %d among running sets' % (key, b, s))
+        assert all(key in FROZEN or key in ('uks', 'iterations', 'done') for key in first), sorted(first)
         # 4. all done: three more launches of every kernel change nothing
         eng.iterate(p, 3)
         eng.sync()
-        after = snapshot(eng, unitary)
+        after = a.snapshot(eng)
         for key in first:
             np.testing.assert_array_equal(after[key], first[key], err_msg='%s after three iterations of finished sets' % key)
         # 5. set_base clears it
         eng.set_base(bases)
         again = eng.run_adam(p)
         assert list(again) == stops, (list(again), stops)
+        if a.full_again:
+            s2 = a.snapshot(eng)
+            for key in first:
+                np.testing.assert_array_equal(s2[key], first[key], err_msg='%s after set_base and the same loop' % key)
         np.testing.assert_array_equal(eng.get_base(), first['base'])
         s2 = eng.scalars()
         for key in s2:
@@ -396,4 +473,4 @@ def check_row(r, rule):
 @pytest.mark.parametrize('rule', RULES)
 @pytest.mark.parametrize('r', ROWS, ids=row_id)
 def test_finished_sets_stay_as_they_finished(r, rule):
-    check_row(r, rule)
+    check_row(r['name'], plain_adapter(r), rule)

@@ -47,9 +47,16 @@ ROWS = {
     'c1': (2, 20, 42, dict(c1=0.9), 10),         # runs of rejections
     'max_ls1': (2, 20, 41, dict(c1=0.9, max_ls=1), 10),           # the direction is reset
     'max_it4': (2, 20, 42, dict(c1=0.9, max_iterations=4), 8),    # a refused trial at the limit: restore, then stop
+    # more than QOC_LBFGS_COLS = 8 stored pairs: k_lbfgs_step forms its dots in further sub-passes, the Gram matrix grows to 33 x 33, the ring wraps at 16.
+    # Seeds and J chosen on the oracle (CPU) so that the margins stay wide: 'ks2048' seeds 41 .. 48 fall below 1e-8 from the 12th evaluation on.
+    # Measured on an MI355X against the reference driven by the twin engine: 3.8e-12 over the 40 steps of history16, 1.3e-13 (history9), 1.4e-16 (ks2048)
+    'history16': (2, 20, 42, dict(history=16), 40),               # 37 accepted, 3 rejected; 16 live pairs from evaluation 19 on, 20 wraps; worst margin 1.9e-6
+    'history9': (2, 20, 42, dict(history=9), 24),                 # the count crosses 8 with the last sub-pass partly filled; wraps from evaluation 11; 1.5e-5
+    'history16_ks2048': (8, 256, 45, dict(history=16), 11),       # ten pairs on the 1024-thread launch; worst margin 4e-7
 }
 ORACLE_ROWS = [r for r in ROWS if ROWS[r][0] * ROWS[r][1] <= 1025]
-EXPECT = {'wrap': 'wrapped', 'c1': ref.REJECT, 'max_ls1': ref.RESET, 'max_it4': ref.RESTORE, 'ks255': ref.REJECT}
+EXPECT = {'wrap': 'wrapped', 'c1': ref.REJECT, 'max_ls1': ref.RESET, 'max_it4': ref.RESTORE, 'ks255': ref.REJECT, 'history16': 'wrapped', 'history9': 'wrapped'}
+PAIRS = {'history16': 16, 'history9': 9, 'history16_ks2048': 10}          # the pairs alive after the row's last evaluation
 
 
 @functools.lru_cache(maxsize=None)
@@ -169,6 +176,10 @@ def test_steps_follow_the_reference(name):
         rec, _ = compare_with_reference(eng, engine_evaluator(twin), sp.base0, p, J, name)
         if name in EXPECT:
             assert rec['wrapped'] if EXPECT[name] == 'wrapped' else EXPECT[name] in rec['branch'], rec['branch']
+        if name in PAIRS:
+            assert len(rec['state'].S) == PAIRS[name] > 8, (len(rec['state'].S), rec['branch'])
+            if name == 'history16_ks2048':
+                assert sp.k * sp.steps >= 2048
     finally:
         eng.close()
         twin.close()
