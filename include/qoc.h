@@ -293,6 +293,33 @@ int qoc_get_final_density(qoc_handle h, double* rho);
 /* Re rho_ii(tau)[l][l] of the last evaluation, [n_seeds][steps+1][n][m] (tau = 0 is the start): the populations a closed run derives from inter_vecs */
 int qoc_get_populations(qoc_handle h, double* pop);
 
+/* ---- open-system ensembles and fleets: every member with its own decay rates ----------------------------------------------------------------
+ * A member of an ensemble, or of a device of a fleet, is a Hamiltonian AND its decay: member e of device f is the open problem above with the drift
+ * H0 + sum_q offsets[f][e][q] P_q, the controls amp_scales[f][e][j] H_j and the collapse operators sqrt(rate_scales[f][e][j]) C_j (a scale of 0
+ * switches the channel off for that member).  Per member everything is what qoc_create_open defines (the slice map with taylor_terms and 2^scaling
+ * sub-steps in both modes, the pairs i <= j, loss, unitary_scale, a zero state regulariser, the first-order gradient); per control set everything is
+ * what qoc_create_ensemble, qoc_create_shaped, qoc_create_mapped or qoc_create_fleet (whichever ens, fleet, transfer and map select) defines over
+ * those members: the weighted mean, the soft worst case of qoc_set_risk, the line, the map's chain rule, the device g / R, the stop rule, Adam and
+ * L-BFGS.  ens, fleet, transfer and map may each be NULL with the meaning they have in qoc_create_fleet; fleet NULL: one block of rows for every
+ * control set; all four NULL: one nominal member, and with scales of 1 the values of qoc_create_open, bit for bit.  A fleet of one device computes
+ * the values of the ensemble with its rows, bit for bit.
+ * qoc_set_risk, qoc_get_member_scalars, qoc_get_member_weights, qoc_get_pulse (with a line), qoc_get_coefficients (with a map) and every loop work as
+ * on any ensemble engine; qoc_get_final_density and qoc_get_populations return member 0 of each control set; qoc_get_final_unitary and
+ * qoc_get_inter_vecs stay QOC_ERR_STATE.  qoc_plan_describe: the open engine's line with what the ensemble entry points append.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: everything qoc_create_open refuses, everything the four ensemble entry
+ * points refuse about their own tables, and a negative or non-finite rate scale. */
+typedef struct qoc_decay {
+    int32_t n_collapse;          /* c, 0 .. 8 */
+    const double* C;             /* [c][n][n] complex: sqrt(dt) C_j at scale 1; NULL when c = 0 */
+    const double* rate_scales;   /* [F][E][c], finite, >= 0; NULL: ones (F = fleet->devices, or 1) */
+} qoc_decay;
+/* after map come exactly qoc_create_open's remaining arguments */
+int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const qoc_ensemble* ens, const qoc_fleet* fleet,
+                          const qoc_transfer* transfer, const qoc_control_map* map, const double* Hs, const double* U0, const double* V,
+                          const double* W, const double* maxA, const double* one_minus_gauss, qoc_handle* out);
+/* rho_ij(T) of every member at the last evaluation, [n_seeds][E][m][m][n][n] complex.  QOC_ERR_STATE on every other engine. */
+int qoc_get_member_final_density(qoc_handle h, double* rho);
+
 /* ---- sparse state transfer: the operators are never dense (the reference has sparse_H / sparse_U / sparse_K for systems built from Kronecker products
  * and switches them off under use_gpu, main_grape/grape.py:28-32) ----------------------------------------------------------------------------
  * The k + 1 operators -i dt H0, -i dt H_1 .. come as COO entries in any order; duplicates of a position are summed, explicit zeros are kept.  The

@@ -649,6 +649,15 @@ struct EnsArgs {
     const qoc_fleet* fleet;          // qoc_create_fleet: the checked member tables of the F devices (in place of ens' offsets and amp_scales), else null
 };
 
+// the decay of an open engine: the collapse operators and, on an ensemble or fleet (qoc_create_open_fleet), the rate scales of every member
+struct DecayHost {
+    int c;
+    const double* C;                 // [c][n][n] complex: sqrt(dt) C_j at scale 1
+    const double* scales;            // [F][E][c] or null (ones)
+    int F, E;                        // the rows of `scales` (1, 1: qoc_create_open)
+    const char* who;
+};
+
 // the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
 struct SparseHost {
     std::vector<QocEllOp> ops;       // [k+1]
@@ -659,6 +668,7 @@ struct SparseHost {
 struct Problem {
     const double *Hs, *U0, *V, *W, *maxA, *one_minus_gauss; const int32_t* forbidden_states; const double *forbidden_coeffs, *Vs;
     const SparseHost* sparse;
+    const DecayHost* decay;          // an open engine through the ensemble funnel (qoc_create_open_fleet), else null
 };
 
 static int check_create_args(const qoc_config* cfg, const Problem& p, qoc_handle* out) {
@@ -1057,13 +1067,15 @@ static int setup_group_view(qoc_engine* e, const EnsArgs& a) {
 }
 
 // the buffers of an open engine: collapse operators, the drift with -1/2 sum_j D_j^dagger D_j folded in, history, partials, populations
-static int setup_lindblad(qoc_engine* e, const Problem& p, const qoc_open* op) {
+// (per member of an ensemble or fleet: a row of drifts with its rate scales s_j on D_j^dagger D_j, and the row of sqrt(s_j) that the kernels put on D_j)
+static int setup_lindblad(qoc_engine* e, const Problem& p, const DecayHost* op) {
     const QocDev& d = e->d;
     QocLb& L = e->lb;
-    const int n = d.n, c = op->n_collapse;
+    const int n = d.n, c = op->c, rows = op->F * op->E;
     const size_t nn = (size_t)n * n, B = (size_t)d.B;
     L.on = 1; L.c = c; L.R = d.m * (d.m + 1) / 2; L.S = qoc_lb_stride(n); L.lds_bytes = qoc_lb_lds_bytes(n, c);
-    std::vector<double> h0(p.Hs, p.Hs + 2 * nn);
+    L.E = op->E; L.Rs = d.B / rows; L.rows = rows;
+    std::vector<double> dd(2 * nn * (size_t)c);                  // D_j^dagger D_j
     for (int j = 0; j < c; ++j) {
         const double* D = op->C + 2 * nn * (size_t)j;
         for (int a = 0; a < n; ++a)
@@ -1074,15 +1086,30 @@ static int setup_lindblad(qoc_engine* e, const Problem& p, const qoc_open* op) {
                     re += xr * yr + xi * yi;
                     im += xr * yi - xi * yr;
                 }
-                h0[2 * (a * n + b)] -= 0.5 * re; h0[2 * (a * n + b) + 1] -= 0.5 * im;
+                dd[2 * (nn * j + a * n + b)] = re; dd[2 * (nn * j + a * n + b) + 1] = im;
             }
     }
-    TRY(dev_upload(e, &L.H0, (const cplx*)h0.data(), nn));
+    std::vector<double> h0(2 * nn * (size_t)rows), rs;
+    if (op->scales) rs.resize((size_t)rows * c);
+    for (int row = 0; row < rows; ++row) {
+        double* h = h0.data() + 2 * nn * (size_t)row;
+        memcpy(h, p.Hs, 2 * nn * sizeof(double));
+        for (int j = 0; j < c; ++j) {
+            const double* x = dd.data() + 2 * nn * (size_t)j;
+            // (no table: the plain -= 0.5 x of qoc_create_open, nothing scaled)
+            if (!op->scales) { for (size_t i = 0; i < 2 * nn; ++i) h[i] -= 0.5 * x[i]; continue; }
+            const double sc = op->scales[(size_t)row * c + j];
+            rs[(size_t)row * c + j] = std::sqrt(sc);
+            for (size_t i = 0; i < 2 * nn; ++i) h[i] -= 0.5 * (sc * x[i]);
+        }
+    }
+    TRY(dev_upload(e, &L.H0, (const cplx*)h0.data(), nn * rows));
     if (c > 0) TRY(dev_upload(e, &L.D, (const cplx*)op->C, (size_t)c * nn));
+    if (c > 0 && op->scales) TRY(dev_upload(e, &L.rs, (const double*)rs.data(), rs.size()));
     TRY(dev_alloc(e, &L.hist, B * L.R * d.steps * nn));
     TRY(dev_alloc(e, &L.partial, B * L.R * d.k * d.steps));
     TRY(dev_alloc(e, &L.pop, B * (d.steps + 1) * n * d.m));
-    HIP_TRY_MSG(qoc_lb_lds_opt_in(L), "qoc_create_open: cannot reserve %zu bytes of LDS for the open-system kernels", L.lds_bytes);
+    HIP_TRY_MSG(qoc_lb_lds_opt_in(L), "%s: cannot reserve %zu bytes of LDS for the open-system kernels", op->who, L.lds_bytes);
     return QOC_OK;
 }
 
@@ -1118,7 +1145,8 @@ static int setup_sparse(qoc_engine* e, const SparseHost& h) {
     return QOC_OK;
 }
 
-static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out, const qoc_open* open = nullptr) {
+static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out, const DecayHost* open = nullptr) {
+    if (!open) open = p.decay;
     TRY(check_create_args(cfg, p, out));
     HIP_TRY(hipSetDevice(cfg->device));
     // the half-built engine owns itself: every early return below destroys it (fail() has set the message by then)
@@ -1203,30 +1231,37 @@ int qoc_create(const qoc_config* cfg, const double* Hs, const double* U0, const 
     return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, nullptr, out);
 }
 
+// what an open engine refuses, on the host and before any device is touched (`who`: qoc_create_open or qoc_create_open_fleet)
+static int check_open(const char* who, const qoc_config* cfg, int c, const double* C) {
+    const int n = cfg->n;
+    if (cfg->n_forbidden > 0) return fail(QOC_ERR_INVALID, "%s: forbidden levels are not available under a master equation (n_forbidden = %d)", who, cfg->n_forbidden);
+    if (cfg->has_speed_up) return fail(QOC_ERR_INVALID, "%s: the speed_up regulariser is not available under a master equation", who);
+    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "%s: forbid_dressed is not available under a master equation", who);
+    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "%s: the exact gradient is not available under a master equation (gradient = %d)", who, cfg->gradient);
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an open system cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
+    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_LINDBLAD)
+        return fail(QOC_ERR_INVALID, "%s: an open system runs on QOC_PATH_LINDBLAD (or AUTO), not on path %d", who, cfg->path);
+    if (c < 0 || (c > 0 && !C)) return fail(QOC_ERR_INVALID, "%s: n_collapse = %d (>= 0) with its operators", who, c);
+    if (n < 1 || n > QOC_LB_MAX_N) return fail(QOC_ERR_INVALID, "%s: n = %d (1 .. %d levels)", who, n, QOC_LB_MAX_N);
+    if (c > QOC_LB_MAX_C) return fail(QOC_ERR_INVALID, "%s: n_collapse = %d (at most %d collapse operators)", who, c, QOC_LB_MAX_C);
+    if (cfg->m < 1 || cfg->m > n) return fail(QOC_ERR_INVALID, "%s: m = %d states of interest (1 .. n = %d)", who, cfg->m, n);
+    if (qoc_lb_lds_bytes(n, c) > QOC_LB_LDS_LIMIT)
+        return fail(QOC_ERR_INVALID, "%s: n = %d with %d collapse operators needs %zu bytes of LDS (limit %zu)", who, n, c, qoc_lb_lds_bytes(n, c),
+                    QOC_LB_LDS_LIMIT);
+    if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_LB_MAX_T)
+        return fail(QOC_ERR_INVALID, "%s: taylor_terms = %d (1 .. %d)", who, cfg->taylor_terms, QOC_LB_MAX_T);
+    if (cfg->scaling < 0 || cfg->scaling > QOC_LB_MAX_S) return fail(QOC_ERR_INVALID, "%s: scaling = %d (0 .. %d)", who, cfg->scaling, QOC_LB_MAX_S);
+    for (size_t i = 0; i < 2 * (size_t)c * n * n; ++i)
+        if (!std::isfinite(C[i])) return fail(QOC_ERR_INVALID, "%s: a collapse operator is not finite", who);
+    return QOC_OK;
+}
+
 int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* Hs, const double* U0, const double* V, const double* W,
                     const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
     if (!cfg || !open || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_open: null argument");
-    const int n = cfg->n, c = open->n_collapse;
-    if (cfg->n_forbidden > 0) return fail(QOC_ERR_INVALID, "qoc_create_open: forbidden levels are not available under a master equation (n_forbidden = %d)", cfg->n_forbidden);
-    if (cfg->has_speed_up) return fail(QOC_ERR_INVALID, "qoc_create_open: the speed_up regulariser is not available under a master equation");
-    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "qoc_create_open: forbid_dressed is not available under a master equation");
-    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "qoc_create_open: the exact gradient is not available under a master equation (gradient = %d)", cfg->gradient);
-    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_open: an open system cannot be time-sharded (time_shards = %d)", cfg->time_shards);
-    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_LINDBLAD)
-        return fail(QOC_ERR_INVALID, "qoc_create_open: an open system runs on QOC_PATH_LINDBLAD (or AUTO), not on path %d", cfg->path);
-    if (c < 0 || (c > 0 && !open->C)) return fail(QOC_ERR_INVALID, "qoc_create_open: n_collapse = %d (>= 0) with its operators", c);
-    if (n < 1 || n > QOC_LB_MAX_N) return fail(QOC_ERR_INVALID, "qoc_create_open: n = %d (1 .. %d levels)", n, QOC_LB_MAX_N);
-    if (c > QOC_LB_MAX_C) return fail(QOC_ERR_INVALID, "qoc_create_open: n_collapse = %d (at most %d collapse operators)", c, QOC_LB_MAX_C);
-    if (cfg->m < 1 || cfg->m > n) return fail(QOC_ERR_INVALID, "qoc_create_open: m = %d states of interest (1 .. n = %d)", cfg->m, n);
-    if (qoc_lb_lds_bytes(n, c) > QOC_LB_LDS_LIMIT)
-        return fail(QOC_ERR_INVALID, "qoc_create_open: n = %d with %d collapse operators needs %zu bytes of LDS (limit %zu)", n, c, qoc_lb_lds_bytes(n, c),
-                    QOC_LB_LDS_LIMIT);
-    if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_LB_MAX_T)
-        return fail(QOC_ERR_INVALID, "qoc_create_open: taylor_terms = %d (1 .. %d)", cfg->taylor_terms, QOC_LB_MAX_T);
-    if (cfg->scaling < 0 || cfg->scaling > QOC_LB_MAX_S) return fail(QOC_ERR_INVALID, "qoc_create_open: scaling = %d (0 .. %d)", cfg->scaling, QOC_LB_MAX_S);
-    for (size_t i = 0; i < 2 * (size_t)c * n * n; ++i)
-        if (!std::isfinite(open->C[i])) return fail(QOC_ERR_INVALID, "qoc_create_open: a collapse operator is not finite");
-    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, open);
+    TRY(check_open("qoc_create_open", cfg, open->n_collapse, open->C));
+    const DecayHost dh{open->n_collapse, open->C, nullptr, 1, 1, "qoc_create_open"};
+    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, &dh);
 }
 
 int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
@@ -1281,12 +1316,21 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
     if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "%s: d2wdt2 needs dwdt (reference: NameError new_weights)", who);
     for (int i = 0; i < E; ++i)
         if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "%s: weight %d is %g", who, i, ens->weights[i]);
+    // (qoc_create_open_fleet: the members' rate scales, a row of c for each of the F E members just checked)
+    if (p.decay && p.decay->scales) {
+        const size_t c = (size_t)p.decay->c, rows = (size_t)(fleet ? fleet->devices : 1) * E;
+        for (size_t i = 0; i < rows * c; ++i) {
+            const double v = p.decay->scales[i];
+            if (!std::isfinite(v) || v < 0.0)
+                return fail(QOC_ERR_INVALID, "%s: rate_scales[%zu][%zu][%zu] is %g (finite, >= 0)", who, i / ((size_t)E * c), (i / c) % E, i % c, v);
+        }
+    }
     // paths whose tail runs inside their own launch, or that form their controls from the variable, cannot host the member reduction
     // (checked before any device is touched)
     if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an ensemble cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
     if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "%s: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
         "inside its launch, where the members' gradients cannot be reduced first", who);
-    if (cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
+    if (!p.decay && cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
         "%s: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail", who);
     // (a control map: the trajectories run the r operators the map feeds)
     const int kt = map ? map->n_terms : cfg->k;
@@ -1409,10 +1453,9 @@ int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_
 
 // the fleet's own checks, on the host and before any device is touched; then the ensemble's entry point that transfer and map select, with the
 // fleet's tables in place of the ensemble's (ens: members, n_perturb, P and weights only; null: one member per device, no perturbation)
-int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map,
-                     const double* Hs, const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
-                     const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    const char* who = "qoc_create_fleet";
+static int create_fleet(const char* who, const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
+                        const qoc_control_map* map, const Problem& p, qoc_handle* out) {
+    const double* maxA = p.maxA;
     if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     if (!fleet) return fail(QOC_ERR_INVALID, "%s: the fleet is missing", who);
     if (!fleet->amp_scales) return fail(QOC_ERR_INVALID, "%s: the fleet's amp_scales are missing", who);
@@ -1435,10 +1478,38 @@ int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_f
             return fail(QOC_ERR_INVALID, "%s: offsets[%zu][%zu][%zu] is not finite", who, i / per_d, (i / q) % E, i % q);
     // (the ensemble's own tables are not read on a fleet)
     members.offsets = nullptr; members.amp_scales = nullptr;
-    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
     if (map) TRY(check_map(who, cfg, map, maxA));
     if (tr || map) return create_shaped(who, cfg, &members, tr, map, p, out, fleet);
     return create_members(who, nullptr, cfg, &members, p, out, nullptr, fleet);
+}
+
+int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map,
+                     const double* Hs, const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                     const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    return create_fleet("qoc_create_fleet", cfg, ens, fleet, tr, map,
+                        Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
+}
+
+// an open engine through the ensemble funnel: the open engine's own refusals and the rate scales checked here, everything about the member tables,
+// the line and the map by the entry point that ens, fleet, transfer and map select -- all on the host and before any device is touched
+int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
+                          const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
+                          const double* one_minus_gauss, qoc_handle* out) {
+    const char* who = "qoc_create_open_fleet";
+    if (!cfg || !decay || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    const int c = decay->n_collapse;
+    TRY(check_open(who, cfg, c, decay->C));
+    // (F and E bound the table of rate scales: create_fleet and create_members check them, and create_members the table once they hold)
+    const int F = fleet ? fleet->devices : 1, E = ens ? ens->members : 1;
+    const DecayHost dh{c, decay->C, c > 0 ? decay->rate_scales : nullptr, F, E, who};
+    Problem p{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr};
+    p.decay = &dh;
+    if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
+    if (map) TRY(check_map(who, cfg, map, maxA));
+    if (tr || map) return create_shaped(who, cfg, ens, tr, map, p, out);
+    const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
+    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
+    return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1707,29 +1778,46 @@ int qoc_get_inter_vecs(qoc_handle e, double* inter) {
     return QOC_OK;
 }
 
+// rho_ij(T) of trajectory b, [m][m][n][n] complex: the pairs i > j mirrored from rho_ji
+static int read_density(qoc_engine* e, size_t b, double* rho) {
+    const QocDev& d = e->d;
+    const int n = d.n, m = d.m, R = e->lb.R;
+    const size_t nn = (size_t)n * n;
+    std::vector<cplx> blk(nn);
+    for (int i = 0, r = 0; i < m; ++i)
+        for (int j = i; j < m; ++j, ++r) {
+            HIP_TRY(hipMemcpy(blk.data(), e->lb.hist + ((b * R + r) * d.steps + (d.steps - 1)) * nn, nn * sizeof(cplx), hipMemcpyDeviceToHost));
+            double* up = rho + 2 * (((size_t)i * m + j) * nn);
+            double* lo = rho + 2 * (((size_t)j * m + i) * nn);
+            for (int a = 0; a < n; ++a)
+                for (int c = 0; c < n; ++c) {
+                    const cplx v = blk[(size_t)a * n + c];
+                    up[2 * (a * n + c)] = v.x; up[2 * (a * n + c) + 1] = v.y;
+                    if (i != j) { lo[2 * (c * n + a)] = v.x; lo[2 * (c * n + a) + 1] = -v.y; }   // rho_ji = rho_ij^dagger
+                }
+        }
+    return QOC_OK;
+}
+
 int qoc_get_final_density(qoc_handle e, double* rho) {
     CHECK_H(e);
     if (!e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_final_density: not an open engine (qoc_create_open)");
     if (!rho) return fail(QOC_ERR_INVALID, "qoc_get_final_density: null output");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_final_density: nothing evaluated yet");
     HIP_TRY(hipStreamSynchronize(e->stream));
-    const QocDev& d = e->d;
-    const int n = d.n, m = d.m, R = e->lb.R;
-    const size_t nn = (size_t)n * n;
-    std::vector<cplx> blk(nn);
-    for (int b = 0; b < d.B; ++b)
-        for (int i = 0, r = 0; i < m; ++i)
-            for (int j = i; j < m; ++j, ++r) {
-                HIP_TRY(hipMemcpy(blk.data(), e->lb.hist + (((size_t)b * R + r) * d.steps + (d.steps - 1)) * nn, nn * sizeof(cplx), hipMemcpyDeviceToHost));
-                double* up = rho + 2 * ((((size_t)b * m + i) * m + j) * nn);
-                double* lo = rho + 2 * ((((size_t)b * m + j) * m + i) * nn);
-                for (int a = 0; a < n; ++a)
-                    for (int c = 0; c < n; ++c) {
-                        const cplx v = blk[(size_t)a * n + c];
-                        up[2 * (a * n + c)] = v.x; up[2 * (a * n + c) + 1] = v.y;
-                        if (i != j) { lo[2 * (c * n + a)] = v.x; lo[2 * (c * n + a) + 1] = -v.y; }   // rho_ji = rho_ij^dagger
-                    }
-            }
+    const size_t per = 2 * (size_t)e->d.m * e->d.m * e->d.n * e->d.n, E = e->ens_E ? (size_t)e->ens_E : 1;      // (an ensemble: member 0 of each control set)
+    for (size_t g = 0; g < (size_t)sets(e).B; ++g) TRY(read_density(e, g * E, rho + g * per));
+    return QOC_OK;
+}
+
+int qoc_get_member_final_density(qoc_handle e, double* rho) {
+    CHECK_H(e);
+    if (!e->lb.on || !e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_final_density: not an open ensemble engine (qoc_create_open_fleet)");
+    if (!rho) return fail(QOC_ERR_INVALID, "qoc_get_member_final_density: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_member_final_density: nothing evaluated yet");
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t per = 2 * (size_t)e->d.m * e->d.m * e->d.n * e->d.n;
+    for (size_t b = 0; b < (size_t)e->d.B; ++b) TRY(read_density(e, b, rho + b * per));
     return QOC_OK;
 }
 
@@ -1739,11 +1827,13 @@ int qoc_get_populations(qoc_handle e, double* pop) {
     if (!pop) return fail(QOC_ERR_INVALID, "qoc_get_populations: null output");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_populations: nothing evaluated yet");
     const QocDev& d = e->d;
-    const size_t total = (size_t)d.B * (d.steps + 1) * d.n * d.m;
+    const size_t row = (size_t)(d.steps + 1) * d.n * d.m, total = (size_t)d.B * row;
     hipLaunchKernelGGL(k_lb_populations, dim3(grid_for(total, QOC_BLOCK, 2048)), dim3(QOC_BLOCK), 0, e->stream, d, e->lb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(pop, e->lb.pop, total * sizeof(double), hipMemcpyDeviceToHost));
+    if (e->ens_E)                                                      // member 0 of each control set
+        HIP_TRY(hipMemcpy2D(pop, row * sizeof(double), e->lb.pop, row * sizeof(double) * e->ens_E, row * sizeof(double), (size_t)e->g.B, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy(pop, e->lb.pop, total * sizeof(double), hipMemcpyDeviceToHost));
     return QOC_OK;
 }
 
@@ -1798,6 +1888,7 @@ int qoc_get_member_weights(qoc_handle e, double* pi) {
 int qoc_get_member_final_unitary(qoc_handle e, double* Uf) {
     CHECK_H(e);
     if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: not an ensemble engine (qoc_create_ensemble)");
+    if (e->lb.on) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: an open engine has no final unitary (qoc_get_member_final_density)");
     if (!Uf) return fail(QOC_ERR_INVALID, "qoc_get_member_final_unitary: null output");
     if (e->d.state_transfer) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: state-transfer mode has no final unitary");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: nothing evaluated yet");
@@ -1851,7 +1942,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 // sweeps=<downup|split|row_tile_gradient|latency|latency_sources|one_wave>
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
-//   open engines (qoc_create_open): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
+//   open engines (qoc_create_open, qoc_create_open_fleet): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
 //   sparse engines (qoc_create_sparse): path=sparse nnz=<stored entries> ell=<W_0,..,W_k> vector_home=<lds|global> lds=<bytes of dynamic LDS> threads=<256|1024 of a sweep>
 //   grad_grid=<workgroups of k_sp_grad>
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>

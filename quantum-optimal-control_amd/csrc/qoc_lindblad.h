@@ -25,6 +25,11 @@
 // a row stride of n complex numbers these are n * 16 bytes apart, and at n = 32 (512 bytes = two bank rows) all sixteen fall on the same four
 // banks.  The row stride is therefore S = n | 1 complex numbers: S odd makes 4 S mod 64 an odd multiple of 4, so sixteen consecutive rows start on
 // sixteen different 16-byte slots of the 256-byte bank row.  (c + 4) n S 16 bytes <= 159 KiB with n <= 32, c <= 8, m <= n; no global-memory variant.
+//
+// Decay per member (qoc_create_open_fleet): the trajectories of an ensemble or fleet engine share the operators D_j and differ in their rates.  Member e of
+// device f has the collapse operators sqrt(s[f][e][j]) D_j, so two tables of F E rows stand where one drift stood: H0[row] = H0' - 1/2 sum_j s_j D_j^dagger D_j
+// (formed on the host) and rs[row][j] = sqrt(s_j), which lb_setup multiplies into D_j on its way into LDS.  Trajectory b reads row ((b / E) / Rs) E + b % E
+// (E members, Rs control sets per device: the member block of qoc_ensemble.h).  An engine of qoc_create_open has one row and no rs: nothing is scaled.
 #pragma once
 #include "qoc_common.h"
 
@@ -38,11 +43,14 @@
 struct QocLb {
     int on, c, R, S;                // collapse operators, pairs i <= j, LDS row stride in complex numbers
     size_t lds_bytes;
-    const cplx* D;                  // [c][n][n] sqrt(dt) C_j
-    const cplx* H0;                 // [n][n] the drift H0' - 1/2 sum_j D_j^dagger D_j
+    const cplx* D;                  // [c][n][n] sqrt(dt) C_j at rate scale 1
+    const cplx* H0;                 // [rows][n][n] the drift H0' - 1/2 sum_j s_j D_j^dagger D_j
     cplx* hist;                     // [B][R][steps][n][n] rho(t+1) of the last evaluation
     double* partial;                // [B][R][k][steps] a pair's share of dL/du
     double* pop;                    // [B][steps+1][n][m] populations (formed on read-back)
+    // the member axis, behind what a one-row engine reads
+    const double* rs;               // [rows][c] sqrt(s_j), or null: every scale is 1 and D_j is copied as it is
+    int E, Rs, rows;                // members per control set, control sets per device, rows of H0 and rs (F E; 1: qoc_create_open)
 };
 
 static inline int qoc_lb_stride(int n) { return n | 1; }
@@ -70,15 +78,22 @@ __device__ __forceinline__ LbOwn lb_own(int n, int S) {
     return w;
 }
 
+// the row of L.H0 and L.rs that trajectory b reads
+__device__ __forceinline__ int lb_row(const QocLb& L, int b) {
+    const int g = b / L.E;
+    return (g / L.Rs) * L.E + (b - g * L.E);
+}
+
 // A = (H0eff + sum_k u_k[t] H_k') / N into LDS rows of stride S (wg_assemble's sum, in its order)
-__device__ __forceinline__ void lb_assemble(const QocDev& d, const QocLb& L, int b, int t, double inv_n, const LbOwn& w, cplx* __restrict__ A) {
+__device__ __forceinline__ void lb_assemble(const QocDev& d, const QocLb& L, const cplx* __restrict__ H0, int b, int t, double inv_n, const LbOwn& w,
+                                            cplx* __restrict__ A) {
     const int nn = d.n * d.n;
     const double* ub = d.u + (size_t)b * d.k * d.steps + t;
 #pragma unroll
     for (int e = 0; e < QOC_LB_E; ++e) {
         if (w.at[e] < 0) continue;
         const int o = threadIdx.x + e * QOC_BLOCK;
-        cplx acc = cscale(L.H0[o], inv_n);
+        cplx acc = cscale(H0[o], inv_n);
         for (int kk = 0; kk < d.k; ++kk) {
             const double c = ub[(size_t)kk * d.steps] * inv_n;
             const cplx h = d.Hs[(size_t)(kk + 1) * nn + o];
@@ -160,9 +175,10 @@ __device__ __forceinline__ void lb_slice(int n, int S, int c, int T, int N, doub
     }
 }
 
-// what both sweeps set up: the 1 / j! table, the LDS carve-up, D_j into LDS
+// what both sweeps set up: the 1 / j! table, the LDS carve-up, D_j (times the row's sqrt(s_j) where there is a table) into LDS
 struct LbLds { cplx *A, *D, *X, *term, *tmp; };
-__device__ __forceinline__ LbLds lb_setup(const QocDev& d, const QocLb& L, cplx* lds, double* ifc) {
+template <bool ROWS>
+__device__ __forceinline__ LbLds lb_setup(const QocDev& d, const QocLb& L, int row, cplx* lds, double* ifc) {
     const int n = d.n, S = L.S, mat = n * S;
     LbLds s;
     s.A = lds; s.D = s.A + mat; s.X = s.D + (size_t)L.c * mat; s.term = s.X + mat; s.tmp = s.term + mat;
@@ -173,11 +189,16 @@ __device__ __forceinline__ LbLds lb_setup(const QocDev& d, const QocLb& L, cplx*
     }
     for (int o = threadIdx.x; o < L.c * n * n; o += QOC_BLOCK) {
         const int q = o / (n * n), rc = o - q * n * n, r = rc / n;
-        s.D[(size_t)q * mat + r * S + (rc - r * n)] = L.D[o];
+        cplx v = L.D[o];
+        if (ROWS && L.rs) v = cscale(v, L.rs[(size_t)row * L.c + q]);
+        s.D[(size_t)q * mat + r * S + (rc - r * n)] = v;
     }
     return s;
 }
 
+// ROWS: the engine has a row per member (qoc_create_open_fleet); false is the one-row engine of qoc_create_open, whose sweeps read L.H0 and
+// L.D as they are -- the kernels it always ran
+template <bool ROWS>
 __global__ void __launch_bounds__(QOC_BLOCK) k_lb_forward(QocDev d, QocLb L) {
     extern __shared__ __attribute__((aligned(16))) cplx lb_lds[];
     __shared__ double ifc[QOC_LB_MAX_T + 2];
@@ -186,7 +207,9 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_forward(QocDev d, QocLb L) {
     const int n = d.n, m = d.m, nn = n * n, N = 1 << d.s;
     const double inv_n = 1.0 / (double)N;
     const LbOwn w = lb_own(n, L.S);
-    const LbLds s = lb_setup(d, L, lb_lds, ifc);
+    const int row = ROWS ? lb_row(L, b) : 0;
+    const cplx* H0 = ROWS ? L.H0 + (size_t)row * nn : L.H0;
+    const LbLds s = lb_setup<ROWS>(d, L, row, lb_lds, ifc);
     int pi, pj;
     lb_pair(r, m, pi, pj);
     // rho_ij(0) = psi_i psi_j^dagger
@@ -195,7 +218,7 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_forward(QocDev d, QocLb L) {
         if (w.at[e] >= 0) s.X[w.at[e]] = cmul(d.Psi0[w.row[e] * m + pi], cconj(d.Psi0[w.col[e] * m + pj]));
     cplx* hist = L.hist + ((size_t)b * L.R + r) * d.steps * nn;
     for (int t = 0; t < d.steps; ++t) {
-        lb_assemble(d, L, b, t, inv_n, w, s.A);
+        lb_assemble(d, L, H0, b, t, inv_n, w, s.A);
         lb_slice<false>(n, L.S, L.c, d.T, N, inv_n, w, s.A, s.D, s.X, s.term, s.tmp, ifc);
 #pragma unroll
         for (int e = 0; e < QOC_LB_E; ++e)
@@ -203,6 +226,7 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_forward(QocDev d, QocLb L) {
     }
 }
 
+template <bool ROWS>
 __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
     extern __shared__ __attribute__((aligned(16))) cplx lb_lds[];
     __shared__ double ifc[QOC_LB_MAX_T + 2];
@@ -212,7 +236,9 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
     const int n = d.n, m = d.m, nn = n * n, N = 1 << d.s, S = L.S;
     const double inv_n = 1.0 / (double)N;
     const LbOwn w = lb_own(n, S);
-    const LbLds s = lb_setup(d, L, lb_lds, ifc);
+    const int row = ROWS ? lb_row(L, b) : 0;
+    const cplx* H0 = ROWS ? L.H0 + (size_t)row * nn : L.H0;
+    const LbLds s = lb_setup<ROWS>(d, L, row, lb_lds, ifc);
     int pi, pj;
     lb_pair(r, m, pi, pj);
     const double weight = pi == pj ? 1.0 : 2.0, c0 = -1.0 / ((double)m * (double)m);
@@ -248,7 +274,7 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
             if (threadIdx.x == 0) part_out[(size_t)kk * d.steps + t] = weight * g;
         }
         __syncthreads();                                      // (k = 0 never happens; the readers of rho are behind block_sum's barriers)
-        lb_assemble(d, L, b, t, inv_n, w, s.A);
+        lb_assemble(d, L, H0, b, t, inv_n, w, s.A);
         lb_slice<true>(n, S, L.c, d.T, N, inv_n, w, s.A, s.D, s.X, s.term, s.tmp, ifc);
     }
 }
@@ -301,19 +327,26 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_populations(QocDev d, QocLb L)
     }
 }
 
+// whether the engine has member rows to pick and scale by (one row of scales counts: a single member whose rates are not the nominal ones)
+static inline bool qoc_lb_member_rows(const QocLb& L) { return L.rows > 1 || L.rs != nullptr; }
 // the three launches of an open engine's evaluation
 static inline void qoc_lb_forward(const QocLb& L, const QocDev& d, hipStream_t s) {
-    hipLaunchKernelGGL(k_lb_forward, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+    if (qoc_lb_member_rows(L)) hipLaunchKernelGGL(k_lb_forward<true>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+    else hipLaunchKernelGGL(k_lb_forward<false>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
 }
 static inline void qoc_lb_backward(const QocLb& L, const QocDev& d, hipStream_t s) {
-    hipLaunchKernelGGL(k_lb_backward, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+    if (qoc_lb_member_rows(L)) hipLaunchKernelGGL(k_lb_backward<true>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+    else hipLaunchKernelGGL(k_lb_backward<false>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
     hipLaunchKernelGGL(k_lb_reduce, dim3((unsigned)d.B), dim3(QOC_BLOCK), 0, s, d, L);
 }
 // Above 64 KiB of dynamic LDS a kernel has to be opted in.  The attribute belongs to the kernel for the whole process, not to an engine, so it is
 // set to the size rule's limit -- never to this engine's own footprint, which would lower it under a larger open engine that is still alive.
 static inline hipError_t qoc_lb_lds_opt_in(const QocLb& L) {
     if (L.lds_bytes <= 64 * 1024) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute((const void*)k_lb_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QOC_LB_LDS_LIMIT);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_lb_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QOC_LB_LDS_LIMIT);
+    const void* kernels[] = {(const void*)k_lb_forward<false>, (const void*)k_lb_backward<false>, (const void*)k_lb_forward<true>, (const void*)k_lb_backward<true>};
+    for (const void* f : kernels) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QOC_LB_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }

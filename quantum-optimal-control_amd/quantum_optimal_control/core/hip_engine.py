@@ -54,6 +54,10 @@ class QocOpen(C.Structure):
     _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double))]
 
 
+class QocDecay(C.Structure):
+    _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double)), ('rate_scales', C.POINTER(C.c_double))]
+
+
 class QocSparse(C.Structure):
     _fields_ = [('indptr', C.POINTER(C.c_int64)), ('row', C.POINTER(C.c_int32)), ('col', C.POINTER(C.c_int32)), ('val', C.POINTER(C.c_double)),
                 ('vector_home', C.c_int32)]
@@ -85,6 +89,9 @@ _SIGNATURES = {
     'qoc_create_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocEnsemble), C.POINTER(QocFleet), C.POINTER(QocTransfer),
                                    C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_open': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocOpen), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_open_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocDecay), C.POINTER(QocEnsemble), C.POINTER(QocFleet), C.POINTER(QocTransfer),
+                                        C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_get_member_final_density': (C.c_int, [C.c_void_p, _DP]),
     'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_populations': (C.c_int, [C.c_void_p, _DP]),
@@ -338,6 +345,38 @@ def fleet_arrays(fleet, E, q, k):
     return off, amp
 
 
+def decay_arrays(ensemble, fleet, n, E, dt):
+    """The decay an ensemble dict (keys collapse_ops, rate_scales (E, c)) or a fleet (attributes or keys collapse_ops, rate_scales (F, E, c)) carries,
+    as the C ABI's qoc_decay arrays: (D = sqrt(dt) C_j stacked (c, n, n), rate_scales (F, E, c) with F = 1 for an ensemble), or None without decay.
+    The fleet's decay stands in front of the ensemble's (Grape hands device 0 of a fleet over as its ensemble)."""
+    from quantum_optimal_control.helper_functions import open_system
+    get = (lambda key: None) if fleet is None else (fleet.get if isinstance(fleet, dict) else lambda key: getattr(fleet, key, None))
+    ops, rates, lead = get('collapse_ops'), get('rate_scales'), 'fleet'
+    if ops is None:
+        if get('rate_scales') is not None:
+            raise ValueError('HipEngine: fleet rate_scales given without collapse_ops')
+        if ensemble is None or ensemble.get('collapse_ops') is None:
+            if ensemble is not None and ensemble.get('rate_scales') is not None:
+                raise ValueError('HipEngine: ensemble rate_scales given without collapse_ops')
+            return None
+        ops, rates, lead = ensemble['collapse_ops'], ensemble.get('rate_scales'), 'ensemble'
+        if rates is not None:
+            rates = np.asarray(rates, dtype=np.float64)[None]
+    ops = open_system.validate(list(ops), n)
+    c = len(ops)
+    if rates is None:
+        F = 1 if (fleet is None or lead == 'ensemble') else np.shape(get('amp_scales'))[0]
+        rates = np.ones((F, E, c))
+    rates = np.ascontiguousarray(np.asarray(rates, dtype=np.float64))
+    if rates.ndim != 3 or rates.shape[1:] != (E, c):
+        raise ValueError('HipEngine: %s rate_scales have shape %s, expected (%s%d, %d)' % (lead, rates.shape[1:] if lead == 'ensemble' else rates.shape,
+                                                                                          '' if lead == 'ensemble' else 'F, ', E, c))
+    if not np.all(np.isfinite(rates)) or np.any(rates < 0):
+        raise ValueError('HipEngine: %s rate_scales must be finite and >= 0' % lead)
+    D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(ops, dtype=np.complex128).reshape(c, n, n))
+    return D, rates
+
+
 VECTOR_HOME = {None: 0, 'auto': 0, 'lds': 1, 'global': 2}
 
 
@@ -397,13 +436,33 @@ class HipEngine(object):
     (F x E x k).  n_seeds = F R control sets, device-major: control set g is optimised on device g // R's members.  `ensemble` then supplies the
     operators, the weights and the risk (its offsets and amp_scales are not read; a Fleet brings its own when `ensemble` is None; neither: one
     member per device, no perturbation).  self.devices is F; every read-back keeps its (n_seeds, ...) shape.  Composes with transfer, control_map
-    and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is loaded)."""
+    and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is loaded).
+
+    decay per member (open-system ensembles and fleets, include/qoc.h qoc_create_open_fleet): an `ensemble` dict with the keys `collapse_ops` (c
+    operators as collapse_ops= takes them) and `rate_scales` (E x c, default ones), or a `fleet` with collapse_ops and rate_scales (F x E x c).  Member
+    e of device f is then the open problem with the collapse operators sqrt(rate_scales[f, e, j]) C_j; self.open_system is True, get_final_density()
+    and get_populations() give member 0 of each control set, member_final_density() every member, and everything an ensemble engine offers (risk,
+    member read-backs, transfer, control_map, the loops) works as it does there.  Not together with the collapse_ops= keyword, exact_gradient,
+    sparse_ops or time sharding (ValueError, before the library is loaded)."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
                  sparse_ops=None, vector_home=None, control_map=None, fleet=None):
         sparse = None
+        decay = None
+        if (ensemble is not None or fleet is not None) and sparse_ops is None:
+            # (before the fleet's own refusal of collapse_ops=: decay that the members carry is named as such)
+            if fleet is not None and ensemble is None and not isinstance(fleet, dict):
+                E_members = int(np.shape(fleet.amp_scales)[1])
+            else:
+                E_members = 1 if ensemble is None else int(np.shape(ensemble['amp_scales'])[0])
+            decay = decay_arrays(ensemble, fleet, int(np.shape(Hs)[1]), E_members, dt)
+        if decay is not None:
+            for name, given in (('the collapse_ops= keyword (the members carry the decay)', collapse_ops is not None),
+                                ('exact_gradient', bool(exact_gradient)), ('time sharding', time_comm is not None or int(time_shards) > 0)):
+                if given:
+                    raise ValueError('HipEngine: an ensemble or fleet with decay does not combine with %s' % name)
         if fleet is not None:
             for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
@@ -484,7 +543,7 @@ class HipEngine(object):
                 _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
                 C.byref(self._h))
         self.members = 0
-        self.open_system = collapse_ops is not None
+        self.open_system = collapse_ops is not None or decay is not None
         self.samples = None                           # transfer-function GRAPE: P, the length of the variable's rows
         ens = None
         if ensemble is not None:
@@ -497,7 +556,7 @@ class HipEngine(object):
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
         tr = None
         self.devices = 0                              # device fleets: F, the devices the n_seeds control sets are spread over
-        if transfer is not None and (control_map is not None or fleet is not None):
+        if transfer is not None:
             T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
             if T.ndim != 2 or T.shape[0] != int(steps):
                 raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
@@ -508,10 +567,25 @@ class HipEngine(object):
             cmap = QocControlMap()
             cmap.n_terms, cmap.degree = control_map.n_terms, control_map.degree
             cmap.poly, cmap.mix, cmap.fixed = _dp(control_map.alpha), _dp(control_map.mix), _dp(control_map.fixed)
+        fl = None
         if fleet is not None:
             foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
             fl = QocFleet()
             fl.devices, fl.offsets, fl.amp_scales = famp.shape[0], (_dp(foff) if foff.shape[2] else None), _dp(famp)
+        if decay is not None:
+            D, rates = decay
+            if fl is not None and rates.shape[0] != fl.devices:
+                raise ValueError('HipEngine: rate_scales are for %d devices, the fleet has %d' % (rates.shape[0], fl.devices))
+            if fl is None and rates.shape[0] != 1:
+                raise ValueError('HipEngine: rate_scales with a device axis need a fleet')
+            dc = QocDecay()
+            dc.n_collapse, dc.C, dc.rate_scales = D.shape[0], (_dp(D.view(np.float64)) if D.shape[0] else None), (_dp(rates) if D.shape[0] else None)
+            _check(lib.qoc_create_open_fleet(C.byref(cfg), C.byref(dc), None if ens is None else C.byref(ens), None if fl is None else C.byref(fl),
+                                             None if tr is None else C.byref(tr), None if cmap is None else C.byref(cmap), *(args[:6] + args[-1:])))
+            if tr is not None:
+                self.samples = int(tr.n_samples)
+            self.devices = 0 if fl is None else int(fl.devices)
+        elif fleet is not None:
             _check(lib.qoc_create_fleet(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(fl), None if tr is None else C.byref(tr),
                                         None if cmap is None else C.byref(cmap), *args))
             if tr is not None:
@@ -533,14 +607,9 @@ class HipEngine(object):
             op = QocOpen()
             op.n_collapse, op.C = len(collapse_ops), (_dp(D.view(np.float64)) if len(collapse_ops) else None)
             _check(lib.qoc_create_open(C.byref(cfg), C.byref(op), *(args[:6] + args[-1:])))
-        elif transfer is not None:
-            T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
-            if T.ndim != 2 or T.shape[0] != int(steps):
-                raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
-            tr = QocTransfer()
-            tr.n_samples, tr.T = T.shape[1], _dp(T)
+        elif tr is not None:
             _check(lib.qoc_create_shaped(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(tr), *args))
-            self.samples = int(T.shape[1])
+            self.samples = int(tr.n_samples)
         elif ens is None:
             _check(lib.qoc_create(C.byref(cfg), *args))
         else:
@@ -679,6 +748,12 @@ class HipEngine(object):
         """Open engines: rho_ij(T) of the last evaluation, (n_seeds, m, m, n, n); [g, i, i] is the density matrix state i ends in."""
         out = np.empty((self.n_seeds, self.m, self.m, self.n, self.n), dtype=np.complex128)
         _check(self._lib.qoc_get_final_density(self._h, _dp(out.view(np.float64))))
+        return out
+
+    def member_final_density(self):
+        """Open ensemble and fleet engines: rho_ij(T) of every member at the last evaluation, (n_seeds, members, m, m, n, n)."""
+        out = np.empty((self.n_seeds, max(self.members, 1), self.m, self.m, self.n, self.n), dtype=np.complex128)
+        _check(self._lib.qoc_get_member_final_density(self._h, _dp(out.view(np.float64))))
         return out
 
     def get_populations(self):

@@ -5,6 +5,9 @@ H0 + sum_q offsets[f, e, q] P_q and the control Hamiltonians amp_scales[f, e, j]
 weights and the risk, the targets, the states of interest, maxA, the regularisers, the line and the control map; nothing else couples them.
 One engine holds R control sets per device (``restarts=R``), device-major, and optimises every device's own pulse in the same launches
 (include/qoc.h, qoc_create_fleet).
+
+Decay per device: a fleet may carry collapse_ops (c operators as Grape(collapse_ops=...) takes them, shared by the devices) and rate_scales
+(F, E, c): member e of device f decays through sqrt(rate_scales[f, e, j]) C_j, and every member is an open problem (qoc_create_open_fleet).
 """
 import numpy as np
 
@@ -14,14 +17,18 @@ from quantum_optimal_control.helper_functions import robust as _robust
 class Fleet(object):
     """offsets (F, E, q), amp_scales (F, E, k), operators (q Hermitian n x n matrices), weights (E,) and risk (beta >= 0).  After a
     Grape(fleet=...) run: losses (F,) of every device's best control set, best (F,) the restart that won, member_losses (F, E) of that
-    control set and iterations (F,) it took."""
+    control set and iterations (F,) it took.  collapse_ops (c operators, or None: closed devices) and rate_scales (F, E, c), default ones."""
 
-    def __init__(self, operators, offsets, amp_scales, weights=None, risk=0.0):
+    def __init__(self, operators, offsets, amp_scales, weights=None, risk=0.0, collapse_ops=None, rate_scales=None):
         self.operators = [np.asarray(p) for p in operators]
         self.offsets = np.asarray(offsets, dtype=np.float64)
         self.amp_scales = np.asarray(amp_scales, dtype=np.float64)
         self.weights = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
         self.risk = risk
+        if rate_scales is not None and collapse_ops is None:
+            raise ValueError('fleet: rate_scales given without collapse_ops')
+        self.collapse_ops = None if collapse_ops is None else list(collapse_ops)
+        self.rate_scales = None if rate_scales is None else np.asarray(rate_scales, dtype=np.float64)
         self.losses = self.best = self.member_losses = self.iterations = None
 
     @property
@@ -33,10 +40,19 @@ class Fleet(object):
         return int(self.amp_scales.shape[1])
 
     def device(self, f):
-        """Device f as the dict Grape(robust=...) takes: its member rows, the shared operators, weights and risk."""
+        """Device f as the dict Grape(robust=...) takes: its member rows, the shared operators, weights and risk, and its decay."""
         w = np.ones(self.n_members) if self.weights is None else self.weights
-        return dict(operators=list(self.operators), offsets=np.array(self.offsets[f]), amp_scales=np.array(self.amp_scales[f]),
-                    weights=np.array(w), risk=self.risk)
+        dev = dict(operators=list(self.operators), offsets=np.array(self.offsets[f]), amp_scales=np.array(self.amp_scales[f]),
+                   weights=np.array(w), risk=self.risk)
+        if self.collapse_ops is not None:
+            dev['collapse_ops'] = list(self.collapse_ops)
+            dev['rate_scales'] = (np.ones((self.n_members, len(self.collapse_ops))) if self.rate_scales is None
+                                  else np.array(self.rate_scales[f]))
+        return dev
+
+    @property
+    def has_decay(self):
+        return self.collapse_ops is not None
 
 
 def _device_rows(values, F, width, name):
@@ -48,8 +64,9 @@ def _device_rows(values, F, width, name):
     return a
 
 
-def devices(operators=(), offsets=None, amp_scales=None, k=None):
-    """A fleet of one member per device: offsets (F, q), one row of perturbation values per device, and amp_scales (F, k) or None (ones)."""
+def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=None, rate_scales=None):
+    """A fleet of one member per device: offsets (F, q), one row of perturbation values per device, and amp_scales (F, k) or None (ones).
+    collapse_ops with rate_scales (F, c) or None (ones): every device decays through its own sqrt(rate_scales[f, j]) C_j."""
     if k is None:
         raise ValueError('fleet.devices: k (the number of pulses) is required')
     k = int(k)
@@ -66,21 +83,29 @@ def devices(operators=(), offsets=None, amp_scales=None, k=None):
     if amp_scales is not None:
         amp_scales = _device_rows(amp_scales, F, k, 'amp_scales')
         F = amp_scales.shape[0]
+    if rate_scales is not None:
+        if collapse_ops is None:
+            raise ValueError('fleet: rate_scales given without collapse_ops')
+        rate_scales = _device_rows(rate_scales, F, len(collapse_ops), 'rate_scales')
+        F = rate_scales.shape[0]
     if F is None:
-        raise ValueError('fleet: the fleet has no devices (give offsets or amp_scales)')
+        raise ValueError('fleet: the fleet has no devices (give offsets, amp_scales or rate_scales)')
     off = np.zeros((F, 1, q)) if not q else offsets.reshape(F, 1, q)
     amp = np.ones((F, 1, k)) if amp_scales is None else amp_scales.reshape(F, 1, k)
-    return validate(Fleet(operators, off, amp), None, k)
+    rates = None if rate_scales is None else rate_scales.reshape(F, 1, -1)
+    return validate(Fleet(operators, off, amp, collapse_ops=collapse_ops, rate_scales=rates), None, k)
 
 
-def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None):
+def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, collapse_ops=None, rate_scales=None):
     """Every device gets the ensemble `robust` (a Grape(robust=...) dict over the same operators) centred on it: member e of device f has the
-    offsets offsets[f] + robust offsets[e] and the scales amp_scales[f] * robust amp_scales[e].  Weights and risk are the ensemble's."""
+    offsets offsets[f] + robust offsets[e] and the scales amp_scales[f] * robust amp_scales[e].  Weights and risk are the ensemble's.
+    Decay: the collapse operators are the fleet's (collapse_ops) or the ensemble's -- the same list when both carry one --, and member e of
+    device f has the rate scales rate_scales[f] * robust rate_scales[e] (either defaults to ones)."""
     if robust is None:
         raise ValueError('fleet.around: robust (the ensemble every device gets) is required')
     if k is None:
         k = np.shape(robust['amp_scales'])[1] if robust.get('amp_scales') is not None else None
-    centre = devices(operators, offsets, amp_scales, k=k)
+    centre = devices(operators, offsets, amp_scales, k=k, collapse_ops=collapse_ops, rate_scales=rate_scales)
     q = len(centre.operators)
     ens = _robust.validate(robust, centre.operators[0].shape[0] if q else None, int(k))
     if len(ens['operators']) != q or any(not np.array_equal(a, b) for a, b in zip(ens['operators'], centre.operators)):
@@ -88,12 +113,22 @@ def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None):
                          % (q, len(ens['operators'])))
     off = centre.offsets[:, 0][:, None, :] + ens['offsets'][None, :, :]
     amp = centre.amp_scales[:, 0][:, None, :] * ens['amp_scales'][None, :, :]
-    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk']), None, int(k))
+    cops, rates = centre.collapse_ops, None
+    if 'collapse_ops' in ens:
+        if cops is not None and (len(cops) != len(ens['collapse_ops']) or any(not np.array_equal(a, b) for a, b in zip(cops, ens['collapse_ops']))):
+            raise ValueError('fleet.around: the ensemble and the fleet must carry the same collapse operators')
+        cops = ens['collapse_ops']
+    if cops is not None:
+        F, E, c = off.shape[0], off.shape[1], len(cops)
+        dev_r = np.ones((F, 1, c)) if centre.rate_scales is None else centre.rate_scales
+        rates = dev_r[:, 0][:, None, :] * (ens['rate_scales'] if 'rate_scales' in ens else np.ones((E, c)))[None, :, :]
+    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=cops, rate_scales=rates), None, int(k))
 
 
 def validate(fleet, n, k):
     """Checks a Fleet against a problem of n levels (None: from the operators) and k pulses and returns a normalised copy: operators complex
     Hermitian n x n, offsets (F, E, q), amp_scales (F, E, k), weights (E,) summing to 1 (default uniform), risk a finite float >= 0.
+    collapse_ops (None, or c complex n x n matrices) and rate_scales (F, E, c), finite and >= 0 (default ones; None without collapse_ops).
     Raises ValueError with the cause."""
     if not isinstance(fleet, Fleet):
         raise ValueError('fleet: a helper_functions.fleet.Fleet (fleet.devices, fleet.around)')
@@ -110,11 +145,23 @@ def validate(fleet, n, k):
     if not (np.all(np.isfinite(amp)) and np.all(np.isfinite(off))):
         raise ValueError('fleet: offsets and amp_scales must be finite')
     # operators, weights and risk: the ensemble's rules (helper_functions/robust.py), on device 0's rows
+    dev0 = dict(operators=fleet.operators, offsets=off[0], amp_scales=amp[0], weights=fleet.weights, risk=fleet.risk)
+    cops, rates = getattr(fleet, 'collapse_ops', None), getattr(fleet, 'rate_scales', None)
+    if rates is not None and cops is None:
+        raise ValueError('fleet: rate_scales given without collapse_ops')
+    if cops is not None:
+        c = len(cops)
+        rates = np.ones((F, E, c)) if rates is None else np.array(rates, dtype=np.float64)
+        if rates.shape != (F, E, c):
+            raise ValueError('fleet: rate_scales have shape %s, expected (%d, %d, %d)' % (rates.shape, F, E, c))
+        if not np.all(np.isfinite(rates)) or np.any(rates < 0):
+            raise ValueError('fleet: rate_scales must be finite and >= 0')
+        dev0.update(collapse_ops=cops, rate_scales=rates[0])
     try:
-        ens = _robust.validate(dict(operators=fleet.operators, offsets=off[0], amp_scales=amp[0], weights=fleet.weights, risk=fleet.risk), n, k)
+        ens = _robust.validate(dev0, n, k)
     except ValueError as err:
         raise ValueError(str(err).replace('robust:', 'fleet:', 1))
-    return Fleet(ens['operators'], off, amp, weights=ens['weights'], risk=ens['risk'])
+    return Fleet(ens['operators'], off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=ens.get('collapse_ops'), rate_scales=rates)
 
 
 def tile_bases(base, F):

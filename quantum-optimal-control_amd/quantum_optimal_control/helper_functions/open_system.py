@@ -80,3 +80,23 @@ def choose_taylor(H0, Hops, maxA, collapse_ops, dt, steps, unitary_error):
         if T > 60:
             raise ValueError('choose_taylor: unitary_error = %g is not reached with 60 Taylor terms' % unitary_error)
     return T, s
+
+
+def choose_taylor_members(H0, Hops, maxA, devices, dt, steps, unitary_error, control_map=None):
+    """(T, s) for an ensemble or fleet with decay: the maximum over the members of choose_taylor on each member's Hamiltonians and scaled collapse
+    operators.  devices: the validated robust dicts (helper_functions/robust.py), one per device -- one dict for a plain ensemble.  control_map: Hops
+    are then the operators the map feeds, bounded by the largest coefficients it can deliver from the member's scaled pulses."""
+    from quantum_optimal_control.helper_functions import robust as _robust
+    best_t, best_s = 0, 0
+    for dev in devices:
+        for e in range(dev['weights'].shape[0]):
+            if control_map is None:
+                H0e, Hopse = _robust.member_hamiltonians(H0, Hops, dev, e)
+                bound = maxA
+            else:
+                from quantum_optimal_control.helper_functions.control_map import coefficient_bounds
+                H0e, _ = _robust.member_hamiltonians(H0, [], dev, e)
+                Hopse, bound = Hops, coefficient_bounds(control_map, np.abs(dev['amp_scales'][e]) * np.asarray(maxA, dtype=np.float64))
+            t, s = choose_taylor(H0e, Hopse, bound, _robust.member_collapse_ops(dev, e), dt, steps, unitary_error)
+            best_t, best_s = max(best_t, t), max(best_s, s)
+    return best_t, best_s

@@ -4,6 +4,10 @@ Member e of an ensemble is an ordinary GRAPE problem with the drift H0 + sum_q o
 amp_scales[e, j] H_j; all members share U0, the targets, the states of interest, maxA, the regularisers and the one trainable pulse.
 Grape optimises the weighted mean objective over the members (include/qoc.h, qoc_create_ensemble), or, with a `risk` beta > 0, their soft
 worst case  max_e c_e + log1p(sum_e w_e expm1(beta (c_e - max_e c_e))) / beta  (qoc_set_risk): the mean at beta = 0, the worst member as beta grows.
+
+Decay per member: with the optional keys `collapse_ops` (c operators as Grape(collapse_ops=...) takes them) and `rate_scales` (E, c) a member is
+an OPEN problem: member e decays through sqrt(rate_scales[e, j]) C_j (a scale of 0 switches the channel off; default ones), and Grape scores and
+optimises the pulse under every member's master equation (include/qoc.h, qoc_create_open_fleet).
 """
 import itertools
 
@@ -24,11 +28,18 @@ def _rows(values, width, name):
     return np.array(out, dtype=np.float64).reshape(len(out), width)
 
 
-def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=None, risk=0.0):
+def has_decay(robust):
+    """True when the ensemble dict makes its members open problems (the key collapse_ops is given, an empty list included)."""
+    return isinstance(robust, dict) and robust.get('collapse_ops') is not None
+
+
+def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=None, risk=0.0, collapse_ops=None, rate_scales=None):
     """Cartesian product of offset rows (each q values, one per operator) and amplitude-scale rows (each k values, or a scalar for
     all k controls).  The nominal point (all offsets 0, all scales 1) comes first when the grid contains it; otherwise the
     product order is kept (offset rows outer).  weights: one per grid point (default uniform), normalised to sum 1.  risk: beta >= 0 of the
     soft worst-case objective (0: the weighted mean).
+    collapse_ops, rate_scales: the members are open problems; the rate-scale rows (each c values, or a scalar for all c operators) are a third
+    axis of the product (innermost), and the nominal point has all rate scales 1 as well.
     Returns the dict Grape(robust=...) takes."""
     operators = [np.asarray(p) for p in operators]
     q = len(operators)
@@ -39,29 +50,40 @@ def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=N
     if q == 0 and offsets is not None and np.size(offsets) != 0:
         raise ValueError('ensemble_grid: offsets given without operators')
     amp_rows = _rows(amp_scales if amp_scales is not None else [1.0], k, 'amp_scales')
-    pts = [(o, a) for o, a in itertools.product(off_rows, amp_rows)]
+    if rate_scales is not None and collapse_ops is None:
+        raise ValueError('ensemble_grid: rate_scales given without collapse_ops')
+    c = 0 if collapse_ops is None else len(collapse_ops)
+    rate_rows = _rows(rate_scales if rate_scales is not None else [1.0], c, 'rate_scales') if c else np.ones((1, 0))
+    if c == 0 and rate_scales is not None and np.size(rate_scales) != 0:
+        raise ValueError('ensemble_grid: rate_scales given without a collapse operator')
+    pts = [(o, a, r) for o, a, r in itertools.product(off_rows, amp_rows, rate_rows)]
     if weights is None:
         w = np.ones(len(pts))
     else:
         w = np.asarray(weights, dtype=np.float64).reshape(-1)
         if w.shape[0] != len(pts):
             raise ValueError('ensemble_grid: %d weights for %d grid points' % (w.shape[0], len(pts)))
-    nominal = [i for i, (o, a) in enumerate(pts) if np.all(o == 0.0) and np.all(a == 1.0)]
+    nominal = [i for i, (o, a, r) in enumerate(pts) if np.all(o == 0.0) and np.all(a == 1.0) and np.all(r == 1.0)]
     order = list(range(len(pts)))
     if nominal:
         order = [nominal[0]] + [i for i in order if i != nominal[0]]
     ens = dict(operators=operators, offsets=np.array([pts[i][0] for i in order]).reshape(len(pts), q),
                amp_scales=np.array([pts[i][1] for i in order]).reshape(len(pts), k), weights=w[order], risk=risk)
+    if collapse_ops is not None:
+        ens['collapse_ops'] = list(collapse_ops)
+        ens['rate_scales'] = np.array([pts[i][2] for i in order]).reshape(len(pts), c)
     return validate(ens, None, k)
 
 
 def validate(robust, n, k):
     """Checks a robust dict (keys operators, offsets, amp_scales, weights, risk) against a problem of n levels (None: from the operators) and
     k controls and returns it normalised: operators a list of q complex n x n Hermitian matrices, offsets (E, q), amp_scales (E, k)
-    (default ones), weights (E,) summing to 1 (default uniform), risk a finite float >= 0 (default 0.0: the weighted mean).  Raises ValueError."""
+    (default ones), weights (E,) summing to 1 (default uniform), risk a finite float >= 0 (default 0.0: the weighted mean).  With the key
+    collapse_ops the result also holds collapse_ops (c complex n x n matrices, open_system.validate's rules) and rate_scales (E, c), finite and
+    >= 0 (default ones); without it the result has exactly the five keys above.  Raises ValueError."""
     if not isinstance(robust, dict):
         raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights, risk')
-    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk'}
+    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk', 'collapse_ops', 'rate_scales'}
     if unknown:
         raise ValueError('robust: unknown keys %s' % sorted(unknown))
     try:
@@ -79,7 +101,22 @@ def validate(robust, n, k):
             n = p.shape[0]
         if not np.allclose(p, p.conj().T, rtol=0.0, atol=1e-12 * max(1.0, float(np.max(np.abs(p))))):
             raise ValueError('robust: operator %d is not Hermitian' % i)
-    E = None
+    cops, rates = robust.get('collapse_ops'), robust.get('rate_scales')
+    if rates is not None and cops is None:
+        raise ValueError('robust: rate_scales given without collapse_ops')
+    if cops is not None:
+        from quantum_optimal_control.helper_functions import open_system
+        if n is None:
+            if not isinstance(cops, (list, tuple)) or (len(cops) and np.ndim(cops[0]) != 2):
+                raise ValueError('robust: collapse_ops is a list of n x n collapse operators')
+            n_c = np.shape(cops[0])[0] if len(cops) else None
+        else:
+            n_c = n
+        try:
+            cops = open_system.validate(cops, n_c) if n_c is not None else []
+        except ValueError as err:
+            raise ValueError('robust: %s' % err)
+    E = None if rates is None else np.shape(rates)[0] if np.ndim(rates) == 2 else None
     offsets = robust.get('offsets')
     if q:
         if offsets is None:
@@ -117,8 +154,17 @@ def validate(robust, n, k):
         raise ValueError('robust: the weights sum to zero')
     if not (np.all(np.isfinite(amp)) and (offsets is None or np.all(np.isfinite(offsets)))):
         raise ValueError('robust: offsets and amp_scales must be finite')
-    return dict(operators=ops, offsets=np.zeros((E, 0)) if offsets is None else offsets.reshape(E, q), amp_scales=amp,
-                weights=w / w.sum(), risk=risk)
+    out = dict(operators=ops, offsets=np.zeros((E, 0)) if offsets is None else offsets.reshape(E, q), amp_scales=amp,
+               weights=w / w.sum(), risk=risk)
+    if cops is not None:
+        c = len(cops)
+        rates = np.ones((E, c)) if rates is None else np.asarray(rates, dtype=np.float64)
+        if rates.shape != (E, c):
+            raise ValueError('robust: rate_scales have shape %s, expected (%d, %d)' % (rates.shape, E, c))
+        if not np.all(np.isfinite(rates)) or np.any(rates < 0):
+            raise ValueError('robust: rate_scales must be finite and >= 0')
+        out['collapse_ops'], out['rate_scales'] = cops, rates
+    return out
 
 
 def member_hamiltonians(H0, Hops, robust, e):
@@ -127,6 +173,13 @@ def member_hamiltonians(H0, Hops, robust, e):
     for qq, p in enumerate(robust['operators']):
         H0e = H0e + robust['offsets'][e, qq] * p
     return H0e, [robust['amp_scales'][e, j] * np.asarray(h) for j, h in enumerate(Hops)]
+
+
+def member_collapse_ops(robust, e):
+    """The collapse operators of member e: sqrt(rate_scales[e, j]) C_j, switched-off channels (scale 0) left out.  [] without decay."""
+    if not has_decay(robust):
+        return []
+    return [np.sqrt(s) * np.asarray(cj, dtype=np.complex128) for s, cj in zip(robust['rate_scales'][e], robust['collapse_ops']) if s > 0]
 
 
 def choose_taylor(H0, Hops, robust, maxA, U0, total_time, steps, unitary_error, state_transfer, no_scaling):

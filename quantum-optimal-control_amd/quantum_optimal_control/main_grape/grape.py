@@ -150,7 +150,18 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     ``losses`` (F,), ``best`` (F,), ``member_losses`` (F, E) and ``iterations`` (F,); ``transfer.samples`` is (F, k, P) and ``control_map.coefficients``
     (F, r, steps).  The Taylor order is the largest any member of any device would get.  ``method`` is ``'Adam'``, ``'LBFGS'`` or ``'EVOLVE'`` (the
     scan of one pulse over the devices).  Works with ``transfer``, ``control_map`` and ``exact_gradient``; not with ``robust`` (a fleet carries its own
-    members: ``fleet.around``), ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm``, ``plan_seeds`` or the sharded entry points."""
+    members: ``fleet.around``), ``collapse_ops``, scipy.sparse Hamiltonians, ``time_comm``, ``plan_seeds`` or the sharded entry points.
+
+    Decay per member (open-system ensembles and fleets): a member of an ensemble, or a device of a fleet, is a Hamiltonian AND its decay.  A ``robust``
+    dict may carry the keys ``collapse_ops`` (as the keyword above takes them) and ``rate_scales`` (E x c, default ones), a fleet ``collapse_ops`` and
+    ``rate_scales`` (F x E x c; ``fleet.devices(..., collapse_ops=, rate_scales=)``, ``fleet.around``): member e of device f then decays through
+    sqrt(rate_scales[f, e, j]) C_j (a scale of 0 switches the channel off), every member is scored under its own master equation as ``collapse_ops``
+    defines it, and the members are combined as ``robust`` and ``fleet`` define it.  ``Grape(robust=ens)`` then returns ``(uks, rho_final)`` of member 0,
+    (m, m, n, n); ``Grape(fleet=fl)`` returns them with a leading device axis and fills ``fl.losses``, ``best``, ``member_losses`` and ``iterations`` as
+    without decay.  Taylor order and sub-steps: the largest that open_system.choose_taylor gives any member, unless ``Taylor_terms=(T, s)``.  Methods:
+    ``'Adam'``, ``'LBFGS'``, ``'EVOLVE'`` and, on a robust call, scipy's.  Works with ``transfer``, ``control_map`` and ``restarts``; not with the
+    ``collapse_ops`` keyword itself, ``exact_gradient``, ``dressed_info``, forbidden-level / ``speed_up`` / ``forbid_dressed`` regularisers,
+    ``time_comm``, scipy.sparse Hamiltonians or the sharded entry points (ValueError, before the library is loaded)."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     sparse = _is_sparse(H0, Hops)
@@ -225,6 +236,23 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if time_comm is not None:
             raise ValueError('Grape: robust ensembles cannot be time-sharded (time_comm)')
         robust = _robust.validate(robust, len(H0), n_pulses)
+    decay_devices = None                               # decay per member: the validated member dicts, one per device
+    if fleet is not None and fleet.has_decay:
+        decay_devices, _who = [fleet.device(f) for f in range(fleet.n_devices)], 'a fleet with decay'
+    elif robust is not None and _robust.has_decay(robust):
+        decay_devices, _who = [robust], 'a robust ensemble with decay'
+    if decay_devices is not None:
+        # what collapse_ops= refuses, refused here too: before anything is built (and before the library is loaded)
+        from quantum_optimal_control.helper_functions import open_system as _open
+        for name, given in (('exact_gradient', bool(exact_gradient)), ('time_comm', time_comm is not None), ('dressed_info', dressed_info is not None),
+                            ('scipy.sparse Hamiltonians (sparse state transfer)', sparse),
+                            ('the forbidden-level regulariser', reg_coeffs is not None and 'forbidden_coeff_list' in reg_coeffs),
+                            ('the speed_up regulariser', reg_coeffs is not None and 'speed_up' in reg_coeffs),
+                            ('forbid_dressed', reg_coeffs is not None and 'forbid_dressed' in reg_coeffs)):
+            if given:
+                raise ValueError('Grape: %s (open-system GRAPE) does not combine with %s' % (_who, name))
+        if _first_seed != 0 or plan_seeds is not None:
+            raise ValueError('Grape: %s (open-system GRAPE) does not run sharded (GrapeSharded)' % _who)
     if transfer is not None:
         from quantum_optimal_control.helper_functions import transfer as _transfer
         if time_comm is not None:
@@ -254,6 +282,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                     hf.add('robust_' + key, data=robust[key])
                 if robust['risk'] > 0:
                     hf.add('robust_risk', data=np.array([robust['risk']]))
+                if _robust.has_decay(robust):
+                    c = len(robust['collapse_ops'])
+                    hf.add('robust_collapse_ops', data=np.array(robust['collapse_ops'], dtype=np.complex128).reshape(c, len(H0), len(H0)))
+                    hf.add('robust_rate_scales', data=robust['rate_scales'])
         if transfer is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -267,6 +299,10 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             with H5File(file_path) as hf:
                 hf.add('fleet_offsets', data=fleet.offsets)
                 hf.add('fleet_amp_scales', data=fleet.amp_scales)
+                if fleet.has_decay:
+                    c = len(fleet.collapse_ops)
+                    hf.add('fleet_collapse_ops', data=np.array(fleet.collapse_ops, dtype=np.complex128).reshape(c, len(H0), len(H0)))
+                    hf.add('fleet_rate_scales', data=fleet.rate_scales)
         if collapse_ops is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -284,6 +320,11 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             maxAmp = 1.5 * np.max(np.abs(initial_guess if fleet_guess is None else fleet_guess)) * np.ones(n_pulses)
     else:
         maxAmp = maxA
+
+    if decay_devices is not None and Taylor_terms is None:
+        # the largest degree and sub-step count that the Lindblad rule gives any member, with its own Hamiltonians and scaled collapse operators
+        Taylor_terms = _open.choose_taylor_members(H0, Hops, maxAmp, decay_devices, float(total_time) / steps, steps, unitary_error,
+                                                   control_map=control_map)
 
     if fleet is not None and Taylor_terms is None:
         # the largest Taylor order and squaring count any member of any device would get
@@ -408,7 +449,10 @@ def _fleet_results(engine, sys_para, fleet, given_fleet, transfer, control_map, 
     best, sets = select_best(s['loss'], fleet.n_devices)
     evaluated = engine.get_uks(evaluated=True)[sets]
     uks = engine.get_pulse()[sets] if engine.samples is not None else evaluated
-    Uf = [[] for _ in sets] if sys_para.state_transfer else engine.get_final_unitary()[sets]
+    if getattr(engine, 'open_system', False):
+        Uf = engine.get_final_density()[sets]              # (F, m, m, n, n): member 0's final density operators, in both modes
+    else:
+        Uf = [[] for _ in sets] if sys_para.state_transfer else engine.get_final_unitary()[sets]
     member_losses = engine.member_scalars()['loss'][sets]
     for fl in (fleet, given_fleet):
         fl.losses, fl.best, fl.member_losses, fl.iterations = np.array(s['loss'][sets]), np.array(best), np.array(member_losses), np.array(s['iterations'][sets])
@@ -441,6 +485,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
         raise ValueError('GrapeTimeSharded: control_map (control maps) is not supported; run Grape(control_map=...) on one GPU')
     if kwargs.get('fleet') is not None:
         raise ValueError('GrapeTimeSharded: fleet (device fleets) is not supported; run Grape(fleet=...) on one GPU')
+    if isinstance(kwargs.get('robust'), dict) and kwargs['robust'].get('collapse_ops') is not None:
+        raise ValueError('GrapeTimeSharded: a robust ensemble with decay (open-system GRAPE) is not supported; run Grape(robust=...) on one GPU')
     if _sparse_call(args, kwargs):
         raise ValueError('GrapeTimeSharded: scipy.sparse Hamiltonians (sparse state transfer) are not supported; run Grape(...) on one GPU')
     if comm is None:
