@@ -167,6 +167,12 @@ int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const do
 int qoc_get_member_scalars(qoc_handle h, double* loss, double* reg_state);
 /* Every member's final unitary of the last evaluation: [n_seeds][E][n][n] complex (unitary mode only). */
 int qoc_get_member_final_unitary(qoc_handle h, double* Uf);
+/* The gradient array of the TRAJECTORIES as the backward kernels of the last evaluation left it, before the member reduction:
+ * [n_seeds * E][kt + q][steps], dJ_e / du of every control row of every member (first order, or exact).  On the engines of
+ * qoc_create_sparse_fleet the q frozen perturbation rows are cleared at creation and never written, so they read as exact zeros; what the dense
+ * paths leave in those rows is not specified (no reduction reads them).  On a mapped engine the first kt rows are dJ / dc of the operators.
+ * QOC_ERR_STATE on an engine that is no ensemble engine, or before the first evaluation. */
+int qoc_get_trajectory_gradient(qoc_handle h, double* dLdu);
 
 /* ---- risk-sensitive robust GRAPE: the soft worst case over the members in place of their weighted mean (no counterpart in the reference) ----
  * With beta > 0, the member costs c_e = loss_e + (forbidden levels + speed_up)_e and c_max their maximum, per control set:
@@ -342,6 +348,34 @@ typedef struct qoc_sparse {
 } qoc_sparse;
 int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
                       const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out);
+
+/* ---- sparse ensembles, fleets, lines and maps: the ensemble entry points on sparse operators ------------------------------------------------
+ * ens, fleet, transfer and map may each be NULL with the meaning they have in qoc_create_fleet; per control set every quantity is what those entry
+ * points define over the members, per member everything is what qoc_create_sparse defines.  ops holds kt + 1 + q operators in the order
+ * [H0, H_1 .. H_kt, P_1 .. P_q] with kt = map ? map->n_terms : cfg->k and q = ens->n_perturb (indptr has kt + q + 2 entries): the perturbation
+ * operators are the last q of ops and ens->P must be NULL.  All four NULL: one nominal member, and with row_layout = 1 the values of
+ * qoc_create_sparse, bit for bit.
+ * plan (may be NULL: all auto) selects how a sweep walks the operators of a row:
+ *   1 per operator   the kernels of qoc_create_sparse: one ELLPACK block per operator, kt + q + 1 passes per Taylor term
+ *   2 merged         the stored entries of all operators of a row in ONE list (operator 0 first, columns ascending inside an operator, padding
+ *                    dropped), each slot a column and an operator index packed as col | op << 24; the slice's coefficients come from a table in
+ *                    LDS.  The arithmetic order is the per-operator kernels', so both layouts compute the same numbers (equal under ==; the sign
+ *                    of a zero may differ).  At most 255 operators and n < 2^24
+ *   0 auto           merged for n >= 1024 with 12 or more operators, where it was measured ahead (QOC_SP_MERGED_AUTO in csrc/qoc_sparse.h,
+ *                    profiles/sparse_ensemble.txt), per operator everywhere else and where 2 cannot run
+ * The gradient kernel reads each control's own ELLPACK block in both layouts and forms no gradient for the frozen perturbation rows.
+ * The vectors of a merged sweep live in LDS while 2 n 16 B + the table (8 B per operator, rounded up to 16 B) <= 159 KiB.
+ * qoc_plan_describe: the sparse engine's line with rows=<per_operator|merged> merged_width=<longest merged row, 0 per operator> and what the ensemble
+ * entry points append.  The ensemble getters work as on a dense ensemble engine; the final-unitary getters keep their state-transfer refusal.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: everything qoc_create_sparse refuses; everything the four ensemble entry
+ * points refuse about member counts, weights, tables, devices, the line and the map; a non-NULL ens->P; row_layout outside 0 .. 2; row_layout = 2
+ * with more than 255 operators or n >= 2^24. */
+typedef struct qoc_sparse_plan {
+    int32_t row_layout;         /* 0 auto, 1 per operator, 2 merged */
+} qoc_sparse_plan;
+int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const qoc_sparse_plan* plan, const qoc_ensemble* ens, const qoc_fleet* fleet,
+                            const qoc_transfer* transfer, const qoc_control_map* map, const double* V, const double* W, const double* maxA,
+                            const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out);
 
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).

@@ -121,6 +121,7 @@ struct qoc_engine {
     // sparse state transfer (qoc_create_sparse, csrc/qoc_sparse.h): ELLPACK operators, no n x n array anywhere (d.Hs, d.U0 and d.Xfinal stay null)
     QocSparse sp{};
     std::vector<int> sp_widths;     // [k+1] W_j, for qoc_plan_describe
+    bool sp_fleet_entry = false;    // made by qoc_create_sparse_fleet: qoc_plan_describe names the row layout
     // device-resident L-BFGS loop (qoc_iterate_lbfgs / qoc_run_lbfgs, csrc/qoc_lbfgs.h): per-set state, allocated by the first call for lq_cap pairs
     QocLbfgsDev lq{};
     int lq_cap = 0;
@@ -659,9 +660,15 @@ struct DecayHost {
 };
 
 // the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
+// (qoc_create_sparse_fleet: kt + q + 1 operators, the merged layout of them when the sweeps walk it, and kt, the rows k_sp_grad forms gradients for)
 struct SparseHost {
     std::vector<QocEllOp> ops;       // [k+1]
     int vector_home;
+    const char* who = "qoc_create_sparse";
+    int kgrad = -1;                  // -1: every row (qoc_create_sparse)
+    bool fleet_entry = false;        // made by qoc_create_sparse_fleet: the plan string names the row layout
+    bool merged = false;
+    QocMergedOps rows;               // merged only
 };
 
 // the caller's arrays of qoc_create (include/qoc.h), passed on together (sparse: the operators of qoc_create_sparse in place of Hs, else null)
@@ -1120,8 +1127,24 @@ static int setup_sparse(qoc_engine* e, const SparseHost& h) {
     // QOC_EXPERIMENTAL=1 QOC_SP_THREADS=256|1024: the sweeps' workgroup size, for the A/B runs behind QOC_SP_WIDE_FROM
     int threads = 0;
     if (const char* t = qoc_exp_env("QOC_SP_THREADS")) threads = atoi(t) == 1024 ? 1024 : (atoi(t) == 256 ? 256 : 0);
-    if (const char* why = qoc_sp_plan(sp, d, h.vector_home, threads)) return fail(QOC_ERR_INVALID, "qoc_create_sparse: %s (n = %d)", why, d.n);
+    if (const char* why = qoc_sp_plan(sp, d, h.vector_home, threads, h.merged, (int)h.ops.size())) return fail(QOC_ERR_INVALID, "%s: %s (n = %d)", h.who, why, d.n);
     const size_t n = (size_t)d.n, K = h.ops.size();
+    e->sp_fleet_entry = h.fleet_entry;
+    if (h.kgrad >= 0 && h.kgrad < d.k) {
+        // the frozen perturbation rows of the trajectories' gradient: cleared once, never written (k_sp_grad stops at kgrad) and never read
+        sp.kgrad = h.kgrad;
+        HIP_TRY(hipMemset(d.dLdu, 0, (size_t)d.B * d.k * d.steps * sizeof(double)));
+    }
+    if (h.merged) {
+        // the merged rows beside the per-operator blocks (which k_sp_grad keeps reading)
+        const size_t slots = n * (size_t)h.rows.Wm;
+        sp.Wm = h.rows.Wm;
+        TRY(dev_upload(e, &sp.mlen, (const int*)h.rows.len.data(), n));
+        if (slots) {
+            TRY(dev_upload(e, &sp.midx, (const int*)h.rows.idx.data(), slots));
+            TRY(dev_upload(e, &sp.mval, (const cplx*)h.rows.val.data(), slots));
+        }
+    }
     std::vector<int> W(K);
     std::vector<long long> off(K);
     size_t total = 0;
@@ -1141,7 +1164,7 @@ static int setup_sparse(qoc_engine* e, const SparseHost& h) {
     TRY(dev_upload(e, &sp.off, (const long long*)off.data(), K));
     TRY(dev_alloc(e, &sp.Lam, (size_t)d.B * d.steps * n * d.m));
     if (sp.home == 2) TRY(dev_alloc(e, &sp.scratch, (size_t)d.B * d.m * 2 * n));
-    HIP_TRY_MSG(qoc_sp_lds_opt_in(sp), "qoc_create_sparse: cannot reserve %zu bytes of LDS for the sparse sweeps", sp.lds_bytes);
+    HIP_TRY_MSG(qoc_sp_lds_opt_in(sp), "%s: cannot reserve %zu bytes of LDS for the sparse sweeps", h.who, sp.lds_bytes);
     return QOC_OK;
 }
 
@@ -1264,38 +1287,44 @@ int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* H
     return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, &dh);
 }
 
-int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
-                      const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out) {
-    if (!cfg || !ops || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_sparse: null argument");
-    if (!cfg->state_transfer) return fail(QOC_ERR_INVALID, "qoc_create_sparse: sparse operators run in state-transfer mode only (unitary mode propagates an n x n matrix)");
-    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "qoc_create_sparse: forbid_dressed needs the n x n matrix of dressed states; forbidden levels are bare on a sparse engine");
-    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "qoc_create_sparse: the exact gradient is not available on sparse operators (gradient = %d)", cfg->gradient);
-    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "qoc_create_sparse: a sparse engine cannot be time-sharded (time_shards = %d)", cfg->time_shards);
+// what a sparse engine refuses about its configuration and its operators (K of them), on the host and before any device is touched; then COO ->
+// ELLPACK: indices in range, values finite, n W_j within int32 (`who`: qoc_create_sparse or qoc_create_sparse_fleet)
+static int check_sparse(const char* who, const qoc_config* cfg, const qoc_sparse* ops, int K, SparseHost& sh) {
+    if (!cfg->state_transfer) return fail(QOC_ERR_INVALID, "%s: sparse operators run in state-transfer mode only (unitary mode propagates an n x n matrix)", who);
+    if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "%s: forbid_dressed needs the n x n matrix of dressed states; forbidden levels are bare on a sparse engine", who);
+    if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "%s: the exact gradient is not available on sparse operators (gradient = %d)", who, cfg->gradient);
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: a sparse engine cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
     if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_SPARSE)
-        return fail(QOC_ERR_INVALID, "qoc_create_sparse: sparse operators run on QOC_PATH_SPARSE (or AUTO), not on path %d", cfg->path);
-    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1) return fail(QOC_ERR_INVALID, "qoc_create_sparse: n, k, steps, n_seeds must be >= 1");
+        return fail(QOC_ERR_INVALID, "%s: sparse operators run on QOC_PATH_SPARSE (or AUTO), not on path %d", who, cfg->path);
+    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1) return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
     if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_SP_MAX_T)
-        return fail(QOC_ERR_INVALID, "qoc_create_sparse: taylor_terms = %d (1 .. %d)", cfg->taylor_terms, QOC_SP_MAX_T);
-    if (cfg->m < 1) return fail(QOC_ERR_INVALID, "qoc_create_sparse: m = %d states of interest (>= 1)", cfg->m);
-    if ((long long)cfg->n * cfg->m > (long long)INT32_MAX) return fail(QOC_ERR_INVALID, "qoc_create_sparse: n * m = %d * %d does not fit 32-bit indices", cfg->n, cfg->m);
-    if (ops->vector_home < 0 || ops->vector_home > 2) return fail(QOC_ERR_INVALID, "qoc_create_sparse: vector_home = %d (0 auto, 1 LDS, 2 global scratch)", ops->vector_home);
+        return fail(QOC_ERR_INVALID, "%s: taylor_terms = %d (1 .. %d)", who, cfg->taylor_terms, QOC_SP_MAX_T);
+    if (cfg->m < 1) return fail(QOC_ERR_INVALID, "%s: m = %d states of interest (>= 1)", who, cfg->m);
+    if ((long long)cfg->n * cfg->m > (long long)INT32_MAX) return fail(QOC_ERR_INVALID, "%s: n * m = %d * %d does not fit 32-bit indices", who, cfg->n, cfg->m);
+    if (ops->vector_home < 0 || ops->vector_home > 2) return fail(QOC_ERR_INVALID, "%s: vector_home = %d (0 auto, 1 LDS, 2 global scratch)", who, ops->vector_home);
     if (ops->vector_home == 1 && 2 * (size_t)cfg->n * sizeof(cplx) > QOC_SP_LDS_LIMIT)
-        return fail(QOC_ERR_INVALID, "qoc_create_sparse: vector_home = 1 (LDS) needs 2 n 16 bytes <= 159 KiB (n = %d, at most 5088)", cfg->n);
-    if (!ops->indptr) return fail(QOC_ERR_INVALID, "qoc_create_sparse: indptr is missing");
-    const int K = cfg->k + 1;
+        return fail(QOC_ERR_INVALID, "%s: vector_home = 1 (LDS) needs 2 n 16 bytes <= 159 KiB (n = %d, at most 5088)", who, cfg->n);
+    if (!ops->indptr) return fail(QOC_ERR_INVALID, "%s: indptr is missing", who);
     for (int j = 0; j < K; ++j)
-        if (ops->indptr[j] < 0 || ops->indptr[j + 1] < ops->indptr[j]) return fail(QOC_ERR_INVALID, "qoc_create_sparse: indptr[%d .. %d] does not ascend from 0", j, j + 1);
-    if (ops->indptr[K] > 0 && (!ops->row || !ops->col || !ops->val)) return fail(QOC_ERR_INVALID, "qoc_create_sparse: entry arrays missing");
-    // COO -> ELLPACK on the host, before any device is touched: indices in range, values finite, n W_j within int32
-    SparseHost sh;
+        if (ops->indptr[j] < 0 || ops->indptr[j + 1] < ops->indptr[j]) return fail(QOC_ERR_INVALID, "%s: indptr[%d .. %d] does not ascend from 0", who, j, j + 1);
+    if (ops->indptr[K] > 0 && (!ops->row || !ops->col || !ops->val)) return fail(QOC_ERR_INVALID, "%s: entry arrays missing", who);
+    sh.who = who;
     sh.vector_home = ops->vector_home;
     sh.ops.resize((size_t)K);
     std::string why;
     for (int j = 0; j < K; ++j) {
         const int64_t a = ops->indptr[j], cnt = ops->indptr[j + 1] - a;
         if (!qoc_ell_build(cfg->n, cnt, ops->row + a, ops->col + a, ops->val + 2 * a, sh.ops[(size_t)j], why))
-            return fail(QOC_ERR_INVALID, "qoc_create_sparse: operator %d: %s", j, why.c_str());
+            return fail(QOC_ERR_INVALID, "%s: operator %d: %s", who, j, why.c_str());
     }
+    return QOC_OK;
+}
+
+int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double* V, const double* W, const double* maxA,
+                      const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out) {
+    if (!cfg || !ops || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_sparse: null argument");
+    SparseHost sh;
+    TRY(check_sparse("qoc_create_sparse", cfg, ops, cfg->k + 1, sh));
     return create_engine(cfg, Problem{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh}, nullptr, out);
 }
 
@@ -1304,10 +1333,10 @@ int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double
 // (fleet: the checked tables of qoc_create_fleet, read in place of ens' offsets and amp_scales)
 static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, Problem p,
                           qoc_handle* out, const qoc_control_map* map = nullptr, const qoc_fleet* fleet = nullptr) {
-    if (!cfg || !ens || !p.Hs || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    if (!cfg || !ens || (!p.Hs && !p.sparse) || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int E = ens->members, q = ens->n_perturb;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
-    if ((!fleet && !ens->amp_scales) || !ens->weights || (q > 0 && (!ens->P || (!fleet && !ens->offsets))))
+    if ((!fleet && !ens->amp_scales) || !ens->weights || (q > 0 && ((!ens->P && !p.sparse) || (!fleet && !ens->offsets))))
         return fail(QOC_ERR_INVALID, "%s: ensemble arrays missing", who);
     if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
         return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
@@ -1345,14 +1374,15 @@ static int create_members(const char* who, const ShapeHost* shape, const qoc_con
     tc.plan_seeds = cfg->plan_seeds > 0 ? cfg->plan_seeds * E : 0;
     tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
     tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
-    std::vector<double> Hst(2 * nn * (size_t)(kt + q + 1));
-    memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(kt + 1) * sizeof(double));
-    if (q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(kt + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
+    // (sparse operators: the SparseHost carries the kt + q + 1 ELLPACK blocks already; no dense array is stacked)
+    std::vector<double> Hst(p.sparse ? 0 : 2 * nn * (size_t)(kt + q + 1));
+    if (!p.sparse) memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(kt + 1) * sizeof(double));
+    if (!p.sparse && q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(kt + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
     // (no trajectory kernel of an ensemble forms controls from maxA: the rows of a mapped engine carry ones)
     std::vector<double> maxAt(p.maxA, p.maxA + (map ? 0 : k));
     maxAt.resize((size_t)(kt + q), 1.0);
     const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape, map, fleet};
-    p.Hs = Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
+    p.Hs = p.sparse ? nullptr : Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
     return create_engine(&tc, p, &ea, out);
 }
 
@@ -1506,6 +1536,49 @@ int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const q
     p.decay = &dh;
     if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
     if (map) TRY(check_map(who, cfg, map, maxA));
+    if (tr || map) return create_shaped(who, cfg, ens, tr, map, p, out);
+    const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
+    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
+    return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out);
+}
+
+// sparse operators through the ensemble funnel: the sparse engine's own refusals, the operators and the row layout settled here, everything about
+// the member tables, the line and the map by the entry point that ens, fleet, transfer and map select -- all on the host and before any device is
+// touched.  The trajectories run kt + q operators; k_sp_grad forms gradients for the first kt
+int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const qoc_sparse_plan* plan, const qoc_ensemble* ens, const qoc_fleet* fleet,
+                            const qoc_transfer* tr, const qoc_control_map* map, const double* V, const double* W, const double* maxA,
+                            const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out) {
+    const char* who = "qoc_create_sparse_fleet";
+    if (!cfg || !ops || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    const int layout = plan ? plan->row_layout : 0;
+    if (layout < 0 || layout > 2) return fail(QOC_ERR_INVALID, "%s: row_layout = %d (0 auto, 1 per operator, 2 merged)", who, layout);
+    if (ens && ens->P) return fail(QOC_ERR_INVALID, "%s: ens->P must be NULL (the perturbation operators are the last n_perturb of ops)", who);
+    const int E = ens ? ens->members : 1, q = ens ? ens->n_perturb : 0;
+    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
+    if (map) TRY(check_map(who, cfg, map, maxA));
+    const int kt = map ? map->n_terms : cfg->k;
+    if (kt < 1 || (long long)kt + q + 1 > (1 << 20)) return fail(QOC_ERR_INVALID, "%s: %d + %d + 1 operators", who, kt, q);
+    const int K = kt + q + 1;
+    const bool can_merge = K <= QOC_MERGE_MAX_OPS && (long long)cfg->n < (1LL << QOC_MERGE_COL_BITS);
+    if (layout == 2 && K > QOC_MERGE_MAX_OPS)
+        return fail(QOC_ERR_INVALID, "%s: row_layout = 2 (merged) packs the operator index into 8 bits: %d operators, at most %d", who, K, QOC_MERGE_MAX_OPS);
+    if (layout == 2 && !can_merge)
+        return fail(QOC_ERR_INVALID, "%s: row_layout = 2 (merged) packs the column into %d bits: n = %d, below %d", who, QOC_MERGE_COL_BITS, cfg->n, 1 << QOC_MERGE_COL_BITS);
+    SparseHost sh;
+    TRY(check_sparse(who, cfg, ops, K, sh));
+    sh.fleet_entry = true;
+    sh.kgrad = kt;
+    sh.merged = layout == 2 || (layout == 0 && can_merge && QOC_SP_MERGED_AUTO(cfg->n, K));
+    // (the LDS home asked for: the merged sweeps keep their coefficient table beside the vectors)
+    if (sh.merged && ops->vector_home == 1 && cfg->n > qoc_sp_lds_max_n(qoc_sp_tab_bytes(K)))
+        return fail(QOC_ERR_INVALID, "%s: vector_home = 1 (LDS) needs 2 n 16 bytes + %zu bytes of coefficients <= 159 KiB (n = %d, at most %d with %d merged operators)",
+                    who, qoc_sp_tab_bytes(K), cfg->n, qoc_sp_lds_max_n(qoc_sp_tab_bytes(K)), K);
+    if (sh.merged) {
+        std::string why;
+        if (!qoc_ell_merge(cfg->n, sh.ops, sh.rows, why)) return fail(QOC_ERR_INVALID, "%s: the merged rows: %s", who, why.c_str());
+    }
+    Problem p{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh};
+    if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
     if (tr || map) return create_shaped(who, cfg, ens, tr, map, p, out);
     const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
     const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
@@ -1885,6 +1958,16 @@ int qoc_get_member_weights(qoc_handle e, double* pi) {
     return QOC_OK;
 }
 
+int qoc_get_trajectory_gradient(qoc_handle e, double* dLdu) {
+    CHECK_H(e);
+    if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_trajectory_gradient: not an ensemble engine (qoc_create_ensemble)");
+    if (!dLdu) return fail(QOC_ERR_INVALID, "qoc_get_trajectory_gradient: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_trajectory_gradient: nothing evaluated yet");
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(dLdu, e->d.dLdu, (size_t)e->d.B * e->d.k * e->d.steps * sizeof(double), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
 int qoc_get_member_final_unitary(qoc_handle e, double* Uf) {
     CHECK_H(e);
     if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_final_unitary: not an ensemble engine (qoc_create_ensemble)");
@@ -1944,12 +2027,12 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 //   others:     path=generic | path=st_fused
 //   open engines (qoc_create_open, qoc_create_open_fleet): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
 //   sparse engines (qoc_create_sparse): path=sparse nnz=<stored entries> ell=<W_0,..,W_k> vector_home=<lds|global> lds=<bytes of dynamic LDS> threads=<256|1024 of a sweep>
-//   grad_grid=<workgroups of k_sp_grad>
+//   grad_grid=<workgroups of k_sp_grad>; engines of qoc_create_sparse_fleet add rows=<per_operator|merged> merged_width=<Wm, 0 per operator>
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
 // exact engines add exact_variant=<lds|global> exact_lds=<bytes of dynamic LDS, 0 in the global variant> exact_grid=<workgroups of k_exact_grad>
 int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
-    char tmp[384];
+    char tmp[768];
     if (e->path == QOC_PATH_MFMA) {
         const int w = snprintf(tmp, sizeof tmp, "path=mfma nt=%d expm=%d chunks=%d sweeps=%s", e->mf.NT, e->mp.expm_variant, e->mf.C, e->mp.sweeps);
         // the in-place exponential kernel only: what it makes of exactly anti-Hermitian generators (Taylor order 5, 29 <= n <= 32; qoc_mfma_plan.h)
@@ -1971,8 +2054,10 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     } else if (e->path == QOC_PATH_SPARSE) {
         const QocSparse& sp = e->sp;
         int w = snprintf(tmp, sizeof tmp, "path=sparse nnz=%lld ell=", sp.stored);
-        for (size_t j = 0; j < e->sp_widths.size() && w < (int)sizeof tmp - 64; ++j) w += snprintf(tmp + w, sizeof tmp - w, j ? ",%d" : "%d", e->sp_widths[j]);
-        snprintf(tmp + w, sizeof tmp - w, " vector_home=%s lds=%zu threads=%d grad_grid=%d", sp.home == 1 ? "lds" : "global", sp.lds_bytes, sp.threads, sp.grad_grid);
+        for (size_t j = 0; j < e->sp_widths.size() && w < 320; ++j) w += snprintf(tmp + w, sizeof tmp - w, j ? ",%d" : "%d", e->sp_widths[j]);
+        w += snprintf(tmp + w, sizeof tmp - w, " vector_home=%s lds=%zu threads=%d grad_grid=%d", sp.home == 1 ? "lds" : "global", sp.lds_bytes, sp.threads, sp.grad_grid);
+        // engines of qoc_create_sparse_fleet only (the line of qoc_create_sparse stays as it was)
+        if (e->sp_fleet_entry) snprintf(tmp + w, sizeof tmp - w, " rows=%s merged_width=%d", sp.merged ? "merged" : "per_operator", sp.Wm);
     } else if (e->path == QOC_PATH_SMALL) {
         snprintf(tmp, sizeof tmp, "path=small n_pad=%d rows=%d slices_per_row=%d workgroups=%d state_sources=%d lds_kb=%d", e->sm.N, e->sm.R, e->sm.L, e->sm.G,
             e->sm.src ? 1 : 0, (int)((e->sm.lds_bytes + 1023) / 1024));

@@ -63,6 +63,10 @@ class QocSparse(C.Structure):
                 ('vector_home', C.c_int32)]
 
 
+class QocSparsePlan(C.Structure):
+    _fields_ = [('row_layout', C.c_int32)]
+
+
 class QocAdamParams(C.Structure):
     _fields_ = [('rate', C.c_double), ('learning_rate_decay', C.c_double), ('conv_target', C.c_double),
                 ('min_grad', C.c_double), ('max_iterations', C.c_int32), ('poll_every', C.c_int32)]
@@ -93,11 +97,15 @@ _SIGNATURES = {
                                         C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_member_final_density': (C.c_int, [C.c_void_p, _DP]),
     'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_create_sparse_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), C.POINTER(QocSparsePlan), C.POINTER(QocEnsemble),
+                                          C.POINTER(QocFleet), C.POINTER(QocTransfer), C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _IP, _DP,
+                                          C.POINTER(C.c_void_p)]),
     'qoc_get_final_density': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_populations': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_pulse': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_member_scalars': (C.c_int, [C.c_void_p, _DP, _DP]),
     'qoc_get_member_final_unitary': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_get_trajectory_gradient': (C.c_int, [C.c_void_p, _DP]),
     'qoc_set_risk': (C.c_int, [C.c_void_p, C.c_double]),
     'qoc_get_member_weights': (C.c_int, [C.c_void_p, _DP]),
     'qoc_destroy': (C.c_int, [C.c_void_p]),
@@ -314,10 +322,11 @@ class QocComm(object):
         _check(self._lib.qoc_comm_barrier(self._h))
 
 
-def ensemble_arrays(ensemble, n, k, dt):
+def ensemble_arrays(ensemble, n, k, dt, dense=True):
     """The C ABI's qoc_ensemble arrays from a dict with keys `operators` (q Hermitian n x n matrices P_q), `offsets` (E x q), `amp_scales`
-    (E x k) and `weights` (E, used as given): (P = -i dt P_q stacked, offsets, amp_scales, weights), all C-contiguous."""
-    ops = [np.asarray(p, dtype=np.complex128) for p in ensemble.get('operators', [])]
+    (E x k) and `weights` (E, used as given): (P = -i dt P_q stacked, offsets, amp_scales, weights), all C-contiguous.  dense=False (the sparse
+    route: the operators travel with the sparse operators, sparse_perturbations): the operators are only counted, and P is None."""
+    ops = [np.asarray(_densified(p), dtype=np.complex128) for p in ensemble.get('operators', [])] if dense else list(ensemble.get('operators', []))
     q = len(ops)
     amp = np.ascontiguousarray(np.asarray(ensemble['amp_scales'], dtype=np.float64))
     E = amp.shape[0]
@@ -325,6 +334,8 @@ def ensemble_arrays(ensemble, n, k, dt):
     off = np.ascontiguousarray(np.asarray(ensemble.get('offsets', np.zeros((E, 0))), dtype=np.float64).reshape(E, q))
     wt = np.ascontiguousarray(np.asarray(ensemble['weights'], dtype=np.float64))
     assert wt.shape == (E,), wt.shape
+    if not dense:
+        return None, off, amp, wt
     P = np.ascontiguousarray(np.stack([-1j * float(dt) * p for p in ops]) if q else np.zeros((0, n, n), dtype=np.complex128))
     assert P.shape == (q, n, n), P.shape
     return P, off, amp, wt
@@ -378,6 +389,19 @@ def decay_arrays(ensemble, fleet, n, E, dt):
 
 
 VECTOR_HOME = {None: 0, 'auto': 0, 'lds': 1, 'global': 2}
+ROW_LAYOUT = {0: 0, 'auto': 0, 1: 1, 'per_operator': 1, 2: 2, 'merged': 2}
+
+
+def _densified(op):
+    """A perturbation operator for a dense route: a scipy.sparse matrix becomes an array, anything else passes."""
+    return op.toarray() if hasattr(op, 'toarray') else op
+
+
+def sparse_perturbations(ensemble, dt):
+    """The perturbation operators of an ensemble dict as the sparse route takes them: -i dt P_q as complex CSR, a dense P_q converted once and a
+    scipy.sparse one never densified.  They stand behind the controls in HipEngine's sparse_ops (include/qoc.h, qoc_create_sparse_fleet)."""
+    import scipy.sparse as sps
+    return [sps.csr_matrix(-1j * float(dt) * sps.csr_matrix(p, dtype=np.complex128)) for p in (ensemble or {}).get('operators', [])]
 
 
 def sparse_arrays(sparse_ops):
@@ -423,20 +447,26 @@ class HipEngine(object):
     sparse_ops (sparse state transfer, include/qoc.h qoc_create_sparse): a list of k + 1 scipy.sparse matrices -i dt H0, -i dt H_1 .. in place of Hs
     (pass Hs=None, U0=None).  State transfer only; the engine keeps every operator in ELLPACK and never forms an n x n array, so n = 2^14 and more
     fit.  vector_home: None / 'auto', 'lds' or 'global' (where the Taylor chain's two vectors live; A/B runs and tests).  Every other entry point
-    works as on a dense state-transfer engine.  Combines with none of ensemble, transfer, exact_gradient, collapse_ops, Vs or time sharding, and
-    only with path AUTO or PATH_SPARSE (ValueError, before the library is loaded).
+    works as on a dense state-transfer engine.  Combines with none of transfer, exact_gradient, collapse_ops, Vs or time sharding, and only with path
+    AUTO or PATH_SPARSE (ValueError, before the library is loaded).
+    Sparse ensembles, fleets and maps (include/qoc.h qoc_create_sparse_fleet): with ensemble, fleet, control_map or row_layout the engine is made by
+    the sparse ensemble entry point (a line, transfer=, is served by that entry point in C only).  The ensemble's `operators` (Hermitian P_q, scipy.sparse or dense; never densified here) go
+    behind the controls as -i dt P_q; with a control_map sparse_ops holds the drift and the r operators the map feeds.  row_layout: None (a plain
+    sparse engine stays on qoc_create_sparse), 0 / 'auto', 1 / 'per_operator' (the kernels of a plain sparse engine) or 2 / 'merged' (one list per
+    row over all operators; the same numbers, fewer passes per Taylor term); self.plan['rows'] names what ran.  Decay per member (collapse_ops,
+    rate_scales in the ensemble or the fleet) is refused.
 
     control_map (include/qoc.h qoc_create_mapped): a helper_functions.control_map.ControlMap (or a dict alpha / mix / fixed).  Hs then holds the drift
     and the r operators the map feeds, maxA (and one_minus_gauss, the variable, the gradient, get_uks) the k pulses: self.k is the number of pulses,
     self.terms the number of operators.  get_coefficients() gives the (n_seeds, r, steps) coefficients the nominal member's trajectories ran on.
-    Composes with ensemble, transfer and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is
+    Composes with ensemble, transfer, exact_gradient and sparse_ops; not with collapse_ops or time sharding (ValueError, before the library is
     loaded).
 
     fleet (device fleets, include/qoc.h qoc_create_fleet): a helper_functions.fleet.Fleet, or a dict with keys `offsets` (F x E x q) and `amp_scales`
     (F x E x k).  n_seeds = F R control sets, device-major: control set g is optimised on device g // R's members.  `ensemble` then supplies the
     operators, the weights and the risk (its offsets and amp_scales are not read; a Fleet brings its own when `ensemble` is None; neither: one
     member per device, no perturbation).  self.devices is F; every read-back keeps its (n_seeds, ...) shape.  Composes with transfer, control_map
-    and exact_gradient; not with collapse_ops, sparse_ops or time sharding (ValueError, before the library is loaded).
+    and exact_gradient; not with collapse_ops or time sharding (ValueError, before the library is loaded).
 
     decay per member (open-system ensembles and fleets, include/qoc.h qoc_create_open_fleet): an `ensemble` dict with the keys `collapse_ops` (c
     operators as collapse_ops= takes them) and `rate_scales` (E x c, default ones), or a `fleet` with collapse_ops and rate_scales (F x E x c).  Member
@@ -448,9 +478,17 @@ class HipEngine(object):
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
-                 sparse_ops=None, vector_home=None, control_map=None, fleet=None):
+                 sparse_ops=None, vector_home=None, control_map=None, fleet=None, row_layout=None):
         sparse = None
         decay = None
+        if sparse_ops is not None:
+            # decay per member needs the open engine, which the sparse route does not have: named before anything is built
+            fget = (lambda key: None) if fleet is None else (fleet.get if isinstance(fleet, dict) else lambda key: getattr(fleet, key, None))
+            for key in ('collapse_ops', 'rate_scales'):
+                if (ensemble is not None and ensemble.get(key) is not None) or fget(key) is not None:
+                    raise ValueError('HipEngine: sparse_ops (sparse state transfer) does not combine with decay per member (%s)' % key)
+        elif row_layout is not None:
+            raise ValueError('HipEngine: row_layout belongs to sparse_ops (sparse state transfer)')
         if (ensemble is not None or fleet is not None) and sparse_ops is None:
             # (before the fleet's own refusal of collapse_ops=: decay that the members carry is named as such)
             if fleet is not None and ensemble is None and not isinstance(fleet, dict):
@@ -464,21 +502,24 @@ class HipEngine(object):
                 if given:
                     raise ValueError('HipEngine: an ensemble or fleet with decay does not combine with %s' % name)
         if fleet is not None:
-            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
+            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None),
+                                ('sparse_ops (sparse state transfer) beside a dense Hs', sparse_ops is not None and Hs is not None),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
                 if given:
                     raise ValueError('HipEngine: fleet does not combine with %s' % name)
             if ensemble is None and not isinstance(fleet, dict):
                 ensemble = fleet.device(0)
         if control_map is not None:
-            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None), ('sparse_ops (sparse state transfer)', sparse_ops is not None),
+            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None),
+                                ('sparse_ops (sparse state transfer) beside a dense Hs', sparse_ops is not None and Hs is not None),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
                 if given:
                     raise ValueError('HipEngine: control_map does not combine with %s' % name)
             from quantum_optimal_control.helper_functions import control_map as _cmap
-            control_map = _cmap.validate(control_map, k=np.shape(maxA)[0], r=np.shape(Hs)[0] - 1, steps=steps)
+            control_map = _cmap.validate(control_map, k=np.shape(maxA)[0], r=(len(sparse_ops) if sparse_ops is not None else np.shape(Hs)[0]) - 1, steps=steps)
         if sparse_ops is not None:
-            for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
+            # (transfer: the line runs on sparse operators behind the C ABI, qoc_create_sparse_fleet; this binding keeps its refusal)
+            for name, given in (('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
                                 ('collapse_ops', collapse_ops is not None), ('time sharding', time_comm is not None or int(time_shards) > 0),
                                 ('Vs (dressed forbidden levels)', Vs is not None), ('a dense Hs', Hs is not None), ('U0', U0 is not None),
                                 ('path %s' % (path,), int(path) not in (PATH_AUTO, PATH_SPARSE))):
@@ -488,7 +529,12 @@ class HipEngine(object):
                 raise ValueError('HipEngine: sparse_ops needs state_transfer=True (unitary mode propagates an n x n matrix)')
             if vector_home not in VECTOR_HOME:
                 raise ValueError("HipEngine: vector_home is None, 'auto', 'lds' or 'global', got %r" % (vector_home,))
-            sparse = sparse_arrays(sparse_ops)
+            if ensemble is not None and ensemble.get('amp_scales') is None:
+                raise ValueError('HipEngine: an ensemble on sparse_ops needs amp_scales (E x k) and weights (helper_functions.robust.validate)')
+            if row_layout is not None and row_layout not in ROW_LAYOUT:
+                raise ValueError("HipEngine: row_layout is None, 0 / 'auto', 1 / 'per_operator' or 2 / 'merged', got %r" % (row_layout,))
+            # (the ensemble's perturbation operators stand behind the controls, kept sparse)
+            sparse = sparse_arrays(list(sparse_ops) + sparse_perturbations(ensemble, dt))
         if collapse_ops is not None:
             for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
                                 ('time sharding', time_comm is not None or int(time_shards) > 0)):
@@ -504,7 +550,7 @@ class HipEngine(object):
             k = Hs.shape[0] - 1 if control_map is None else control_map.n_pulses
             n = Hs.shape[1]
         else:
-            k, n = len(sparse_ops) - 1, sparse[0]
+            k, n = (len(sparse_ops) - 1 if control_map is None else control_map.n_pulses), sparse[0]
         V = np.ascontiguousarray(np.asarray(V, dtype=np.complex128))
         m = V.shape[1]
         self.n, self.k, self.m, self.steps, self.n_seeds = n, k, m, int(steps), int(n_seeds)
@@ -547,11 +593,11 @@ class HipEngine(object):
         self.samples = None                           # transfer-function GRAPE: P, the length of the variable's rows
         ens = None
         if ensemble is not None:
-            P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt)
+            P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt, dense=sparse is None)
             ens = QocEnsemble()
-            ens.members, ens.n_perturb = amp.shape[0], P.shape[0]
-            ens.P = _dp(P.view(np.float64)) if P.shape[0] else None
-            ens.offsets = _dp(off) if P.shape[0] else None
+            ens.members, ens.n_perturb = amp.shape[0], off.shape[1]
+            ens.P = _dp(P.view(np.float64)) if (P is not None and P.shape[0]) else None
+            ens.offsets = _dp(off) if off.shape[1] else None
             ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
             self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
         tr = None
@@ -572,7 +618,23 @@ class HipEngine(object):
             foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
             fl = QocFleet()
             fl.devices, fl.offsets, fl.amp_scales = famp.shape[0], (_dp(foff) if foff.shape[2] else None), _dp(famp)
-        if decay is not None:
+        self.row_layout = None
+        if sparse is not None and (ens is not None or fl is not None or tr is not None or cmap is not None or row_layout is not None):
+            # sparse operators through the ensemble funnel (include/qoc.h, qoc_create_sparse_fleet); a plain sparse engine stays on qoc_create_sparse
+            _, indptr, row, col, val = sparse
+            sp = QocSparse()
+            sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
+            sp.val, sp.vector_home = _dp(val.view(np.float64)), VECTOR_HOME[vector_home]
+            pl = QocSparsePlan()
+            pl.row_layout = ROW_LAYOUT[0 if row_layout is None else row_layout]
+            _check(lib.qoc_create_sparse_fleet(C.byref(cfg), C.byref(sp), C.byref(pl), None if ens is None else C.byref(ens),
+                                               None if fl is None else C.byref(fl), None if tr is None else C.byref(tr),
+                                               None if cmap is None else C.byref(cmap), *(args[2:8] + args[-1:])))
+            if tr is not None:
+                self.samples = int(tr.n_samples)
+            self.devices = 0 if fl is None else int(fl.devices)
+            self.row_layout = int(pl.row_layout)
+        elif decay is not None:
             D, rates = decay
             if fl is not None and rates.shape[0] != fl.devices:
                 raise ValueError('HipEngine: rate_scales are for %d devices, the fleet has %d' % (rates.shape[0], fl.devices))
@@ -614,17 +676,18 @@ class HipEngine(object):
             _check(lib.qoc_create(C.byref(cfg), *args))
         else:
             _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
+        self.perturbations = 0 if ens is None else int(ens.n_perturb)     # q: the frozen control rows behind the `terms` rows of every trajectory
         if ens is not None:
             self.members = int(ens.members)
-        elif fleet is not None:
-            self.members = 1
+        elif fleet is not None or self.row_layout is not None:
+            self.members = 1                          # (a sparse engine of the ensemble entry point: one nominal member)
         self.risk = 0.0
         if ensemble is not None and float(ensemble.get('risk', 0.0)) > 0:
             self.set_risk(ensemble['risk'])
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
-        buf = C.create_string_buffer(512)
-        _check(lib.qoc_plan_describe(self._h, buf, 512))
+        buf = C.create_string_buffer(1024)
+        _check(lib.qoc_plan_describe(self._h, buf, 1024))
         self.plan = dict(kv.split('=', 1) for kv in buf.value.decode().split())
         if time_comm is not None:
             _check(lib.qoc_set_time_comm(self._h, time_comm._h))
@@ -779,6 +842,13 @@ class HipEngine(object):
         """Ensemble engines: the tilted weights pi_e of the last evaluation, [n_seeds][members] (the members' own weights at risk 0)."""
         out = np.empty((self.n_seeds, max(self.members, 1)))
         _check(self._lib.qoc_get_member_weights(self._h, _dp(out)))
+        return out
+
+    def trajectory_gradient(self):
+        """Ensemble engines: the trajectories' gradient array of the last evaluation, before the member reduction:
+        (n_seeds, members, terms + perturbations, steps).  On a sparse ensemble engine the frozen perturbation rows are exact zeros."""
+        out = np.empty((self.n_seeds, max(self.members, 1), self.terms + self.perturbations, self.steps))
+        _check(self._lib.qoc_get_trajectory_gradient(self._h, _dp(out)))
         return out
 
     def member_final_unitary(self):

@@ -37,6 +37,43 @@ def max_abs_entry(H0, Hops, maxA):
     return float(np.max(np.abs(H_max.data))) if H_max.nnz else 0.0
 
 
+def member_max_abs_entry(H0, Hops, amps, perturbations=(), offsets=()):
+    """The rule above for one member of an ensemble: the largest stored entry of |H0 + sum_k amps_k H_k| + sum_q |offsets_q| |P_q|.  The
+    perturbations enter by their absolute values, entry for entry, so the figure bounds the largest entry of the member's H_max whatever the signs
+    of its offsets (and equals max_abs_entry without perturbations).  Sparse sums only: no n x n array."""
+    H_max = as_csr(H0)
+    for amp, op in zip(amps, Hops):
+        H_max = H_max + float(amp) * as_csr(op)
+    bound = abs(sps.csr_matrix(H_max))
+    for off, p in zip(offsets, perturbations):
+        bound = bound + abs(float(off)) * abs(as_csr(p))
+    bound = sps.csr_matrix(bound)
+    return float(np.max(np.abs(bound.data))) if bound.nnz else 0.0
+
+
+def choose_taylor_members(H0, Hops, maxA, devices, dt, steps, unitary_error, control_map=None):
+    """The Taylor order of a sparse ensemble, fleet or mapped problem: choose_taylor_terms on every member's own operators, the largest order wins
+    (as robust.choose_taylor and fleet.choose_taylor take it for dense members).  devices: a list of validated ensemble dicts (one for
+    Grape(robust=), one per device of a fleet), or [None]: the nominal member alone.  Member e runs the controls amp_scales[e, j] maxA_j -- under a
+    control map the coefficient bounds control_map.coefficient_bounds gives for those pulse bounds, one per operator the map feeds -- and the
+    perturbations |offsets[e, q]| |P_q|."""
+    maxA = np.asarray(maxA, dtype=np.float64).reshape(-1)
+    best = 0
+    for dev in devices:
+        members = 1 if dev is None else dev['weights'].shape[0]
+        for e in range(members):
+            scale = np.ones_like(maxA) if dev is None else np.abs(dev['amp_scales'][e])
+            amps = scale * maxA
+            if control_map is not None:
+                from quantum_optimal_control.helper_functions.control_map import coefficient_bounds
+                amps = coefficient_bounds(control_map, amps)
+            perts = [] if dev is None else dev['operators']
+            offs = [] if dev is None else dev['offsets'][e]
+            x = dt * member_max_abs_entry(H0, Hops, amps, perts, offs)
+            best = max(best, int(choose_taylor_terms(x, steps, unitary_error)))
+    return best
+
+
 def choose_taylor_terms(x, steps, unitary_error):
     """The reference's downward search (Choose_exp_terms) with the scalar metric, no squarings: the first term count that fails."""
     n_terms = MAX_TAYLOR_TERMS
@@ -53,7 +90,9 @@ class SparseSystemParameters(SystemParameters):
     sparse_route = True
 
     def __init__(self, H0, Hops, Hnames, U, total_time, steps, states_concerned_list, maxA, draw, initial_guess, show_plots, Unitary_error,
-                 reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs):
+                 reg_coeffs, save, file_path, Taylor_terms, use_gpu, use_inter_vecs, members=None):
+        # members: the validated ensemble dicts whose members the Taylor order has to serve (choose_taylor_members), or None: the nominal problem
+        self.members = members
         self.sparse_U = self.sparse_H = self.sparse_K = False        # the reference's flags stay ignored under use_gpu
         self.use_inter_vecs = use_inter_vecs
         self.use_gpu = use_gpu
@@ -97,7 +136,9 @@ class SparseSystemParameters(SystemParameters):
         self.ops_len = len(self.ops_c)
         self.ops_sparse = [sps.csr_matrix(-1j * self.dt * op) for op in [self.H0_c] + self.ops_c]
         self.scaling = 0
-        if self.Taylor_terms is None:
+        if self.Taylor_terms is None and self.members is not None:
+            self.exp_terms = choose_taylor_members(self.H0_c, self.ops_c, self.ops_max_amp, self.members, self.dt, self.steps, self.Unitary_error)
+        elif self.Taylor_terms is None:
             x = self.dt * max_abs_entry(self.H0_c, self.ops_c, self.ops_max_amp)
             self.exp_terms = choose_taylor_terms(x, self.steps, self.Unitary_error)
         else:

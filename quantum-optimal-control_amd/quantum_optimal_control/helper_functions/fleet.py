@@ -20,7 +20,7 @@ class Fleet(object):
     control set and iterations (F,) it took.  collapse_ops (c operators, or None: closed devices) and rate_scales (F, E, c), default ones."""
 
     def __init__(self, operators, offsets, amp_scales, weights=None, risk=0.0, collapse_ops=None, rate_scales=None):
-        self.operators = [np.asarray(p) for p in operators]
+        self.operators = [_robust.as_operator(p) for p in operators]
         self.offsets = np.asarray(offsets, dtype=np.float64)
         self.amp_scales = np.asarray(amp_scales, dtype=np.float64)
         self.weights = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
@@ -70,7 +70,7 @@ def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=No
     if k is None:
         raise ValueError('fleet.devices: k (the number of pulses) is required')
     k = int(k)
-    operators = [np.asarray(p) for p in operators]
+    operators = [_robust.as_operator(p) for p in operators]
     q = len(operators)
     F = None
     if offsets is not None and (q or np.size(offsets)):
@@ -93,7 +93,7 @@ def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=No
     off = np.zeros((F, 1, q)) if not q else offsets.reshape(F, 1, q)
     amp = np.ones((F, 1, k)) if amp_scales is None else amp_scales.reshape(F, 1, k)
     rates = None if rate_scales is None else rate_scales.reshape(F, 1, -1)
-    return validate(Fleet(operators, off, amp, collapse_ops=collapse_ops, rate_scales=rates), None, k)
+    return validate(Fleet(operators, off, amp, collapse_ops=collapse_ops, rate_scales=rates), None, k, sparse=None)
 
 
 def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, collapse_ops=None, rate_scales=None):
@@ -107,8 +107,8 @@ def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, col
         k = np.shape(robust['amp_scales'])[1] if robust.get('amp_scales') is not None else None
     centre = devices(operators, offsets, amp_scales, k=k, collapse_ops=collapse_ops, rate_scales=rate_scales)
     q = len(centre.operators)
-    ens = _robust.validate(robust, centre.operators[0].shape[0] if q else None, int(k))
-    if len(ens['operators']) != q or any(not np.array_equal(a, b) for a, b in zip(ens['operators'], centre.operators)):
+    ens = _robust.validate(robust, centre.operators[0].shape[0] if q else None, int(k), sparse=None)
+    if len(ens['operators']) != q or any(not _robust.same_operator(a, b) for a, b in zip(ens['operators'], centre.operators)):
         raise ValueError('fleet.around: the ensemble must perturb the fleet\'s own operators (%d given, the ensemble has %d)'
                          % (q, len(ens['operators'])))
     off = centre.offsets[:, 0][:, None, :] + ens['offsets'][None, :, :]
@@ -122,14 +122,16 @@ def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, col
         F, E, c = off.shape[0], off.shape[1], len(cops)
         dev_r = np.ones((F, 1, c)) if centre.rate_scales is None else centre.rate_scales
         rates = dev_r[:, 0][:, None, :] * (ens['rate_scales'] if 'rate_scales' in ens else np.ones((E, c)))[None, :, :]
-    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=cops, rate_scales=rates), None, int(k))
+    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=cops, rate_scales=rates), None, int(k),
+                    sparse=None)
 
 
-def validate(fleet, n, k):
+def validate(fleet, n, k, sparse=False):
     """Checks a Fleet against a problem of n levels (None: from the operators) and k pulses and returns a normalised copy: operators complex
     Hermitian n x n, offsets (F, E, q), amp_scales (F, E, k), weights (E,) summing to 1 (default uniform), risk a finite float >= 0.
     collapse_ops (None, or c complex n x n matrices) and rate_scales (F, E, c), finite and >= 0 (default ones; None without collapse_ops).
-    Raises ValueError with the cause."""
+    Raises ValueError with the cause.  sparse=True (the sparse state-transfer route): the operators come back as complex CSR and are never
+    densified, and decay is refused; sparse=None (the builders): the operators stay as given (robust.validate's rules)."""
     if not isinstance(fleet, Fleet):
         raise ValueError('fleet: a helper_functions.fleet.Fleet (fleet.devices, fleet.around)')
     amp = np.array(fleet.amp_scales, dtype=np.float64)            # (copies: the normalised fleet owns its arrays)
@@ -158,7 +160,7 @@ def validate(fleet, n, k):
             raise ValueError('fleet: rate_scales must be finite and >= 0')
         dev0.update(collapse_ops=cops, rate_scales=rates[0])
     try:
-        ens = _robust.validate(dev0, n, k)
+        ens = _robust.validate(dev0, n, k, sparse=sparse)
     except ValueError as err:
         raise ValueError(str(err).replace('robust:', 'fleet:', 1))
     return Fleet(ens['operators'], off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=ens.get('collapse_ops'), rate_scales=rates)

@@ -28,6 +28,54 @@ def _rows(values, width, name):
     return np.array(out, dtype=np.float64).reshape(len(out), width)
 
 
+def _is_sparse(op):
+    """A scipy.sparse matrix (duck-typed, so that dense-only callers never import scipy)."""
+    return hasattr(op, 'tocsr') and hasattr(op, 'nnz')
+
+
+def as_operator(op):
+    """A perturbation operator as it was given: a scipy.sparse matrix stays one (np.asarray would wrap it in a 0-d object array), anything else
+    becomes an array."""
+    return op if _is_sparse(op) else np.asarray(op)
+
+
+def same_operator(a, b):
+    """Entry-for-entry equality of two operators, either of which may be scipy.sparse; a sparse one is never densified."""
+    if _is_sparse(a) or _is_sparse(b):
+        import scipy.sparse as sps
+        a, b = sps.csr_matrix(a), sps.csr_matrix(b)
+        return a.shape == b.shape and (a != b).nnz == 0
+    return np.array_equal(a, b)
+
+
+def _validated_operators(operators, n, sparse):
+    """The perturbation operators for the route at hand, checked square, n x n and Hermitian: complex CSR on the sparse route (sparse=True: a dense
+    one is converted, a sparse one is never densified), complex arrays on a dense route (sparse=False: a sparse one is densified); sparse=None (the
+    builders, which know no route yet): every operator in the kind it was given as.  Returns (operators, n)."""
+    ops = []
+    kind = sparse
+    for i, p in enumerate(operators):
+        sparse = _is_sparse(p) if kind is None else kind
+        if sparse:
+            import scipy.sparse as sps
+            p = sps.csr_matrix(p, dtype=np.complex128)
+        else:
+            p = np.asarray(p.toarray() if _is_sparse(p) else p, dtype=np.complex128)
+        if p.ndim != 2 or p.shape[0] != p.shape[1] or (n is not None and p.shape[0] != n):
+            raise ValueError('robust: operator %d has shape %s, expected %s' % (i, p.shape, (n, n) if n is not None else 'square'))
+        if n is None:
+            n = p.shape[0]
+        if sparse:
+            top = float(np.max(np.abs(p.data))) if p.nnz else 0.0
+            diff = (p - p.conj().T).tocsr()
+            if diff.nnz and float(np.max(np.abs(diff.data))) > 1e-12 * max(1.0, top):
+                raise ValueError('robust: operator %d is not Hermitian' % i)
+        elif not np.allclose(p, p.conj().T, rtol=0.0, atol=1e-12 * max(1.0, float(np.max(np.abs(p))))):
+            raise ValueError('robust: operator %d is not Hermitian' % i)
+        ops.append(p)
+    return ops, n
+
+
 def has_decay(robust):
     """True when the ensemble dict makes its members open problems (the key collapse_ops is given, an empty list included)."""
     return isinstance(robust, dict) and robust.get('collapse_ops') is not None
@@ -41,7 +89,7 @@ def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=N
     collapse_ops, rate_scales: the members are open problems; the rate-scale rows (each c values, or a scalar for all c operators) are a third
     axis of the product (innermost), and the nominal point has all rate scales 1 as well.
     Returns the dict Grape(robust=...) takes."""
-    operators = [np.asarray(p) for p in operators]
+    operators = [as_operator(p) for p in operators]
     q = len(operators)
     if k is None:
         raise ValueError('ensemble_grid: k (the number of control Hamiltonians) is required')
@@ -72,15 +120,18 @@ def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=N
     if collapse_ops is not None:
         ens['collapse_ops'] = list(collapse_ops)
         ens['rate_scales'] = np.array([pts[i][2] for i in order]).reshape(len(pts), c)
-    return validate(ens, None, k)
+    return validate(ens, None, k, sparse=None)          # (the operators stay as given: the route's own validate call makes them sparse or dense)
 
 
-def validate(robust, n, k):
+def validate(robust, n, k, sparse=False):
     """Checks a robust dict (keys operators, offsets, amp_scales, weights, risk) against a problem of n levels (None: from the operators) and
     k controls and returns it normalised: operators a list of q complex n x n Hermitian matrices, offsets (E, q), amp_scales (E, k)
     (default ones), weights (E,) summing to 1 (default uniform), risk a finite float >= 0 (default 0.0: the weighted mean).  With the key
     collapse_ops the result also holds collapse_ops (c complex n x n matrices, open_system.validate's rules) and rate_scales (E, c), finite and
-    >= 0 (default ones); without it the result has exactly the five keys above.  Raises ValueError."""
+    >= 0 (default ones); without it the result has exactly the five keys above.  Raises ValueError.
+    sparse=True (the sparse state-transfer route): the operators come back as complex CSR matrices -- a scipy.sparse operator is never densified,
+    a dense one is converted once -- and the decay keys are refused; sparse=False densifies scipy.sparse operators; sparse=None (ensemble_grid and
+    the fleet builders, before any route is known) leaves every operator in the kind it was given as and refuses nothing."""
     if not isinstance(robust, dict):
         raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights, risk')
     unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk', 'collapse_ops', 'rate_scales'}
@@ -92,16 +143,12 @@ def validate(robust, n, k):
         raise ValueError('robust: risk must be a number >= 0, got %r' % (robust.get('risk'),))
     if not (np.isfinite(risk) and risk >= 0):
         raise ValueError('robust: risk must be finite and >= 0, got %r' % risk)
-    ops = [np.asarray(p, dtype=np.complex128) for p in robust.get('operators', [])]
+    ops, n = _validated_operators(robust.get('operators', []), n, sparse)
     q = len(ops)
-    for i, p in enumerate(ops):
-        if p.ndim != 2 or p.shape[0] != p.shape[1] or (n is not None and p.shape[0] != n):
-            raise ValueError('robust: operator %d has shape %s, expected %s' % (i, p.shape, (n, n) if n is not None else 'square'))
-        if n is None:
-            n = p.shape[0]
-        if not np.allclose(p, p.conj().T, rtol=0.0, atol=1e-12 * max(1.0, float(np.max(np.abs(p))))):
-            raise ValueError('robust: operator %d is not Hermitian' % i)
     cops, rates = robust.get('collapse_ops'), robust.get('rate_scales')
+    if sparse is True and (cops is not None or rates is not None):
+        raise ValueError('robust: decay per member (%s) is not available on scipy.sparse Hamiltonians (sparse state transfer)'
+                         % ('collapse_ops' if cops is not None else 'rate_scales'))
     if rates is not None and cops is None:
         raise ValueError('robust: rate_scales given without collapse_ops')
     if cops is not None:

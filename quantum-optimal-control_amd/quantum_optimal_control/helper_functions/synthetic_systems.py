@@ -76,3 +76,20 @@ def xx_chain(spins, coupling=1.0, control_sites=None):
         return v
 
     return H0, Hops, Hnames, excitation
+
+
+def xx_bonds(spins, coupling=1.0):
+    """The bonds of xx_chain one by one: spins - 1 scipy.sparse operators (coupling / 2) (X_i X_{i+1} + Y_i Y_{i+1}) whose sum is its H0 -- the
+    perturbation operators of a chain whose couplings are known to a few percent (one offset per bond).  Built with scipy.sparse.kron; no dense
+    n x n array is formed."""
+    import scipy.sparse as sps
+    X = sps.csr_matrix(np.array([[0, 1], [1, 0]], dtype=np.complex128))
+    Y = sps.csr_matrix(np.array([[0, -1j], [1j, 0]], dtype=np.complex128))
+    eye = lambda d: sps.identity(d, dtype=np.complex128, format='csr')
+    bonds = []
+    for i in range(spins - 1):
+        pair = sps.kron(X, X, format='csr') + sps.kron(Y, Y, format='csr')
+        op = sps.csr_matrix((coupling / 2.0) * sps.kron(sps.kron(eye(2 ** i), pair, format='csr'), eye(2 ** (spins - 2 - i)), format='csr'))
+        op.eliminate_zeros()
+        bonds.append(op)
+    return bonds

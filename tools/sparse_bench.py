@@ -9,8 +9,15 @@ problem, from the same library -- the numbers of profiles/sparse_state_transfer.
                                            attempted only when the host has the 13 GB its three dense operators take)
     python tools/sparse_bench.py threads   the sweeps' workgroup size: 256 against 1024 threads (QOC_EXPERIMENTAL=1 QOC_SP_THREADS) at every size above,
                                            one and 64 control sets -- what QOC_SP_WIDE_FROM in csrc/qoc_sparse.h rests on
+    python tools/sparse_bench.py ensemble [--spins 6,8,10,12] [--members 1,8] [--q 0,bonds] [--layouts 1,2] [--rounds 3]
+                                           sparse ensembles (qoc_create_sparse_fleet): the same chains with E members and q perturbation
+                                           operators (bonds: one per bond of the chain, spins - 1 of them, offsets of +-5 %), one control set; per-operator
+                                           rows (row_layout 1) against merged rows (2), the two engines alive side by side and timed alternately `rounds`
+                                           times -- the numbers of profiles/sparse_ensemble.txt and what QOC_SP_MERGED_AUTO in csrc/qoc_sparse.h rests on
+    python tools/sparse_bench.py plain     the plain sparse rows at 6 and 10 spins (n = 64, 1024), one and 64 control sets: the figures to hold against
+                                           the same rows of another build of the library
 
-This tool only times; tests/test_sparse_gpu.py checks what the engine computes."""
+This tool only times; tests/test_sparse_gpu.py and tests/test_sparse_ensemble_gpu.py check what the engines compute."""
 import os
 import sys
 
@@ -129,5 +136,64 @@ def threads():
                     eng.close()
 
 
+def plain():
+    for spins in (6, 10):
+        sp = problem(spins)
+        for n_seeds in (1, 64):
+            eng = engine(sp, n_seeds)
+            try:
+                lo, hi, iters = ms_per_iteration(eng, sp, n_seeds)
+                print('plain sparse n = %5d x %2d control sets: %9.4f ms per iteration (max of 3: %9.4f; %d iterations each)' % (2 ** spins, n_seeds, lo, hi, iters), flush=True)
+            finally:
+                eng.close()
+
+
+def ensemble_of(spins, E, q):
+    """E members over the first q bonds of the chain: member 0 nominal, the others with coupling errors of +-5 %."""
+    from quantum_optimal_control.helper_functions import robust
+    from quantum_optimal_control.helper_functions.synthetic_systems import xx_bonds
+    rng = np.random.default_rng(2)
+    off = np.vstack([np.zeros(q), rng.uniform(-0.05, 0.05, size=(E - 1, q))]) if q else np.zeros((E, 0))
+    return robust.validate(dict(operators=xx_bonds(spins)[:q], offsets=off, amp_scales=np.ones((E, 2))), 2 ** spins, 2, sparse=True)
+
+
+def ensemble(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='sparse_bench.py ensemble')
+    ap.add_argument('--spins', default='6,8,10,12')
+    ap.add_argument('--members', default='1,8')
+    ap.add_argument('--q', default='0,bonds')
+    ap.add_argument('--layouts', default='1,2')
+    ap.add_argument('--rounds', type=int, default=3)
+    args = ap.parse_args(argv)
+    layouts = [int(x) for x in args.layouts.split(',')]
+    names = {0: 'auto', 1: 'per_operator', 2: 'merged'}
+    for spins in [int(x) for x in args.spins.split(',')]:
+        sp = problem(spins)
+        print('--- %d spins, n = %d, %d slices, Taylor terms %d' % (spins, 2 ** spins, STEPS, sp.exp_terms), flush=True)
+        for qname in args.q.split(','):
+            q = spins - 1 if qname == 'bonds' else int(qname)
+            for E in [int(x) for x in args.members.split(',')]:
+                ens = ensemble_of(spins, E, q)
+                engines = {lay: engine(sp, 1, ensemble=ens, row_layout=lay) for lay in layouts}
+                try:
+                    times = {lay: [] for lay in layouts}
+                    for _ in range(args.rounds):                                    # alternating: a drift of the machine hits both alike
+                        for lay in layouts:
+                            lo, hi, iters = ms_per_iteration(engines[lay], sp, 1, budget_ms=400.0)
+                            times[lay] += [lo, hi]
+                    for lay in layouts:
+                        t = times[lay]
+                        print('n = %5d  operators = %2d (q = %2d)  E = %d  %-12s %9.4f ms per iteration (min; max %9.4f over %d windows)  rows=%s merged_width=%s lds=%s'
+                              % (2 ** spins, 3 + q, q, E, names[lay], min(t), max(t), len(t), engines[lay].plan['rows'], engines[lay].plan['merged_width'],
+                                 engines[lay].plan['lds']), flush=True)
+                finally:
+                    for eng in engines.values():
+                        eng.close()
+
+
 if __name__ == '__main__':
-    {'compare': compare, 'large': large, 'threads': threads}[sys.argv[1]]()
+    if sys.argv[1] == 'ensemble':
+        ensemble(sys.argv[2:])
+    else:
+        {'compare': compare, 'large': large, 'threads': threads, 'plain': plain}[sys.argv[1]]()
