@@ -326,6 +326,40 @@ int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const q
 /* rho_ij(T) of every member at the last evaluation, [n_seeds][E][m][m][n][n] complex.  QOC_ERR_STATE on every other engine. */
 int qoc_get_member_final_density(qoc_handle h, double* rho);
 
+/* ---- open-system running costs: penalties on expectation values along the pulse (the reference's forbidden-level regulariser is the special case
+ * of a projector on a closed system, regularization_functions.py:81-85) -----------------------------------------------------------------------
+ * Per trajectory (a control set, or a member of one), with L observables O_l (n x n complex), coefficients a_l and powers p_l in {1, 2}:
+ *   x_l,i(tau) = Re sum_ac conj(O_l[a][c]) rho_ii(tau)[a][c]                       (= Re Tr(O_l rho_ii(tau)) for a Hermitian O_l)
+ *   R          = sum_l (a_l / steps) sum_{tau = 0 .. steps} sum_{i < m} x_l,i(tau)^p_l / p_l
+ * R is the trajectory's state regulariser: reg_loss = loss + R + the pulse regularisers, the stop rule reads loss as before, and on an ensemble,
+ * line, map or fleet the members' R go where the closed engines' forbidden levels go (the weighted mean, the cost c_e of qoc_set_risk,
+ * qoc_get_member_scalars).  O_l = |l><l| with p = 2 is the reference's forbidden level, O_l = v v^dagger its dressed form.
+ *   grad : the costates of the diagonal pairs get a source per slice -- Lambda_ii(t+1) += sum_l (a_l / steps) x_l,i(t+1)^(p_l - 1) O_l, added after
+ *          rho_ii(t+1) is loaded and before the slice's contraction, once per slice (not per sub-step); off-diagonal pairs are untouched.  First order
+ *          in dt, as the engine's gradient is.
+ *   tau = 0 : the start operators (from U0 V in unitary mode, V in state transfer) count in the value and, being independent of the pulse, not in the
+ *          gradient -- the convention of qoc_get_populations.  (The reference's closed regulariser takes V itself at tau = 0: the closed-limit value
+ *          equals it in state transfer and in unitary mode with U0 = I, and differs by that pulse-independent term otherwise.)
+ * qoc_create_open_costs takes everything qoc_create_open_fleet takes, with the same meaning (all four of ens, fleet, transfer and map may be NULL);
+ * with n_obs = 0 (costs may then be NULL) it computes qoc_create_open_fleet's values bit for bit; with n_obs > 0 qoc_plan_describe appends
+ * running_costs=<L>.  Two evaluations are bit-identical.
+ * QOC_ERR_INVALID, with the cause named and before any device is touched: everything qoc_create_open_fleet refuses (cfg.n_forbidden, has_speed_up and
+ * forbid_dressed included: they keep their meaning); NULL arrays with n_obs > 0; n_obs outside 0 .. 16; a power other than 1 or 2; a non-finite entry
+ * or coefficient. */
+typedef struct qoc_running_costs {
+    int32_t n_obs;               /* L, 0 .. 16 */
+    const double* O;             /* [L][n][n] complex, row-major */
+    const double* coeffs;        /* [L] finite; the engine divides by cfg->steps */
+    const int32_t* powers;       /* [L] 1 or 2 */
+} qoc_running_costs;
+/* after map come exactly qoc_create_open's remaining arguments */
+int qoc_create_open_costs(const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const qoc_ensemble* ens,
+                          const qoc_fleet* fleet, const qoc_transfer* transfer, const qoc_control_map* map, const double* Hs, const double* U0,
+                          const double* V, const double* W, const double* maxA, const double* one_minus_gauss, qoc_handle* out);
+/* x_l,i(tau) of the last evaluation, [n_seeds][steps+1][L][m] (tau = 0 is the start; member 0 of each control set).  QOC_ERR_STATE on every engine
+ * without running costs. */
+int qoc_get_expectations(qoc_handle h, double* x);
+
 /* ---- sparse state transfer: the operators are never dense (the reference has sparse_H / sparse_U / sparse_K for systems built from Kronecker products
  * and switches them off under use_gpu, main_grape/grape.py:28-32) ----------------------------------------------------------------------------
  * The k + 1 operators -i dt H0, -i dt H_1 .. come as COO entries in any order; duplicates of a position are summed, explicit zeros are kept.  The

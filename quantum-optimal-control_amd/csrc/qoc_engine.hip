@@ -657,6 +657,7 @@ struct DecayHost {
     const double* scales;            // [F][E][c] or null (ones)
     int F, E;                        // the rows of `scales` (1, 1: qoc_create_open)
     const char* who;
+    const qoc_running_costs* costs = nullptr;   // qoc_create_open_costs: the checked running costs (n_obs > 0), else null
 };
 
 // the operators of qoc_create_sparse as the host prepared them: one ELLPACK block per operator (csrc/qoc_sparse_host.h)
@@ -1116,6 +1117,18 @@ static int setup_lindblad(qoc_engine* e, const Problem& p, const DecayHost* op) 
     TRY(dev_alloc(e, &L.hist, B * L.R * d.steps * nn));
     TRY(dev_alloc(e, &L.partial, B * L.R * d.k * d.steps));
     TRY(dev_alloc(e, &L.pop, B * (d.steps + 1) * n * d.m));
+    if (op->costs) {
+        // running costs: the observables as they came, the coefficients divided by steps (as every state regulariser's are)
+        const int nc = op->costs->n_obs;
+        std::vector<double> ca(op->costs->coeffs, op->costs->coeffs + nc);
+        for (double& a : ca) a /= (double)d.steps;
+        L.nc = nc;
+        TRY(dev_upload(e, &L.cO, (const cplx*)op->costs->O, nn * nc));
+        TRY(dev_upload(e, &L.ca, (const double*)ca.data(), (size_t)nc));
+        TRY(dev_upload(e, &L.cp, (const int*)op->costs->powers, (size_t)nc));
+        TRY(dev_alloc(e, &L.cost_partial, B * L.R));
+        TRY(dev_alloc(e, &L.expct, B * (d.steps + 1) * nc * d.m));
+    }
     HIP_TRY_MSG(qoc_lb_lds_opt_in(L), "%s: cannot reserve %zu bytes of LDS for the open-system kernels", op->who, L.lds_bytes);
     return QOC_OK;
 }
@@ -1522,16 +1535,31 @@ int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_f
 
 // an open engine through the ensemble funnel: the open engine's own refusals and the rate scales checked here, everything about the member tables,
 // the line and the map by the entry point that ens, fleet, transfer and map select -- all on the host and before any device is touched
-int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
-                          const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
-                          const double* one_minus_gauss, qoc_handle* out) {
-    const char* who = "qoc_create_open_fleet";
+// (`costs`: the running costs of qoc_create_open_costs, checked here; null, or n_obs = 0: the engine of qoc_create_open_fleet)
+static int create_open_fleet(const char* who, const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const qoc_ensemble* ens,
+                             const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs, const double* U0,
+                             const double* V, const double* W, const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
     if (!cfg || !decay || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int c = decay->n_collapse;
     TRY(check_open(who, cfg, c, decay->C));
+    if (costs) {
+        const int nc = costs->n_obs;
+        if (nc < 0 || nc > QOC_LB_MAX_COSTS) return fail(QOC_ERR_INVALID, "%s: n_obs = %d (0 .. %d running costs)", who, nc, QOC_LB_MAX_COSTS);
+        if (nc > 0 && (!costs->O || !costs->coeffs || !costs->powers))
+            return fail(QOC_ERR_INVALID, "%s: n_obs = %d with its observables, coefficients and powers (a null array)", who, nc);
+        for (int l = 0; l < nc; ++l) {
+            if (costs->powers[l] != 1 && costs->powers[l] != 2) return fail(QOC_ERR_INVALID, "%s: powers[%d] = %d (1 or 2)", who, l, costs->powers[l]);
+            if (!std::isfinite(costs->coeffs[l])) return fail(QOC_ERR_INVALID, "%s: coeffs[%d] is not finite", who, l);
+            const size_t per = 2 * (size_t)cfg->n * cfg->n;
+            for (size_t i = 0; i < per; ++i)
+                if (!std::isfinite(costs->O[per * l + i])) return fail(QOC_ERR_INVALID, "%s: observable %d is not finite", who, l);
+        }
+        if (nc == 0) costs = nullptr;
+    }
     // (F and E bound the table of rate scales: create_fleet and create_members check them, and create_members the table once they hold)
     const int F = fleet ? fleet->devices : 1, E = ens ? ens->members : 1;
-    const DecayHost dh{c, decay->C, c > 0 ? decay->rate_scales : nullptr, F, E, who};
+    DecayHost dh{c, decay->C, c > 0 ? decay->rate_scales : nullptr, F, E, who};
+    dh.costs = costs;
     Problem p{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr};
     p.decay = &dh;
     if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
@@ -1540,6 +1568,19 @@ int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const q
     const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
     const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
     return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out);
+}
+
+int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
+                          const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
+                          const double* one_minus_gauss, qoc_handle* out) {
+    return create_open_fleet("qoc_create_open_fleet", cfg, decay, nullptr, ens, fleet, tr, map, Hs, U0, V, W, maxA, one_minus_gauss, out);
+}
+
+// the same funnel with running costs on expectation values (csrc/qoc_lindblad.h): the COSTS instances of the backward sweep and of the reduction
+int qoc_create_open_costs(const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const qoc_ensemble* ens, const qoc_fleet* fleet,
+                          const qoc_transfer* tr, const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W,
+                          const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
+    return create_open_fleet("qoc_create_open_costs", cfg, decay, costs, ens, fleet, tr, map, Hs, U0, V, W, maxA, one_minus_gauss, out);
 }
 
 // sparse operators through the ensemble funnel: the sparse engine's own refusals, the operators and the row layout settled here, everything about
@@ -1910,6 +1951,22 @@ int qoc_get_populations(qoc_handle e, double* pop) {
     return QOC_OK;
 }
 
+int qoc_get_expectations(qoc_handle e, double* x) {
+    CHECK_H(e);
+    if (!e->lb.on || e->lb.nc < 1) return fail(QOC_ERR_STATE, "qoc_get_expectations: not an open engine with running costs (qoc_create_open_costs)");
+    if (!x) return fail(QOC_ERR_INVALID, "qoc_get_expectations: null output");
+    if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_expectations: nothing evaluated yet");
+    const QocDev& d = e->d;
+    const size_t row = (size_t)(d.steps + 1) * e->lb.nc * d.m, total = (size_t)d.B * row;
+    hipLaunchKernelGGL(k_lb_expectations, dim3((unsigned)((size_t)d.B * (d.steps + 1))), dim3(QOC_BLOCK), 0, e->stream, d, e->lb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->ens_E)                                                      // member 0 of each control set
+        HIP_TRY(hipMemcpy2D(x, row * sizeof(double), e->lb.expct, row * sizeof(double) * e->ens_E, row * sizeof(double), (size_t)e->g.B, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy(x, e->lb.expct, total * sizeof(double), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
 int qoc_get_member_scalars(qoc_handle e, double* loss, double* reg_state) {
     CHECK_H(e);
     if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_scalars: not an ensemble engine (qoc_create_ensemble)");
@@ -2026,6 +2083,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
 //   open engines (qoc_create_open, qoc_create_open_fleet): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
+//   (qoc_create_open_costs with n_obs > 0 ends the line with running_costs=<L>)
 //   sparse engines (qoc_create_sparse): path=sparse nnz=<stored entries> ell=<W_0,..,W_k> vector_home=<lds|global> lds=<bytes of dynamic LDS> threads=<256|1024 of a sweep>
 //   grad_grid=<workgroups of k_sp_grad>; engines of qoc_create_sparse_fleet add rows=<per_operator|merged> merged_width=<Wm, 0 per operator>
 // on every path gradient=<first_order|exact> (qoc_config.gradient), and tail=<finish256_regs|finish256_memory|finish1024_regs|finish1024_regs8|finish1024_memory|split<S>[_partials]|latency_fused_regs|latency_fused_memory|in_launch>
@@ -2084,6 +2142,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     add(" gradient=%s", e->xg.on ? "exact" : "first_order");
     // exact engines only: where k_exact_grad keeps its generator and vector blocks, its dynamic LDS and its grid (qoc_exact_plan)
     if (e->xg.on) add(" exact_variant=%s exact_lds=%zu exact_grid=%d", e->xg.lds ? "lds" : "global", e->xg.lds_bytes, e->xg.grid);
+    // open engines with running costs only (qoc_create_open_costs)
+    if (e->lb.on && e->lb.nc > 0) add(" running_costs=%d", e->lb.nc);
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }

@@ -30,6 +30,14 @@
 // device f has the collapse operators sqrt(s[f][e][j]) D_j, so two tables of F E rows stand where one drift stood: H0[row] = H0' - 1/2 sum_j s_j D_j^dagger D_j
 // (formed on the host) and rs[row][j] = sqrt(s_j), which lb_setup multiplies into D_j on its way into LDS.  Trajectory b reads row ((b / E) / Rs) E + b % E
 // (E members, Rs control sets per device: the member block of qoc_ensemble.h).  An engine of qoc_create_open has one row and no rs: nothing is scaled.
+//
+// Running costs (qoc_create_open_costs): nc observables O_l with coefficients a_l (already divided by steps) and powers p_l in {1, 2} put
+//     R = sum_l a_l sum_{tau = 0 .. steps} sum_{i < m} x_l,i(tau)^p_l / p_l,    x_l,i(tau) = Re sum_ac conj(O_l[a][c]) rho_ii(tau)[a][c]
+// into reg_state.  Only the COSTS instances of k_lb_backward and k_lb_reduce know of them: the workgroup of a diagonal pair (i, i) forms x_l,i(t+1) from
+// the operator it has just loaded (one block_sum per observable, O_l read from global memory: no LDS), adds a_l x^(p_l - 1) O_l to its own elements of
+// Lambda_ii(t+1) BEFORE the slice's contraction -- once per slice, not per sub-step -- and leaves its share of R in cost_partial[B][R]; k_lb_reduce<true>
+// adds the tau = 0 terms from Psi0 (value only: the start does not depend on the pulse) and the partials of the diagonal pairs in ascending pair order.
+// Off-diagonal pairs run what they always ran.  The instances without COSTS are the kernels of every engine that has no costs.
 #pragma once
 #include "qoc_common.h"
 
@@ -37,6 +45,7 @@
 #define QOC_LB_MAX_C 8
 #define QOC_LB_MAX_T 60             // 1 / j! table
 #define QOC_LB_MAX_S 12
+#define QOC_LB_MAX_COSTS 16
 #define QOC_LB_E 4                  // elements of an n x n operator per thread: 32 * 32 / QOC_BLOCK
 #define QOC_LB_LDS_LIMIT ((size_t)159 * 1024)     // of the 160 KiB per compute unit; the static part (reduction slots, 1 / j! table) stays below 1 KiB
 
@@ -51,6 +60,13 @@ struct QocLb {
     // the member axis, behind what a one-row engine reads
     const double* rs;               // [rows][c] sqrt(s_j), or null: every scale is 1 and D_j is copied as it is
     int E, Rs, rows;                // members per control set, control sets per device, rows of H0 and rs (F E; 1: qoc_create_open)
+    // running costs (qoc_create_open_costs), read by the COSTS instances only
+    int nc;                         // observables, 0 .. QOC_LB_MAX_COSTS
+    const cplx* cO;                 // [nc][n][n] row-major
+    const double* ca;               // [nc] a_l / steps
+    const int* cp;                  // [nc] 1 or 2
+    double* cost_partial;           // [B][R] a pair's share of R over tau = 1 .. steps (diagonal pairs only)
+    double* expct;                  // [B][steps+1][nc][m] x_l,i(tau) (formed on read-back)
 };
 
 static inline int qoc_lb_stride(int n) { return n | 1; }
@@ -226,7 +242,8 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_forward(QocDev d, QocLb L) {
     }
 }
 
-template <bool ROWS>
+// COSTS: the running costs of a diagonal pair -- sources on Lambda_ii(t+1) and the pair's share of R
+template <bool ROWS, bool COSTS = false>
 __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
     extern __shared__ __attribute__((aligned(16))) cplx lb_lds[];
     __shared__ double ifc[QOC_LB_MAX_T + 2];
@@ -249,11 +266,38 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
     const cplx* hist = L.hist + ((size_t)b * L.R + r) * d.steps * nn;
     double* part_out = L.partial + ((size_t)b * L.R + r) * d.k * d.steps;
     cplx* rho = s.tmp;
+    double cost = 0.0;
     for (int t = d.steps - 1; t >= 0; --t) {
 #pragma unroll
         for (int e = 0; e < QOC_LB_E; ++e)
             if (w.at[e] >= 0) rho[w.at[e]] = hist[(size_t)t * nn + threadIdx.x + e * QOC_BLOCK];
         __syncthreads();
+        if (COSTS && pi == pj) {
+            // x = Re <O_l, rho_ii(t+1)>; Lambda_ii(t+1) += a_l x^(p_l - 1) O_l on the thread's own elements (the contraction below reads only those)
+            for (int l = 0; l < L.nc; ++l) {
+                const cplx* O = L.cO + (size_t)l * nn;
+                double part = 0.0;
+#pragma unroll
+                for (int e = 0; e < QOC_LB_E; ++e) {
+                    if (w.at[e] < 0) continue;
+                    const cplx ov = O[threadIdx.x + e * QOC_BLOCK], rv = rho[w.at[e]];
+                    part += ov.x * rv.x + ov.y * rv.y;
+                }
+                const double x = block_sum(part, red);
+                const double a = L.ca[l];
+                const bool sq = L.cp[l] == 2;
+                const double f = sq ? a * x : a;
+                cost += sq ? 0.5 * (a * x * x) : a * x;
+#pragma unroll
+                for (int e = 0; e < QOC_LB_E; ++e) {
+                    if (w.at[e] < 0) continue;
+                    const cplx ov = O[threadIdx.x + e * QOC_BLOCK];         // (read again, from L2: four registers per element are dearer)
+                    cplx lam = s.X[w.at[e]];
+                    lam.x = fma(f, ov.x, lam.x); lam.y = fma(f, ov.y, lam.y);
+                    s.X[w.at[e]] = lam;
+                }
+            }
+        }
         // weight Re <Lambda(t+1), H_k' rho(t+1) + rho(t+1) H_k'^dagger>
         for (int kk = 0; kk < d.k; ++kk) {
             const cplx* Hk = d.Hs + (size_t)(kk + 1) * nn;
@@ -277,9 +321,12 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_backward(QocDev d, QocLb L) {
         lb_assemble(d, L, H0, b, t, inv_n, w, s.A);
         lb_slice<true>(n, S, L.c, d.T, N, inv_n, w, s.A, s.D, s.X, s.term, s.tmp, ifc);
     }
+    if (COSTS && pi == pj && threadIdx.x == 0) L.cost_partial[(size_t)b * L.R + r] = cost;
 }
 
 // d.dLdu = sum over the pairs, ascending; loss, unitary_scale, reg_state = 0 from the final operators
+// COSTS: reg_state = the tau = 0 terms of the running costs from Psi0 (l ascending, i ascending inside), then the diagonal pairs' partials, ascending
+template <bool COSTS = false>
 __global__ void __launch_bounds__(QOC_BLOCK) k_lb_reduce(QocDev d, QocLb L) {
     __shared__ double red[8];
     const int b = blockIdx.x;
@@ -304,10 +351,29 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_reduce(QocDev d, QocLb L) {
     }
     fid = block_sum(fid, red);
     tr = block_sum(tr, red);
+    double reg = 0.0;
+    if (COSTS) {
+        for (int l = 0; l < L.nc; ++l) {
+            const cplx* O = L.cO + (size_t)l * nn;
+            const double a = L.ca[l];
+            const bool sq = L.cp[l] == 2;
+            for (int i = 0; i < m; ++i) {
+                double part = 0.0;
+                for (int o = threadIdx.x; o < nn; o += QOC_BLOCK) {
+                    const int a_ = o / n, c = o - a_ * n;
+                    const cplx rv = cmul(d.Psi0[a_ * m + i], cconj(d.Psi0[c * m + i]));
+                    part += O[o].x * rv.x + O[o].y * rv.y;
+                }
+                const double x = block_sum(part, red);
+                reg += sq ? 0.5 * (a * x * x) : a * x;
+            }
+        }
+        for (int i = 0, r = 0; i < m; r += m - i, ++i) reg += L.cost_partial[(size_t)b * L.R + r];
+    }
     if (threadIdx.x == 0) {
         d.loss[b] = 1.0 - fid / ((double)m * (double)m);
         d.uscale[b] = tr / (double)m;
-        d.reg_state[b] = 0.0;
+        d.reg_state[b] = reg;
     }
 }
 
@@ -327,6 +393,28 @@ __global__ void __launch_bounds__(QOC_BLOCK) k_lb_populations(QocDev d, QocLb L)
     }
 }
 
+// read-back: expct[b][tau][l][i] = Re <O_l, rho_ii(tau)>, tau = 0 the start; one workgroup per (b, tau), the elements summed in a fixed order
+__global__ void __launch_bounds__(QOC_BLOCK) k_lb_expectations(QocDev d, QocLb L) {
+    __shared__ double red[8];
+    const int n = d.n, m = d.m, nn = n * n;
+    const int tau = blockIdx.x % (d.steps + 1);
+    const size_t b = blockIdx.x / (d.steps + 1);
+    for (int l = 0; l < L.nc; ++l) {
+        const cplx* O = L.cO + (size_t)l * nn;
+        for (int i = 0, r = 0; i < m; r += m - i, ++i) {          // r: the diagonal pair (i, i)
+            double part = 0.0;
+            for (int o = threadIdx.x; o < nn; o += QOC_BLOCK) {
+                cplx rv;
+                if (tau == 0) { const int a = o / n, c = o - a * n; rv = cmul(d.Psi0[a * m + i], cconj(d.Psi0[c * m + i])); }
+                else rv = L.hist[((b * L.R + r) * d.steps + (tau - 1)) * nn + o];
+                part += O[o].x * rv.x + O[o].y * rv.y;
+            }
+            const double x = block_sum(part, red);
+            if (threadIdx.x == 0) L.expct[((b * (d.steps + 1) + tau) * L.nc + l) * m + i] = x;
+        }
+    }
+}
+
 // whether the engine has member rows to pick and scale by (one row of scales counts: a single member whose rates are not the nominal ones)
 static inline bool qoc_lb_member_rows(const QocLb& L) { return L.rows > 1 || L.rs != nullptr; }
 // the three launches of an open engine's evaluation
@@ -335,15 +423,22 @@ static inline void qoc_lb_forward(const QocLb& L, const QocDev& d, hipStream_t s
     else hipLaunchKernelGGL(k_lb_forward<false>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
 }
 static inline void qoc_lb_backward(const QocLb& L, const QocDev& d, hipStream_t s) {
+    if (L.nc > 0) {                                           // running costs: the COSTS instances of the sweep and of the reduction
+        if (qoc_lb_member_rows(L)) hipLaunchKernelGGL((k_lb_backward<true, true>), dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+        else hipLaunchKernelGGL((k_lb_backward<false, true>), dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
+        hipLaunchKernelGGL(k_lb_reduce<true>, dim3((unsigned)d.B), dim3(QOC_BLOCK), 0, s, d, L);
+        return;
+    }
     if (qoc_lb_member_rows(L)) hipLaunchKernelGGL(k_lb_backward<true>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
     else hipLaunchKernelGGL(k_lb_backward<false>, dim3((unsigned)(d.B * L.R)), dim3(QOC_BLOCK), L.lds_bytes, s, d, L);
-    hipLaunchKernelGGL(k_lb_reduce, dim3((unsigned)d.B), dim3(QOC_BLOCK), 0, s, d, L);
+    hipLaunchKernelGGL(k_lb_reduce<false>, dim3((unsigned)d.B), dim3(QOC_BLOCK), 0, s, d, L);
 }
 // Above 64 KiB of dynamic LDS a kernel has to be opted in.  The attribute belongs to the kernel for the whole process, not to an engine, so it is
 // set to the size rule's limit -- never to this engine's own footprint, which would lower it under a larger open engine that is still alive.
 static inline hipError_t qoc_lb_lds_opt_in(const QocLb& L) {
     if (L.lds_bytes <= 64 * 1024) return hipSuccess;
-    const void* kernels[] = {(const void*)k_lb_forward<false>, (const void*)k_lb_backward<false>, (const void*)k_lb_forward<true>, (const void*)k_lb_backward<true>};
+    const void* kernels[] = {(const void*)k_lb_forward<false>, (const void*)k_lb_backward<false>, (const void*)k_lb_forward<true>, (const void*)k_lb_backward<true>,
+                             (const void*)k_lb_backward<false, true>, (const void*)k_lb_backward<true, true>};
     for (const void* f : kernels) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QOC_LB_LDS_LIMIT);
         if (e != hipSuccess) return e;

@@ -58,6 +58,10 @@ class QocDecay(C.Structure):
     _fields_ = [('n_collapse', C.c_int32), ('C', C.POINTER(C.c_double)), ('rate_scales', C.POINTER(C.c_double))]
 
 
+class QocRunningCosts(C.Structure):
+    _fields_ = [('n_obs', C.c_int32), ('O', C.POINTER(C.c_double)), ('coeffs', C.POINTER(C.c_double)), ('powers', C.POINTER(C.c_int32))]
+
+
 class QocSparse(C.Structure):
     _fields_ = [('indptr', C.POINTER(C.c_int64)), ('row', C.POINTER(C.c_int32)), ('col', C.POINTER(C.c_int32)), ('val', C.POINTER(C.c_double)),
                 ('vector_home', C.c_int32)]
@@ -96,6 +100,9 @@ _SIGNATURES = {
     'qoc_create_open_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocDecay), C.POINTER(QocEnsemble), C.POINTER(QocFleet), C.POINTER(QocTransfer),
                                         C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_get_member_final_density': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_create_open_costs': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocDecay), C.POINTER(QocRunningCosts), C.POINTER(QocEnsemble), C.POINTER(QocFleet),
+                                        C.POINTER(QocTransfer), C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_void_p)]),
+    'qoc_get_expectations': (C.c_int, [C.c_void_p, _DP]),
     'qoc_create_sparse': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), _DP, _DP, _DP, _DP, _IP, _DP, C.POINTER(C.c_void_p)]),
     'qoc_create_sparse_fleet': (C.c_int, [C.POINTER(QocConfig), C.POINTER(QocSparse), C.POINTER(QocSparsePlan), C.POINTER(QocEnsemble),
                                           C.POINTER(QocFleet), C.POINTER(QocTransfer), C.POINTER(QocControlMap), _DP, _DP, _DP, _DP, _IP, _DP,
@@ -473,12 +480,19 @@ class HipEngine(object):
     e of device f is then the open problem with the collapse operators sqrt(rate_scales[f, e, j]) C_j; self.open_system is True, get_final_density()
     and get_populations() give member 0 of each control set, member_final_density() every member, and everything an ensemble engine offers (risk,
     member read-backs, transfer, control_map, the loops) works as it does there.  Not together with the collapse_ops= keyword, exact_gradient,
-    sparse_ops or time sharding (ValueError, before the library is loaded)."""
+    sparse_ops or time sharding (ValueError, before the library is loaded).
+
+    running_costs (open-system running costs, include/qoc.h qoc_create_open_costs): a list of at most 16 records (O, coeff, power) as
+    helper_functions/open_system.py builds them (level_cost, subspace_cost, observable_cost, dressed_level_cost).  Every trajectory's state regulariser is
+    then sum_l (coeff_l / steps) sum_tau sum_i x_l,i(tau)^power_l / power_l over the expectation values x_l,i(tau) = Re Tr(O_l rho_ii(tau)), tau = 0 ..
+    steps; get_expectations() gives them, member_scalars()['reg_state'] every member's sum.  Needs an open engine -- collapse_ops= (an empty list is the
+    closed limit) or decay carried by ensemble or fleet -- and composes with whatever that engine composes with; on a closed engine: ValueError, before
+    the library is loaded (closed engines take reg_coeffs['forbidden_coeff_list'])."""
 
     def __init__(self, Hs, U0, V, W, maxA, dt, total_time, steps, taylor_terms, scaling, state_transfer=False,
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
-                 sparse_ops=None, vector_home=None, control_map=None, fleet=None, row_layout=None):
+                 sparse_ops=None, vector_home=None, control_map=None, fleet=None, row_layout=None, running_costs=None):
         sparse = None
         decay = None
         if sparse_ops is not None:
@@ -542,6 +556,12 @@ class HipEngine(object):
                     raise ValueError('HipEngine: collapse_ops (open-system GRAPE) does not combine with %s' % name)
             from quantum_optimal_control.helper_functions import open_system
             collapse_ops = open_system.validate(collapse_ops, np.shape(Hs)[1])
+        if running_costs is not None:
+            if collapse_ops is None and decay is None:
+                raise ValueError("HipEngine: running_costs need an open engine (collapse_ops=, or decay carried by ensemble or fleet); closed engines take "
+                                 "reg_coeffs['forbidden_coeff_list']")
+            from quantum_optimal_control.helper_functions import open_system
+            running_costs = open_system.validate_costs(running_costs, np.shape(Hs)[1])
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
@@ -618,6 +638,16 @@ class HipEngine(object):
             foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
             fl = QocFleet()
             fl.devices, fl.offsets, fl.amp_scales = famp.shape[0], (_dp(foff) if foff.shape[2] else None), _dp(famp)
+        rcs = None
+        self.n_costs = 0                              # running costs: L, the observables behind get_expectations()
+        if running_costs is not None:
+            L = len(running_costs)
+            cO = np.ascontiguousarray(np.array([r[0] for r in running_costs], dtype=np.complex128).reshape(L, n, n))
+            ca = np.ascontiguousarray(np.array([r[1] for r in running_costs], dtype=np.float64).reshape(L))
+            cp = np.ascontiguousarray(np.array([r[2] for r in running_costs], dtype=np.int32).reshape(L))
+            rcs = QocRunningCosts()
+            rcs.n_obs, rcs.O, rcs.coeffs, rcs.powers = L, (_dp(cO.view(np.float64)) if L else None), (_dp(ca) if L else None), (cp.ctypes.data_as(_IP) if L else None)
+            self.n_costs = L
         self.row_layout = None
         if sparse is not None and (ens is not None or fl is not None or tr is not None or cmap is not None or row_layout is not None):
             # sparse operators through the ensemble funnel (include/qoc.h, qoc_create_sparse_fleet); a plain sparse engine stays on qoc_create_sparse
@@ -642,8 +672,12 @@ class HipEngine(object):
                 raise ValueError('HipEngine: rate_scales with a device axis need a fleet')
             dc = QocDecay()
             dc.n_collapse, dc.C, dc.rate_scales = D.shape[0], (_dp(D.view(np.float64)) if D.shape[0] else None), (_dp(rates) if D.shape[0] else None)
-            _check(lib.qoc_create_open_fleet(C.byref(cfg), C.byref(dc), None if ens is None else C.byref(ens), None if fl is None else C.byref(fl),
-                                             None if tr is None else C.byref(tr), None if cmap is None else C.byref(cmap), *(args[:6] + args[-1:])))
+            glue = (None if ens is None else C.byref(ens), None if fl is None else C.byref(fl), None if tr is None else C.byref(tr),
+                    None if cmap is None else C.byref(cmap))
+            if rcs is not None:
+                _check(lib.qoc_create_open_costs(C.byref(cfg), C.byref(dc), C.byref(rcs), *(glue + args[:6] + args[-1:])))
+            else:
+                _check(lib.qoc_create_open_fleet(C.byref(cfg), C.byref(dc), *(glue + args[:6] + args[-1:])))
             if tr is not None:
                 self.samples = int(tr.n_samples)
             self.devices = 0 if fl is None else int(fl.devices)
@@ -663,6 +697,12 @@ class HipEngine(object):
             sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
             sp.val, sp.vector_home = _dp(val.view(np.float64)), VECTOR_HOME[vector_home]
             _check(lib.qoc_create_sparse(C.byref(cfg), C.byref(sp), *(args[2:8] + args[-1:])))
+        elif collapse_ops is not None and rcs is not None:
+            # the plain open problem with running costs: every glue pointer NULL (in the library an ensemble engine of one nominal member; self.members stays 0)
+            D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
+            dc = QocDecay()
+            dc.n_collapse, dc.C, dc.rate_scales = len(collapse_ops), (_dp(D.view(np.float64)) if len(collapse_ops) else None), None
+            _check(lib.qoc_create_open_costs(C.byref(cfg), C.byref(dc), C.byref(rcs), None, None, None, None, *(args[:6] + args[-1:])))
         elif collapse_ops is not None:
             # D_j = sqrt(dt) C_j; the state regularisers and Vs stay behind (the library refuses them by name)
             D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
@@ -825,10 +865,20 @@ class HipEngine(object):
         _check(self._lib.qoc_get_populations(self._h, _dp(out)))
         return out
 
+    def get_expectations(self):
+        """Open engines with running_costs: x_l,i(tau) = Re Tr(O_l rho_ii(tau)) of the last evaluation, (n_seeds, steps + 1, L, m); tau = 0 is the start
+        (member 0 of each control set)."""
+        out = np.empty((self.n_seeds, self.steps + 1, self.n_costs, self.m))
+        _check(self._lib.qoc_get_expectations(self._h, _dp(out)))
+        return out
+
     def member_scalars(self):
-        """Ensemble engines: dict(loss, reg_state) of the last evaluation, each [n_seeds][members]."""
-        loss = np.empty((self.n_seeds, self.members))
-        reg = np.empty((self.n_seeds, self.members))
+        """Ensemble engines: dict(loss, reg_state) of the last evaluation, each [n_seeds][members].  An engine of collapse_ops= with running_costs is, in
+        the library, an ensemble of one nominal member (qoc_create_open_costs with every glue pointer NULL): self.members stays 0, as on every engine
+        made without ensemble or fleet (the run summary of a robust call keys on it), and the arrays are [n_seeds][1] -- reg_state is each control set's
+        running cost R."""
+        loss = np.empty((self.n_seeds, max(self.members, 1)))      # (collapse_ops= with running_costs: one nominal member)
+        reg = np.empty((self.n_seeds, max(self.members, 1)))
         _check(self._lib.qoc_get_member_scalars(self._h, _dp(loss), _dp(reg)))
         return dict(loss=loss, reg_state=reg)
 

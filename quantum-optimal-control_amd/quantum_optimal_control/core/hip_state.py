@@ -12,7 +12,7 @@ from quantum_optimal_control.core import hip_engine
 class HipState(object):
 
     def __init__(self, sys_para, n_seeds=1, device=0, path=hip_engine.PATH_AUTO, chunks=0, first_seed=0, plan_seeds=0, time_comm=None, ensemble=None, transfer=None,
-                 exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, fleet_base=None):
+                 exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, fleet_base=None, running_costs=None):
         self.sys_para = sys_para
         self.n_seeds = n_seeds
         self.first_seed = first_seed      # global index of this engine's first restart (seed-sharded runs)
@@ -28,6 +28,7 @@ class HipState(object):
         self.control_map = control_map    # control map: the validated helper_functions.control_map.ControlMap, or None (sys_para.ops_c are then the r operators it feeds)
         self.fleet = fleet                # device fleet: the validated helper_functions.fleet.Fleet, or None; n_seeds is then F x restarts, device-major
         self.fleet_base = fleet_base      # ... and each device's own first start point (F, k, P), or None: sys_para.ops_weight_base for every device
+        self.running_costs = running_costs   # open-system running costs: the validated (O, coeff, power) records (helper_functions/open_system.py), or None
         self.engine = None
 
     def build_graph(self):
@@ -53,7 +54,8 @@ class HipState(object):
             n_seeds=self.n_seeds, device=self.device, path=self.path, chunks=self.chunks, plan_seeds=self.plan_seeds,
             time_shards=0 if self.time_comm is None else self.time_comm.world, time_rank=-1 if self.time_comm is None else self.time_comm.rank,
             time_comm=self.time_comm, ensemble=self.ensemble, transfer=self.transfer, exact_gradient=self.exact_gradient,
-            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops, control_map=self.control_map, fleet=self.fleet)
+            collapse_ops=self.collapse_ops, sparse_ops=sparse_ops, control_map=self.control_map, fleet=self.fleet,
+            running_costs=self.running_costs)
         base = np.asarray(sp.ops_weight_base, dtype=np.float64)
         if self.fleet is not None:
             # control set (f, r) starts where control set r of the same call without a fleet starts (or, r = 0, from device f's own point)

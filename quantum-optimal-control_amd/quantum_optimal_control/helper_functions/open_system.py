@@ -49,6 +49,71 @@ def dephasing(n, tphi):
     return math.sqrt(2.0 / float(tphi)) * (a.conj().T @ a)
 
 
+# ---- running costs: penalties on expectation values along the pulse (Grape(running_costs=...) / HipEngine(running_costs=...)) ------------------
+# A cost is one record (O, coeff, power): with x_i(tau) = Re Tr(O rho_ii(tau)) of every state of interest i at every slice boundary tau = 0 .. steps
+# it adds (coeff / steps) sum_tau sum_i x_i(tau)^power / power to the objective.
+
+MAX_COSTS = 16
+
+
+def observable_cost(O, coeff, power=2):
+    """A penalty on the expectation value of the Hermitian observable O (n x n)."""
+    return (np.array(O, dtype=np.complex128), float(coeff), int(power))
+
+
+def level_cost(n, level, coeff, power=2):
+    """A penalty on the population of one bare level: O = |level><level| (power 2: the closed engines' forbidden level)."""
+    return subspace_cost(n, [level], coeff, power)
+
+
+def subspace_cost(n, levels, coeff, power=2):
+    """A penalty on the population of a set of bare levels, e.g. everything outside the computational subspace: O = the projector on them."""
+    O = np.zeros((n, n), dtype=np.complex128)
+    for l in levels:
+        if not 0 <= int(l) < n:
+            raise ValueError('subspace_cost: level %r is outside 0 .. %d' % (l, n - 1))
+        O[int(l), int(l)] = 1.0
+    return observable_cost(O, coeff, power)
+
+
+def dressed_level_cost(v, coeff, power=2):
+    """A penalty on the population of the (dressed) state v: O = v v^dagger."""
+    v = np.asarray(v, dtype=np.complex128).reshape(-1)
+    return observable_cost(np.outer(v, np.conj(v)), coeff, power)
+
+
+def validate_costs(costs, n):
+    """The list as the engine takes it: records (O complex n x n, coeff, power).  ValueError on a wrong shape, an observable that is not Hermitian within
+    1e-12 max|O|, a coefficient that is not finite, a power other than 1 or 2, or more than 16 costs (an empty list is no cost)."""
+    if not isinstance(costs, (list, tuple)):
+        raise ValueError('running_costs: a list of (O, coeff, power) records is expected, got %s' % type(costs).__name__)
+    if len(costs) > MAX_COSTS:
+        raise ValueError('running_costs: %d costs, at most %d' % (len(costs), MAX_COSTS))
+    out = []
+    for j, rec in enumerate(costs):
+        if not isinstance(rec, (list, tuple)) or len(rec) != 3:
+            raise ValueError('running_costs[%d]: a record (O, coeff, power) is expected (open_system.level_cost and its kin build them)' % j)
+        O, coeff, power = rec
+        a = np.asarray(O)
+        if a.shape != (n, n):
+            raise ValueError('running_costs[%d]: the observable has shape %s, expected (%d, %d)' % (j, a.shape, n, n))
+        try:
+            a = np.ascontiguousarray(a.astype(np.complex128))
+            coeff = float(coeff)
+        except (TypeError, ValueError):
+            raise ValueError('running_costs[%d] is not numeric' % j)
+        if not np.all(np.isfinite(a)):
+            raise ValueError('running_costs[%d]: the observable is not finite' % j)
+        if np.max(np.abs(a - a.conj().T)) > 1e-12 * np.max(np.abs(a)):
+            raise ValueError('running_costs[%d]: the observable is not Hermitian' % j)
+        if not np.isfinite(coeff):
+            raise ValueError('running_costs[%d]: the coefficient is not finite' % j)
+        if isinstance(power, bool) or power not in (1, 2):
+            raise ValueError('running_costs[%d]: power = %r (1 or 2)' % (j, power))
+        out.append((a, coeff, int(power)))
+    return out
+
+
 def lindblad_bound(H0, Hops, maxA, collapse_ops, dt):
     """x = 2 dt (|H0|_2 + sum_k maxA_k |H_k|_2 + sum_j |C_j|_2^2) >= |dt L| for every admissible pulse."""
     x = np.linalg.norm(np.asarray(H0, dtype=np.complex128), 2)

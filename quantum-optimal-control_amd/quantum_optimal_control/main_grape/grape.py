@@ -87,7 +87,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
           dressed_info=None, maxA=None, use_gpu=True, sparse_H=True, sparse_U=False, sparse_K=False, draw=None,
           initial_guess=None, show_plots=True, unitary_error=1e-4, method='Adam', state_transfer=False,
           no_scaling=False, freq_unit='GHz', file_name=None, save=True, data_path=None, Taylor_terms=None,
-          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
+          use_inter_vecs=True, restarts=1, plan_seeds=None, time_comm=None, robust=None, *, transfer=None, exact_gradient=False, collapse_ops=None, control_map=None, fleet=None, running_costs=None, _first_seed=0, _device=0, _return_session=False, _restart_info=None):
     """Reference signature (main_grape/grape.py:19) plus one optional extension: ``restarts=B`` optimises B control sets at
     once on the GPU -- the first is the reference's own initial guess (same NumPy RNG draw / ``initial_guess``), the others
     are independent N(0, 1/sqrt(steps)) restarts -- and returns the (uks, U_final) of the best final fidelity.
@@ -161,7 +161,16 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     without decay.  Taylor order and sub-steps: the largest that open_system.choose_taylor gives any member, unless ``Taylor_terms=(T, s)``.  Methods:
     ``'Adam'``, ``'LBFGS'``, ``'EVOLVE'`` and, on a robust call, scipy's.  Works with ``transfer``, ``control_map`` and ``restarts``; not with the
     ``collapse_ops`` keyword itself, ``exact_gradient``, ``dressed_info``, forbidden-level / ``speed_up`` / ``forbid_dressed`` regularisers,
-    ``time_comm``, scipy.sparse Hamiltonians or the sharded entry points (ValueError, before the library is loaded)."""
+    ``time_comm``, scipy.sparse Hamiltonians or the sharded entry points (ValueError, before the library is loaded).
+
+    ``running_costs`` (open-system running costs): a list of at most 16 records from helper_functions.open_system -- ``level_cost(n, level, coeff)``,
+    ``subspace_cost(n, levels, coeff)``, ``observable_cost(O, coeff)``, ``dressed_level_cost(v, coeff)``, each with ``power=2`` (or 1).  With
+    x_i(tau) = Re Tr(O rho_ii(tau)) of every state of interest at every slice boundary tau = 0 .. steps, a record adds
+    (coeff / steps) sum_tau sum_i x_i(tau)^power / power to the objective (reg_loss; the stop rule keeps reading the loss): "keep the resonator empty",
+    "stay out of everything above the computational subspace", a truncation guard on the top level.  ``level_cost`` with power 2 is what
+    ``reg_coeffs['forbidden_coeff_list']`` is on a closed engine.  Needs an open engine: ``collapse_ops=`` (``[]`` is the closed limit), or a ``robust``
+    dict or a ``fleet`` that carries ``collapse_ops``; it then works with whatever that call works with.  Anything else: ValueError, before the library
+    is loaded.  The gradient of the term is first order in dt, as the engine's is."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     sparse = _is_sparse(H0, Hops)
@@ -253,6 +262,13 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                 raise ValueError('Grape: %s (open-system GRAPE) does not combine with %s' % (_who, name))
         if _first_seed != 0 or plan_seeds is not None:
             raise ValueError('Grape: %s (open-system GRAPE) does not run sharded (GrapeSharded)' % _who)
+    if running_costs is not None:
+        # running costs: an open engine's term, refused everywhere else before anything is built (and before the library is loaded)
+        from quantum_optimal_control.helper_functions import open_system as _open
+        if collapse_ops is None and decay_devices is None:
+            raise ValueError("Grape: running_costs need an open engine (collapse_ops=, or a robust dict or a fleet that carries collapse_ops); closed "
+                             "engines take reg_coeffs['forbidden_coeff_list']")
+        running_costs = _open.validate_costs(running_costs, len(H0))
     if transfer is not None:
         from quantum_optimal_control.helper_functions import transfer as _transfer
         if time_comm is not None:
@@ -307,6 +323,12 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
                 hf.add('collapse_ops', data=np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), len(H0), len(H0)))
+        if running_costs is not None:
+            from quantum_optimal_control.helper_functions.data_management import H5File
+            with H5File(file_path) as hf:
+                hf.add('running_cost_observables', data=np.array([r[0] for r in running_costs], dtype=np.complex128).reshape(len(running_costs), len(H0), len(H0)))
+                hf.add('running_cost_coeffs', data=np.array([r[1] for r in running_costs], dtype=np.float64))
+                hf.add('running_cost_powers', data=np.array([r[2] for r in running_costs], dtype=np.int32))
 
     if U0 is None and not sparse:
         U0 = np.identity(len(H0))
@@ -402,7 +424,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     tfs = HipState(sys_para, n_seeds=n_sets, device=_device if time_comm is None else time_comm.device, first_seed=_first_seed,
                    plan_seeds=0 if plan_seeds is None else int(plan_seeds), time_comm=time_comm, ensemble=robust if fleet is None else fleet.device(0),
                    transfer=None if transfer is None else transfer.matrix, exact_gradient=bool(exact_gradient),
-                   collapse_ops=collapse_ops, control_map=control_map, fleet=fleet, fleet_base=fleet_base)   # constants -> HBM
+                   collapse_ops=collapse_ops, control_map=control_map, fleet=fleet, fleet_base=fleet_base, running_costs=running_costs)   # constants -> HBM
     graph = tfs.build_graph()
     conv = Convergence(sys_para, time_unit, convergence)
     try:
@@ -418,6 +440,9 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if _restart_info is not None:
             # (a dict to fill: every control set's final scalars and variable, read before the engine goes -- examples/lbfgs_restarts.py)
             _restart_info.update(tfs.engine.scalars(), base=tfs.engine.get_base(), best=int(SS.seed))
+            if running_costs:
+                # (with running costs: x_l,i(tau) of every control set's last evaluation, (restarts, steps + 1, L, m) -- examples/guarded_transmon_under_decay.py)
+                _restart_info.update(expectations=tfs.engine.get_expectations())
         if save:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -481,6 +506,8 @@ def GrapeTimeSharded(*args, comm=None, **kwargs):
         raise ValueError("GrapeTimeSharded: method='LBFGS' is not supported; run Grape(method='LBFGS') on one GPU")
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeTimeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=...) on one GPU')
+    if kwargs.get('running_costs') is not None:
+        raise ValueError('GrapeTimeSharded: running_costs (open-system running costs) are not supported; run Grape(running_costs=...) on one GPU')
     if kwargs.get('control_map') is not None:
         raise ValueError('GrapeTimeSharded: control_map (control maps) is not supported; run Grape(control_map=...) on one GPU')
     if kwargs.get('fleet') is not None:
@@ -527,6 +554,8 @@ def GrapeSharded(*args, restarts=8, dist=None, comm=None, **kwargs):
         raise ValueError('GrapeSharded: transfer functions are not supported; run Grape(transfer=..., restarts=R) on one GPU')
     if kwargs.get('collapse_ops') is not None:
         raise ValueError('GrapeSharded: collapse_ops (open-system GRAPE) is not supported; run Grape(collapse_ops=..., restarts=R) on one GPU')
+    if kwargs.get('running_costs') is not None:
+        raise ValueError('GrapeSharded: running_costs (open-system running costs) are not supported; run Grape(running_costs=..., restarts=R) on one GPU')
     if kwargs.get('control_map') is not None:
         raise ValueError('GrapeSharded: control_map (control maps) is not supported; run Grape(control_map=..., restarts=R) on one GPU')
     if kwargs.get('fleet') is not None:
