@@ -630,6 +630,32 @@ static int enqueue_lbfgs_iteration(qoc_engine* e, const QocLbfgsDev& L) {
     return QOC_OK;
 }
 
+// the poll loop of qoc_run_adam and qoc_run_lbfgs (`who`): bursts of poll_every evaluations, the last one cut to the budget; after each the stream
+// is drained and the stop flags are read, until every control set has stopped (`what` names them in the failure message)
+template <typename F>
+static int run_until_done(qoc_engine* e, const char* who, const char* what, long long budget, int poll_every, int32_t* iterations_out,
+                          F&& enqueue_burst) {
+    const int poll = poll_every > 0 ? poll_every : 1;
+    const QocDev& sd = sets(e);
+    std::vector<int> done(sd.B);
+    long long launched = 0;
+    while (true) {
+        int burst = poll;
+        if (launched + burst > budget) burst = (int)(budget - launched);
+        TRY(enqueue_burst(burst));
+        launched += burst;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        TRY(small_check(e));
+        HIP_TRY(hipMemcpy(done.data(), sd.done, sd.B * sizeof(int), hipMemcpyDeviceToHost));
+        bool all = true;
+        for (int b = 0; b < sd.B; ++b) all = all && done[b];
+        if (all) break;
+        if (launched >= budget) return fail(QOC_ERR_STATE, "%s: %s not finished after %lld evaluations", who, what, launched);
+    }
+    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
 
 // the response matrix of qoc_create_shaped as the host prepared it: the transposed copy and the nonzero window of every row and column
 struct ShapeHost {
@@ -676,7 +702,7 @@ struct SparseHost {
 struct Problem {
     const double *Hs, *U0, *V, *W, *maxA, *one_minus_gauss; const int32_t* forbidden_states; const double *forbidden_coeffs, *Vs;
     const SparseHost* sparse;
-    const DecayHost* decay;          // an open engine through the ensemble funnel (qoc_create_open_fleet), else null
+    const DecayHost* decay;          // an open engine (qoc_create_open, qoc_create_open_fleet, qoc_create_open_costs), else null
 };
 
 static int check_create_args(const qoc_config* cfg, const Problem& p, qoc_handle* out) {
@@ -1181,8 +1207,8 @@ static int setup_sparse(qoc_engine* e, const SparseHost& h) {
     return QOC_OK;
 }
 
-static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out, const DecayHost* open = nullptr) {
-    if (!open) open = p.decay;
+static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs* ens, qoc_handle* out) {
+    const DecayHost* open = p.decay;
     TRY(check_create_args(cfg, p, out));
     HIP_TRY(hipSetDevice(cfg->device));
     // the half-built engine owns itself: every early return below destroys it (fail() has set the message by then)
@@ -1297,7 +1323,7 @@ int qoc_create_open(const qoc_config* cfg, const qoc_open* open, const double* H
     if (!cfg || !open || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "qoc_create_open: null argument");
     TRY(check_open("qoc_create_open", cfg, open->n_collapse, open->C));
     const DecayHost dh{open->n_collapse, open->C, nullptr, 1, 1, "qoc_create_open"};
-    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr}, nullptr, out, &dh);
+    return create_engine(cfg, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr, nullptr, &dh}, nullptr, out);
 }
 
 // what a sparse engine refuses about its configuration and its operators (K of them), on the host and before any device is touched; then COO ->
@@ -1341,121 +1367,8 @@ int qoc_create_sparse(const qoc_config* cfg, const qoc_sparse* ops, const double
     return create_engine(cfg, Problem{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh}, nullptr, out);
 }
 
-// qoc_create_ensemble, qoc_create_shaped and qoc_create_mapped (`who` names the caller in the messages; shape: the prepared response of a line,
-// else null; map: the checked control map of the last, else null -- the trajectories then run its r operators in place of the k pulses')
-// (fleet: the checked tables of qoc_create_fleet, read in place of ens' offsets and amp_scales)
-static int create_members(const char* who, const ShapeHost* shape, const qoc_config* cfg, const qoc_ensemble* ens, Problem p,
-                          qoc_handle* out, const qoc_control_map* map = nullptr, const qoc_fleet* fleet = nullptr) {
-    if (!cfg || !ens || (!p.Hs && !p.sparse) || !p.maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
-    const int E = ens->members, q = ens->n_perturb;
-    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
-    if ((!fleet && !ens->amp_scales) || !ens->weights || (q > 0 && ((!ens->P && !p.sparse) || (!fleet && !ens->offsets))))
-        return fail(QOC_ERR_INVALID, "%s: ensemble arrays missing", who);
-    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
-        return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
-    if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "%s: %d x %d trajectories", who, cfg->n_seeds, E);
-    if (cfg->has_envelope && !p.one_minus_gauss) return fail(QOC_ERR_INVALID, "%s: envelope constant missing", who);
-    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "%s: d2wdt2 needs dwdt (reference: NameError new_weights)", who);
-    for (int i = 0; i < E; ++i)
-        if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "%s: weight %d is %g", who, i, ens->weights[i]);
-    // (qoc_create_open_fleet: the members' rate scales, a row of c for each of the F E members just checked)
-    if (p.decay && p.decay->scales) {
-        const size_t c = (size_t)p.decay->c, rows = (size_t)(fleet ? fleet->devices : 1) * E;
-        for (size_t i = 0; i < rows * c; ++i) {
-            const double v = p.decay->scales[i];
-            if (!std::isfinite(v) || v < 0.0)
-                return fail(QOC_ERR_INVALID, "%s: rate_scales[%zu][%zu][%zu] is %g (finite, >= 0)", who, i / ((size_t)E * c), (i / c) % E, i % c, v);
-        }
-    }
-    // paths whose tail runs inside their own launch, or that form their controls from the variable, cannot host the member reduction
-    // (checked before any device is touched)
-    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an ensemble cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
-    if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "%s: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
-        "inside its launch, where the members' gradients cannot be reduced first", who);
-    if (!p.decay && cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
-        "%s: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail", who);
-    // (a control map: the trajectories run the r operators the map feeds)
-    const int kt = map ? map->n_terms : cfg->k;
-    if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && kt + q > 8) return fail(QOC_ERR_INVALID,
-        "%s: path %d is limited to 8 controls; the ensemble's trajectories have %s + q = %d", who, cfg->path, map ? "r" : "k", kt + q);
-    // the trajectories: G E of them, k + q controls (the perturbations are frozen control rows), no pulse regulariser (the group view has them)
-    qoc_config tc = *cfg;
-    const int n = cfg->n, k = cfg->k;
-    const size_t nn = (size_t)n * n;
-    tc.k = kt + q;
-    tc.n_seeds = cfg->n_seeds * E;
-    tc.plan_seeds = cfg->plan_seeds > 0 ? cfg->plan_seeds * E : 0;
-    tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
-    tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
-    // (sparse operators: the SparseHost carries the kt + q + 1 ELLPACK blocks already; no dense array is stacked)
-    std::vector<double> Hst(p.sparse ? 0 : 2 * nn * (size_t)(kt + q + 1));
-    if (!p.sparse) memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(kt + 1) * sizeof(double));
-    if (!p.sparse && q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(kt + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
-    // (no trajectory kernel of an ensemble forms controls from maxA: the rows of a mapped engine carry ones)
-    std::vector<double> maxAt(p.maxA, p.maxA + (map ? 0 : k));
-    maxAt.resize((size_t)(kt + q), 1.0);
-    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, shape, map, fleet};
-    p.Hs = p.sparse ? nullptr : Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
-    return create_engine(&tc, p, &ea, out);
-}
-
-int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
-                        const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    const Problem p{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs};
-    return create_members("qoc_create_ensemble", nullptr, cfg, ens, p, out);
-}
-
-// qoc_create_shaped and qoc_create_mapped (`who`): the response matrix prepared (tr may be null under a map: no line), one nominal member
-// where there is no ensemble, the checked control map handed on
-static int create_shaped(const char* who, const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map,
-                         const Problem& p, qoc_handle* out, const qoc_fleet* fleet = nullptr) {
-    if (!cfg || (!tr && !map) || !p.maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
-    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "%s: k, steps must be >= 1", who);
-    const int steps = cfg->steps, k = cfg->k;
-    // no ensemble: one nominal member
-    const std::vector<double> ones((size_t)k + 1, 1.0);
-    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    if (!tr) return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out, map, fleet);
-    const int P = tr->n_samples;
-    if (P < 1) return fail(QOC_ERR_INVALID, "%s: n_samples = %d (>= 1)", who, P);
-    if (!tr->T) return fail(QOC_ERR_INVALID, "%s: the response matrix is missing", who);
-    if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "%s: the envelope regulariser is defined per time slice, not per sample", who);
-    // the response: finite, every sample reaches the pulse; the nonzero window of every row and column and the transposed copy
-    ShapeHost sh{P, 0, 0, std::vector<double>((size_t)P * steps), std::vector<int2>((size_t)steps, make_int2(0, 0)),
-                 std::vector<int2>((size_t)P, make_int2(0, 0))};
-    for (int t = 0; t < steps; ++t)
-        for (int s = 0; s < P; ++s) {
-            const double v = tr->T[(size_t)t * P + s];
-            if (!std::isfinite(v)) return fail(QOC_ERR_INVALID, "%s: T[%d][%d] is not finite", who, t, s);
-            sh.Tt[(size_t)s * steps + t] = v;
-            if (v != 0.0) {
-                int2& r = sh.row_win[t];
-                int2& c = sh.col_win[s];
-                if (r.x == r.y) r.x = s;
-                r.y = s + 1;
-                if (c.x == c.y) c.x = t;
-                c.y = t + 1;
-            }
-        }
-    for (int s = 0; s < P; ++s) {
-        if (sh.col_win[s].x == sh.col_win[s].y) return fail(QOC_ERR_INVALID, "%s: column %d of T is zero (the sample never reaches the pulse)", who, s);
-        sh.col_band = std::max(sh.col_band, sh.col_win[s].y - sh.col_win[s].x);
-    }
-    for (int t = 0; t < steps; ++t) sh.band = std::max(sh.band, sh.row_win[t].y - sh.row_win[t].x);
-    return create_members(who, &sh, cfg, ens ? ens : &nominal, p, out, map, fleet);
-}
-
-int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
-                      const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
-                      const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    if (!tr) return fail(QOC_ERR_INVALID, "qoc_create_shaped: null argument");
-    return create_shaped("qoc_create_shaped", cfg, ens, tr, nullptr, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs},
-                         out);
-}
-
-// the map of qoc_create_mapped and qoc_create_fleet (`who`), checked on the host and before any device is touched: ranges, finite entries, every
-// pulse reaches an operator
+// the map of qoc_create_mapped and of every entry point that takes one (`who`), checked on the host and before any device is touched: ranges,
+// finite entries, every pulse reaches an operator
 static int check_map(const char* who, const qoc_config* cfg, const qoc_control_map* map, const double* maxA) {
     if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     if (!map) return fail(QOC_ERR_INVALID, "%s: the control map is missing", who);
@@ -1486,19 +1399,9 @@ static int check_map(const char* who, const qoc_config* cfg, const qoc_control_m
     return QOC_OK;
 }
 
-int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs,
-                      const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
-                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    const char* who = "qoc_create_mapped";
-    TRY(check_map(who, cfg, map, maxA));
-    return create_shaped(who, cfg, ens, tr, map, Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
-}
-
-// the fleet's own checks, on the host and before any device is touched; then the ensemble's entry point that transfer and map select, with the
-// fleet's tables in place of the ensemble's (ens: members, n_perturb, P and weights only; null: one member per device, no perturbation)
-static int create_fleet(const char* who, const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
-                        const qoc_control_map* map, const Problem& p, qoc_handle* out) {
-    const double* maxA = p.maxA;
+// the fleet's own checks (`who`), on the host and before any device is touched: its tables are read in place of the ensemble's offsets and
+// amp_scales, E members with q perturbations on each of its devices
+static int check_fleet(const char* who, const qoc_config* cfg, const qoc_fleet* fleet, const double* maxA, int E, int q) {
     if (!cfg || !maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     if (!fleet) return fail(QOC_ERR_INVALID, "%s: the fleet is missing", who);
     if (!fleet->amp_scales) return fail(QOC_ERR_INVALID, "%s: the fleet's amp_scales are missing", who);
@@ -1506,10 +1409,6 @@ static int create_fleet(const char* who, const qoc_config* cfg, const qoc_ensemb
     const int F = fleet->devices, k = cfg->k;
     if (F < 1) return fail(QOC_ERR_INVALID, "%s: devices = %d (>= 1)", who, F);
     if (cfg->n_seeds % F != 0) return fail(QOC_ERR_INVALID, "%s: n_seeds = %d is no multiple of devices = %d", who, cfg->n_seeds, F);
-    const std::vector<double> ones((size_t)k + 1, 1.0);
-    qoc_ensemble members{1, 0, nullptr, nullptr, nullptr, ones.data()};
-    if (ens) members = *ens;
-    const int E = members.members, q = members.n_perturb;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
     if (q > 0 && !fleet->offsets) return fail(QOC_ERR_INVALID, "%s: the fleet's offsets are missing (n_perturb = %d)", who, q);
     const size_t per_a = (size_t)E * k, per_d = (size_t)E * q;
@@ -1519,26 +1418,160 @@ static int create_fleet(const char* who, const qoc_config* cfg, const qoc_ensemb
     for (size_t i = 0; i < (size_t)F * per_d; ++i)
         if (!std::isfinite(fleet->offsets[i]))
             return fail(QOC_ERR_INVALID, "%s: offsets[%zu][%zu][%zu] is not finite", who, i / per_d, (i / q) % E, i % q);
-    // (the ensemble's own tables are not read on a fleet)
-    members.offsets = nullptr; members.amp_scales = nullptr;
-    if (map) TRY(check_map(who, cfg, map, maxA));
-    if (tr || map) return create_shaped(who, cfg, &members, tr, map, p, out, fleet);
-    return create_members(who, nullptr, cfg, &members, p, out, nullptr, fleet);
+    return QOC_OK;
+}
+
+// the response matrix of a line (`who`), checked on the host: finite, every sample reaches the pulse; then the nonzero window of every row and
+// column and the transposed copy
+static int build_shape(const char* who, const qoc_config* cfg, const qoc_transfer* tr, ShapeHost& sh) {
+    if (cfg->k < 1 || cfg->steps < 1) return fail(QOC_ERR_INVALID, "%s: k, steps must be >= 1", who);
+    const int steps = cfg->steps, P = tr->n_samples;
+    if (P < 1) return fail(QOC_ERR_INVALID, "%s: n_samples = %d (>= 1)", who, P);
+    if (!tr->T) return fail(QOC_ERR_INVALID, "%s: the response matrix is missing", who);
+    if (cfg->has_envelope) return fail(QOC_ERR_INVALID, "%s: the envelope regulariser is defined per time slice, not per sample", who);
+    sh = ShapeHost{P, 0, 0, std::vector<double>((size_t)P * steps), std::vector<int2>((size_t)steps, make_int2(0, 0)),
+                   std::vector<int2>((size_t)P, make_int2(0, 0))};
+    for (int t = 0; t < steps; ++t)
+        for (int s = 0; s < P; ++s) {
+            const double v = tr->T[(size_t)t * P + s];
+            if (!std::isfinite(v)) return fail(QOC_ERR_INVALID, "%s: T[%d][%d] is not finite", who, t, s);
+            sh.Tt[(size_t)s * steps + t] = v;
+            if (v != 0.0) {
+                int2& r = sh.row_win[t];
+                int2& c = sh.col_win[s];
+                if (r.x == r.y) r.x = s;
+                r.y = s + 1;
+                if (c.x == c.y) c.x = t;
+                c.y = t + 1;
+            }
+        }
+    for (int s = 0; s < P; ++s) {
+        if (sh.col_win[s].x == sh.col_win[s].y) return fail(QOC_ERR_INVALID, "%s: column %d of T is zero (the sample never reaches the pulse)", who, s);
+        sh.col_band = std::max(sh.col_band, sh.col_win[s].y - sh.col_win[s].x);
+    }
+    for (int t = 0; t < steps; ++t) sh.band = std::max(sh.band, sh.row_win[t].y - sh.row_win[t].x);
+    return QOC_OK;
+}
+
+// what an entry point composes its engine from, each null where it has none: the ensemble (null: one nominal member), the fleet's member tables,
+// the line's response matrix, the control map
+struct Glue { const qoc_ensemble* ens; const qoc_fleet* fleet; const qoc_transfer* tr; const qoc_control_map* map; };
+
+// The one way from every entry point but qoc_create to create_engine (`who` names the entry point in the messages).  An entry point has run its
+// own checks by now -- the glue it requires, check_open and the running costs, check_sparse and the row layout -- and filled p, decay and sparse
+// included.  What follows is checked in this order, on the host and before any device is touched, and the first defect names the refusal:
+//   1. cfg and maxA present                                                          "<who>: null argument"
+//   2. the fleet, when there is one (check_fleet): presence, amp_scales, k / n_seeds, devices, divisibility, members / n_perturb, offsets
+//      present, both tables finite
+//   3. the control map, when there is one (check_map)
+//   4. the response matrix, when there is one (build_shape): n_samples, T present, no envelope, finite, no zero column
+//   5. the members: Hs and out present, members / n_perturb, the ensemble's arrays, the sizes, weights, rate scales, what an ensemble cannot
+//      run on (time shards, QOC_PATH_SMALL, the latency mode, the 8-control paths); then the trajectory configuration
+//   6. create_engine (check_create_args speaks as qoc_create)
+static int create_composed(const char* who, const qoc_config* cfg, const Glue& g, Problem p, qoc_handle* out) {
+    if (!cfg || !p.maxA) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    // no ensemble: one nominal member; on a fleet the members' offsets and amp_scales are the fleet's and the ensemble's own are not read
+    const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
+    qoc_ensemble members = g.ens ? *g.ens : qoc_ensemble{1, 0, nullptr, nullptr, ones.data(), ones.data()};
+    const qoc_ensemble* ens = &members;
+    const qoc_fleet* fleet = g.fleet;
+    const qoc_control_map* map = g.map;
+    if (fleet) {
+        TRY(check_fleet(who, cfg, fleet, p.maxA, members.members, members.n_perturb));
+        members.offsets = nullptr; members.amp_scales = nullptr;
+    }
+    if (map) TRY(check_map(who, cfg, map, p.maxA));
+    ShapeHost shape;
+    if (g.tr) TRY(build_shape(who, cfg, g.tr, shape));
+    if ((!p.Hs && !p.sparse) || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
+    const int E = ens->members, q = ens->n_perturb;
+    if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
+    if ((!fleet && !ens->amp_scales) || !ens->weights || (q > 0 && ((!ens->P && !p.sparse) || (!fleet && !ens->offsets))))
+        return fail(QOC_ERR_INVALID, "%s: ensemble arrays missing", who);
+    if (cfg->n < 1 || cfg->k < 1 || cfg->steps < 1 || cfg->n_seeds < 1 || cfg->plan_seeds < 0)
+        return fail(QOC_ERR_INVALID, "%s: n, k, steps, n_seeds must be >= 1", who);
+    if ((long long)cfg->n_seeds * E > (1 << 24)) return fail(QOC_ERR_INVALID, "%s: %d x %d trajectories", who, cfg->n_seeds, E);
+    if (cfg->has_envelope && !p.one_minus_gauss) return fail(QOC_ERR_INVALID, "%s: envelope constant missing", who);
+    if (cfg->has_d2wdt2 && !cfg->has_dwdt) return fail(QOC_ERR_INVALID, "%s: d2wdt2 needs dwdt (reference: NameError new_weights)", who);
+    for (int i = 0; i < E; ++i)
+        if (!(ens->weights[i] >= 0.0)) return fail(QOC_ERR_INVALID, "%s: weight %d is %g", who, i, ens->weights[i]);
+    // (an open engine: the members' rate scales, a row of c for each of the F E members just checked)
+    if (p.decay && p.decay->scales) {
+        const size_t c = (size_t)p.decay->c, rows = (size_t)(fleet ? fleet->devices : 1) * E;
+        for (size_t i = 0; i < rows * c; ++i) {
+            const double v = p.decay->scales[i];
+            if (!std::isfinite(v) || v < 0.0)
+                return fail(QOC_ERR_INVALID, "%s: rate_scales[%zu][%zu][%zu] is %g (finite, >= 0)", who, i / ((size_t)E * c), (i / c) % E, i % c, v);
+        }
+    }
+    // paths whose tail runs inside their own launch, or that form their controls from the variable, cannot host the member reduction
+    if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an ensemble cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
+    if (cfg->path == QOC_PATH_SMALL) return fail(QOC_ERR_INVALID, "%s: the workgroup-resident path (QOC_PATH_SMALL) runs its tail "
+        "inside its launch, where the members' gradients cannot be reduced first", who);
+    if (!p.decay && cfg->variant == 5 && (cfg->path == QOC_PATH_AUTO || cfg->path == QOC_PATH_MFMA)) return fail(QOC_ERR_INVALID,
+        "%s: the latency mode of the MFMA path (variant 5) forms its controls from the variable and fuses its tail", who);
+    // (a control map: the trajectories run the r operators the map feeds)
+    const int kt = map ? map->n_terms : cfg->k;
+    if ((cfg->path == QOC_PATH_MFMA || cfg->path == QOC_PATH_ST_FUSED) && kt + q > 8) return fail(QOC_ERR_INVALID,
+        "%s: path %d is limited to 8 controls; the ensemble's trajectories have %s + q = %d", who, cfg->path, map ? "r" : "k", kt + q);
+    // the trajectories: G E of them, k + q controls (the perturbations are frozen control rows), no pulse regulariser (the group view has them)
+    qoc_config tc = *cfg;
+    const int n = cfg->n, k = cfg->k;
+    const size_t nn = (size_t)n * n;
+    tc.k = kt + q;
+    tc.n_seeds = cfg->n_seeds * E;
+    tc.plan_seeds = cfg->plan_seeds > 0 ? cfg->plan_seeds * E : 0;
+    tc.has_amplitude = tc.has_envelope = tc.has_dwdt = tc.has_d2wdt2 = tc.has_bandpass = 0;
+    tc.c_amplitude = tc.c_envelope = tc.c_dwdt = tc.c_d2wdt2 = tc.c_bandpass = 0.0;
+    // (sparse operators: the SparseHost carries the kt + q + 1 ELLPACK blocks already; no dense array is stacked)
+    std::vector<double> Hst(p.sparse ? 0 : 2 * nn * (size_t)(kt + q + 1));
+    if (!p.sparse) memcpy(Hst.data(), p.Hs, 2 * nn * (size_t)(kt + 1) * sizeof(double));
+    if (!p.sparse && q > 0) memcpy(Hst.data() + 2 * nn * (size_t)(kt + 1), ens->P, 2 * nn * (size_t)q * sizeof(double));
+    // (no trajectory kernel of an ensemble forms controls from maxA: the rows of a mapped engine carry ones)
+    std::vector<double> maxAt(p.maxA, p.maxA + (map ? 0 : k));
+    maxAt.resize((size_t)(kt + q), 1.0);
+    const EnsArgs ea{cfg, p.maxA, cfg->has_envelope ? p.one_minus_gauss : nullptr, ens, g.tr ? &shape : nullptr, map, fleet};
+    p.Hs = p.sparse ? nullptr : Hst.data(); p.maxA = maxAt.data(); p.one_minus_gauss = nullptr;
+    return create_engine(&tc, p, &ea, out);
+}
+
+int qoc_create_ensemble(const qoc_config* cfg, const qoc_ensemble* ens, const double* Hs, const double* U0, const double* V, const double* W,
+                        const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                        const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!ens) return fail(QOC_ERR_INVALID, "qoc_create_ensemble: null argument");
+    return create_composed("qoc_create_ensemble", cfg, Glue{ens, nullptr, nullptr, nullptr},
+                           Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
+}
+
+int qoc_create_shaped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const double* Hs, const double* U0, const double* V,
+                      const double* W, const double* maxA, const double* one_minus_gauss, const int32_t* forbidden_states,
+                      const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!tr) return fail(QOC_ERR_INVALID, "qoc_create_shaped: null argument");
+    return create_composed("qoc_create_shaped", cfg, Glue{ens, nullptr, tr, nullptr},
+                           Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
+}
+
+int qoc_create_mapped(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs,
+                      const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
+                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
+    if (!map) return check_map("qoc_create_mapped", cfg, map, maxA);           // (refused there: a null argument, or the map named as missing)
+    return create_composed("qoc_create_mapped", cfg, Glue{ens, nullptr, tr, map},
+                           Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
 }
 
 int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map,
                      const double* Hs, const double* U0, const double* V, const double* W, const double* maxA, const double* one_minus_gauss,
                      const int32_t* forbidden_states, const double* forbidden_coeffs, const double* Vs, qoc_handle* out) {
-    return create_fleet("qoc_create_fleet", cfg, ens, fleet, tr, map,
-                        Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
+    if (!fleet) return check_fleet("qoc_create_fleet", cfg, fleet, maxA, 1, 0);  // (refused there: a null argument, or the fleet named as missing)
+    return create_composed("qoc_create_fleet", cfg, Glue{ens, fleet, tr, map},
+                           Problem{Hs, U0, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, Vs}, out);
 }
 
-// an open engine through the ensemble funnel: the open engine's own refusals and the rate scales checked here, everything about the member tables,
-// the line and the map by the entry point that ens, fleet, transfer and map select -- all on the host and before any device is touched
-// (`costs`: the running costs of qoc_create_open_costs, checked here; null, or n_obs = 0: the engine of qoc_create_open_fleet)
-static int create_open_fleet(const char* who, const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const qoc_ensemble* ens,
-                             const qoc_fleet* fleet, const qoc_transfer* tr, const qoc_control_map* map, const double* Hs, const double* U0,
-                             const double* V, const double* W, const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
+// an open engine through the funnel (`who`: qoc_create_open_fleet or qoc_create_open_costs): the open engine's own refusals and the running costs
+// (null, or n_obs = 0: none) are checked here, the decay rides in Problem; the table of rate scales is checked with the members it has a row for
+static int create_open_composed(const char* who, const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const Glue& g,
+                                const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
+                                const double* one_minus_gauss, qoc_handle* out) {
     if (!cfg || !decay || !Hs || !V || !W || !maxA || !out) return fail(QOC_ERR_INVALID, "%s: null argument", who);
     const int c = decay->n_collapse;
     TRY(check_open(who, cfg, c, decay->C));
@@ -1556,36 +1589,27 @@ static int create_open_fleet(const char* who, const qoc_config* cfg, const qoc_d
         }
         if (nc == 0) costs = nullptr;
     }
-    // (F and E bound the table of rate scales: create_fleet and create_members check them, and create_members the table once they hold)
-    const int F = fleet ? fleet->devices : 1, E = ens ? ens->members : 1;
-    DecayHost dh{c, decay->C, c > 0 ? decay->rate_scales : nullptr, F, E, who};
+    // (F and E bound the table of rate scales: the funnel checks them, and the table once they hold)
+    DecayHost dh{c, decay->C, c > 0 ? decay->rate_scales : nullptr, g.fleet ? g.fleet->devices : 1, g.ens ? g.ens->members : 1, who};
     dh.costs = costs;
-    Problem p{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr};
-    p.decay = &dh;
-    if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
-    if (map) TRY(check_map(who, cfg, map, maxA));
-    if (tr || map) return create_shaped(who, cfg, ens, tr, map, p, out);
-    const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
-    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out);
+    return create_composed(who, cfg, g, Problem{Hs, U0, V, W, maxA, one_minus_gauss, nullptr, nullptr, nullptr, nullptr, &dh}, out);
 }
 
 int qoc_create_open_fleet(const qoc_config* cfg, const qoc_decay* decay, const qoc_ensemble* ens, const qoc_fleet* fleet, const qoc_transfer* tr,
                           const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W, const double* maxA,
                           const double* one_minus_gauss, qoc_handle* out) {
-    return create_open_fleet("qoc_create_open_fleet", cfg, decay, nullptr, ens, fleet, tr, map, Hs, U0, V, W, maxA, one_minus_gauss, out);
+    return create_open_composed("qoc_create_open_fleet", cfg, decay, nullptr, Glue{ens, fleet, tr, map}, Hs, U0, V, W, maxA, one_minus_gauss, out);
 }
 
-// the same funnel with running costs on expectation values (csrc/qoc_lindblad.h): the COSTS instances of the backward sweep and of the reduction
+// the same with running costs on expectation values (csrc/qoc_lindblad.h): the COSTS instances of the backward sweep and of the reduction
 int qoc_create_open_costs(const qoc_config* cfg, const qoc_decay* decay, const qoc_running_costs* costs, const qoc_ensemble* ens, const qoc_fleet* fleet,
                           const qoc_transfer* tr, const qoc_control_map* map, const double* Hs, const double* U0, const double* V, const double* W,
                           const double* maxA, const double* one_minus_gauss, qoc_handle* out) {
-    return create_open_fleet("qoc_create_open_costs", cfg, decay, costs, ens, fleet, tr, map, Hs, U0, V, W, maxA, one_minus_gauss, out);
+    return create_open_composed("qoc_create_open_costs", cfg, decay, costs, Glue{ens, fleet, tr, map}, Hs, U0, V, W, maxA, one_minus_gauss, out);
 }
 
-// sparse operators through the ensemble funnel: the sparse engine's own refusals, the operators and the row layout settled here, everything about
-// the member tables, the line and the map by the entry point that ens, fleet, transfer and map select -- all on the host and before any device is
-// touched.  The trajectories run kt + q operators; k_sp_grad forms gradients for the first kt
+// sparse operators through the funnel: the sparse engine's own refusals, the operators and the row layout are settled here.  The trajectories run
+// kt + q operators; k_sp_grad forms gradients for the first kt
 int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const qoc_sparse_plan* plan, const qoc_ensemble* ens, const qoc_fleet* fleet,
                             const qoc_transfer* tr, const qoc_control_map* map, const double* V, const double* W, const double* maxA,
                             const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out) {
@@ -1596,6 +1620,7 @@ int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const 
     if (ens && ens->P) return fail(QOC_ERR_INVALID, "%s: ens->P must be NULL (the perturbation operators are the last n_perturb of ops)", who);
     const int E = ens ? ens->members : 1, q = ens ? ens->n_perturb : 0;
     if (E < 1 || q < 0) return fail(QOC_ERR_INVALID, "%s: members = %d (>= 1), n_perturb = %d (>= 0)", who, E, q);
+    // (the number of operators comes from the map: checked here, ahead of the operators, and -- the check is pure -- once more in the funnel)
     if (map) TRY(check_map(who, cfg, map, maxA));
     const int kt = map ? map->n_terms : cfg->k;
     if (kt < 1 || (long long)kt + q + 1 > (1 << 20)) return fail(QOC_ERR_INVALID, "%s: %d + %d + 1 operators", who, kt, q);
@@ -1618,12 +1643,8 @@ int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const 
         std::string why;
         if (!qoc_ell_merge(cfg->n, sh.ops, sh.rows, why)) return fail(QOC_ERR_INVALID, "%s: the merged rows: %s", who, why.c_str());
     }
-    Problem p{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh};
-    if (fleet) return create_fleet(who, cfg, ens, fleet, tr, map, p, out);
-    if (tr || map) return create_shaped(who, cfg, ens, tr, map, p, out);
-    const std::vector<double> ones((size_t)std::max(cfg->k, 0) + 1, 1.0);
-    const qoc_ensemble nominal{1, 0, nullptr, nullptr, ones.data(), ones.data()};
-    return create_members(who, nullptr, cfg, ens ? ens : &nominal, p, out);
+    return create_composed(who, cfg, Glue{ens, fleet, tr, map},
+                           Problem{nullptr, nullptr, V, W, maxA, one_minus_gauss, forbidden_states, forbidden_coeffs, nullptr, &sh}, out);
 }
 
 int qoc_destroy(qoc_handle e) {
@@ -1748,28 +1769,12 @@ int qoc_run_adam(qoc_handle e, const qoc_adam_params* p, int32_t* iterations_out
     CHECK_H(e);
     if (!p) return fail(QOC_ERR_INVALID, "qoc_run_adam: null params");
     const QocAdamDev ap = loop_params(p);
-    const int poll = p->poll_every > 0 ? p->poll_every : 1;
-    const QocDev& sd = sets(e);
-    std::vector<int> done(sd.B);
     // at most max_iterations updates + the evaluation that trips the stop rule
-    const long long budget = (long long)p->max_iterations + 1;
-    long long launched = 0;
-    while (true) {
-        int burst = poll;
-        if (launched + burst > budget) burst = (int)(budget - launched);
-        if (e->path == QOC_PATH_SMALL) TRY(enqueue_small(e, ap, burst));
-        else for (int i = 0; i < burst; ++i) TRY(enqueue_iteration(e, ap));
-        launched += burst;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        TRY(small_check(e));
-        HIP_TRY(hipMemcpy(done.data(), sd.done, sd.B * sizeof(int), hipMemcpyDeviceToHost));
-        bool all = true;
-        for (int b = 0; b < sd.B; ++b) all = all && done[b];
-        if (all) break;
-        if (launched >= budget) return fail(QOC_ERR_STATE, "qoc_run_adam: seeds not finished after %lld evaluations", launched);
-    }
-    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return run_until_done(e, "qoc_run_adam", "seeds", (long long)p->max_iterations + 1, p->poll_every, iterations_out, [&](int burst) -> int {
+        if (e->path == QOC_PATH_SMALL) return enqueue_small(e, ap, burst);       // (one launch per burst)
+        for (int i = 0; i < burst; ++i) TRY(enqueue_iteration(e, ap));
+        return QOC_OK;
+    });
 }
 
 int qoc_iterate_lbfgs(qoc_handle e, const qoc_lbfgs_params* p, int32_t iters) {
@@ -1784,27 +1789,11 @@ int qoc_run_lbfgs(qoc_handle e, const qoc_lbfgs_params* p, int32_t* iterations_o
     CHECK_H(e);
     QocLbfgsDev L;
     TRY(lbfgs_prepare(e, p, "qoc_run_lbfgs", &L));
-    const int poll = p->poll_every > 0 ? p->poll_every : 1;
-    const QocDev& sd = sets(e);
-    std::vector<int> done(sd.B);
     // at most max_iterations evaluations that move the variable, one whose trial is refused at the limit, one of the accepted point restored
-    const long long budget = (long long)p->max_iterations + 2;
-    long long launched = 0;
-    while (true) {
-        int burst = poll;
-        if (launched + burst > budget) burst = (int)(budget - launched);
+    return run_until_done(e, "qoc_run_lbfgs", "control sets", (long long)p->max_iterations + 2, p->poll_every, iterations_out, [&](int burst) -> int {
         for (int i = 0; i < burst; ++i) TRY(enqueue_lbfgs_iteration(e, L));
-        launched += burst;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        TRY(small_check(e));
-        HIP_TRY(hipMemcpy(done.data(), sd.done, sd.B * sizeof(int), hipMemcpyDeviceToHost));
-        bool all = true;
-        for (int b = 0; b < sd.B; ++b) all = all && done[b];
-        if (all) break;
-        if (launched >= budget) return fail(QOC_ERR_STATE, "qoc_run_lbfgs: control sets not finished after %lld evaluations", launched);
-    }
-    if (iterations_out) HIP_TRY(hipMemcpy(iterations_out, sd.iters, sd.B * sizeof(int), hipMemcpyDeviceToHost));
-    return QOC_OK;
+        return QOC_OK;
+    });
 }
 
 int qoc_get_uks(qoc_handle e, double* uks) {
@@ -1848,6 +1837,14 @@ int qoc_get_pulse(qoc_handle e, double* u) {
     return QOC_OK;
 }
 
+// a per-trajectory array read back per control set: the first `bytes` of every trajectory's `stride` bytes, of every trajectory on a plain engine
+// (bytes = stride there) and of member 0 of each control set on an ensemble engine
+static int copy_out_sets(const qoc_engine* e, void* dst, const void* src, size_t bytes, size_t stride) {
+    if (e->ens_E) HIP_TRY(hipMemcpy2D(dst, bytes, src, stride * e->ens_E, bytes, (size_t)e->g.B, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy(dst, src, (size_t)e->d.B * bytes, hipMemcpyDeviceToHost));
+    return QOC_OK;
+}
+
 int qoc_get_coefficients(qoc_handle e, double* c) {
     CHECK_H(e);
     if (!e->mapped) return fail(QOC_ERR_STATE, "qoc_get_coefficients: not a mapped engine (qoc_create_mapped)");
@@ -1855,9 +1852,7 @@ int qoc_get_coefficients(qoc_handle e, double* c) {
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_coefficients: nothing evaluated yet");
     // (the first r rows of member 0's trajectory: what k_map_expand wrote for the last evaluation)
     HIP_TRY(hipStreamSynchronize(e->stream));
-    const size_t row = (size_t)e->cm.r * e->d.steps * sizeof(double), pitch = (size_t)e->ens_E * e->d.k * e->d.steps * sizeof(double);
-    HIP_TRY(hipMemcpy2D(c, row, e->d.u, pitch, row, (size_t)e->g.B, hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return copy_out_sets(e, c, e->d.u, (size_t)e->cm.r * e->d.steps * sizeof(double), (size_t)e->d.k * e->d.steps * sizeof(double));
 }
 
 int qoc_get_final_unitary(qoc_handle e, double* Uf) {
@@ -1868,9 +1863,7 @@ int qoc_get_final_unitary(qoc_handle e, double* Uf) {
     TRY(refresh_final(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const size_t row = (size_t)e->d.n * e->d.n * sizeof(cplx);
-    if (e->ens_E) HIP_TRY(hipMemcpy2D(Uf, row, e->d.Xfinal, row * e->ens_E, row, (size_t)e->g.B, hipMemcpyDeviceToHost));   // member 0 of each group
-    else HIP_TRY(hipMemcpy(Uf, e->d.Xfinal, (size_t)e->d.B * row, hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return copy_out_sets(e, Uf, e->d.Xfinal, row, row);
 }
 
 int qoc_get_inter_vecs(qoc_handle e, double* inter) {
@@ -1887,9 +1880,7 @@ int qoc_get_inter_vecs(qoc_handle e, double* inter) {
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     const size_t row = (size_t)(e->d.steps + 1) * e->d.n * e->d.m * sizeof(cplx);
-    if (e->ens_E) HIP_TRY(hipMemcpy2D(inter, row, e->d.inter, row * e->ens_E, row, (size_t)e->g.B, hipMemcpyDeviceToHost));   // member 0 of each group
-    else HIP_TRY(hipMemcpy(inter, e->d.inter, (size_t)e->d.B * row, hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return copy_out_sets(e, inter, e->d.inter, row, row);
 }
 
 // rho_ij(T) of trajectory b, [m][m][n][n] complex: the pairs i > j mirrored from rho_ji
@@ -1945,10 +1936,7 @@ int qoc_get_populations(qoc_handle e, double* pop) {
     hipLaunchKernelGGL(k_lb_populations, dim3(grid_for(total, QOC_BLOCK, 2048)), dim3(QOC_BLOCK), 0, e->stream, d, e->lb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->ens_E)                                                      // member 0 of each control set
-        HIP_TRY(hipMemcpy2D(pop, row * sizeof(double), e->lb.pop, row * sizeof(double) * e->ens_E, row * sizeof(double), (size_t)e->g.B, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipMemcpy(pop, e->lb.pop, total * sizeof(double), hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return copy_out_sets(e, pop, e->lb.pop, row * sizeof(double), row * sizeof(double));
 }
 
 int qoc_get_expectations(qoc_handle e, double* x) {
@@ -1957,14 +1945,11 @@ int qoc_get_expectations(qoc_handle e, double* x) {
     if (!x) return fail(QOC_ERR_INVALID, "qoc_get_expectations: null output");
     if (!e->evaluated) return fail(QOC_ERR_STATE, "qoc_get_expectations: nothing evaluated yet");
     const QocDev& d = e->d;
-    const size_t row = (size_t)(d.steps + 1) * e->lb.nc * d.m, total = (size_t)d.B * row;
+    const size_t row = (size_t)(d.steps + 1) * e->lb.nc * d.m;
     hipLaunchKernelGGL(k_lb_expectations, dim3((unsigned)((size_t)d.B * (d.steps + 1))), dim3(QOC_BLOCK), 0, e->stream, d, e->lb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->ens_E)                                                      // member 0 of each control set
-        HIP_TRY(hipMemcpy2D(x, row * sizeof(double), e->lb.expct, row * sizeof(double) * e->ens_E, row * sizeof(double), (size_t)e->g.B, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipMemcpy(x, e->lb.expct, total * sizeof(double), hipMemcpyDeviceToHost));
-    return QOC_OK;
+    return copy_out_sets(e, x, e->lb.expct, row * sizeof(double), row * sizeof(double));
 }
 
 int qoc_get_member_scalars(qoc_handle e, double* loss, double* reg_state) {

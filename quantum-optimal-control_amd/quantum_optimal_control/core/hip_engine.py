@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from quantum_optimal_control.helper_functions import control_map as _cmap, open_system
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('QOC_HIP_LIBRARY') or os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libqoc_hip.so'))   # override: A/B builds
 
@@ -329,6 +331,11 @@ class QocComm(object):
         _check(self._lib.qoc_comm_barrier(self._h))
 
 
+def _getter(holder):
+    """key -> value or None, whatever carries the keys: a dict, an object with attributes (helper_functions.fleet.Fleet) or None."""
+    return holder.get if isinstance(holder, dict) else lambda key, default=None: getattr(holder, key, default)
+
+
 def ensemble_arrays(ensemble, n, k, dt, dense=True):
     """The C ABI's qoc_ensemble arrays from a dict with keys `operators` (q Hermitian n x n matrices P_q), `offsets` (E x q), `amp_scales`
     (E x k) and `weights` (E, used as given): (P = -i dt P_q stacked, offsets, amp_scales, weights), all C-contiguous.  dense=False (the sparse
@@ -351,7 +358,7 @@ def ensemble_arrays(ensemble, n, k, dt, dense=True):
 def fleet_arrays(fleet, E, q, k):
     """The C ABI's qoc_fleet arrays from a helper_functions.fleet.Fleet or a dict with keys `offsets` (F x E x q, optional when q = 0) and
     `amp_scales` (F x E x k): (offsets, amp_scales), both C-contiguous."""
-    get = fleet.get if isinstance(fleet, dict) else lambda key, default=None: getattr(fleet, key, default)
+    get = _getter(fleet)
     amp = np.ascontiguousarray(np.asarray(get('amp_scales'), dtype=np.float64))
     if amp.ndim != 3 or amp.shape[1:] != (E, k):
         raise ValueError('HipEngine: fleet amp_scales have shape %s, expected (F, %d, %d)' % (amp.shape, E, k))
@@ -367,8 +374,7 @@ def decay_arrays(ensemble, fleet, n, E, dt):
     """The decay an ensemble dict (keys collapse_ops, rate_scales (E, c)) or a fleet (attributes or keys collapse_ops, rate_scales (F, E, c)) carries,
     as the C ABI's qoc_decay arrays: (D = sqrt(dt) C_j stacked (c, n, n), rate_scales (F, E, c) with F = 1 for an ensemble), or None without decay.
     The fleet's decay stands in front of the ensemble's (Grape hands device 0 of a fleet over as its ensemble)."""
-    from quantum_optimal_control.helper_functions import open_system
-    get = (lambda key: None) if fleet is None else (fleet.get if isinstance(fleet, dict) else lambda key: getattr(fleet, key, None))
+    get = _getter(fleet)
     ops, rates, lead = get('collapse_ops'), get('rate_scales'), 'fleet'
     if ops is None:
         if get('rate_scales') is not None:
@@ -429,8 +435,126 @@ def sparse_arrays(sparse_ops):
     return n, indptr, row, col, val
 
 
+# what a refusal asks of HipEngine's arguments `a`, when its block is reached (a key that is not here: that argument is not None)
+_GIVEN = {
+    'member collapse_ops': lambda a: _getter(a['ensemble'])('collapse_ops') is not None or _getter(a['fleet'])('collapse_ops') is not None,
+    'member rate_scales': lambda a: _getter(a['ensemble'])('rate_scales') is not None or _getter(a['fleet'])('rate_scales') is not None,
+    'exact_gradient': lambda a: bool(a['exact_gradient']),
+    'time sharding': lambda a: a['time_comm'] is not None or int(a['time_shards']) > 0,
+    'sparse_ops beside Hs': lambda a: a['sparse_ops'] is not None and a['Hs'] is not None,
+    'another path': lambda a: int(a['path']) not in (PATH_AUTO, PATH_SPARSE),
+}
+_NOT_ON_GLUE = (('collapse_ops', 'collapse_ops (open-system GRAPE)'), ('sparse_ops beside Hs', 'sparse_ops (sparse state transfer) beside a dense Hs'),
+                ('time sharding', 'time sharding'))
+# What does not combine with what: block -> (the feature as the message names it, ((what is asked, the partner as the message names it), ...)).
+# HipEngine looks at the blocks in this order, each when its feature is there, and at the partners in theirs; the first one given is the ValueError
+# 'HipEngine: <feature> does not combine with <partner>', before the library is loaded.  (Between the blocks stand the checks with messages of
+# their own: row_layout without sparse_ops, the validators of the helper modules, running_costs on a closed engine.)
+_REFUSALS = {
+    # (decay per member needs the open engine, which the sparse route does not have: named before anything is built)
+    'sparse_ops with decay': ('sparse_ops (sparse state transfer)', (('member collapse_ops', 'decay per member (collapse_ops)'),
+                                                                     ('member rate_scales', 'decay per member (rate_scales)'))),
+    # (before the fleet's own refusal of collapse_ops=: decay that the members carry is named as such)
+    'decay': ('an ensemble or fleet with decay', (('collapse_ops', 'the collapse_ops= keyword (the members carry the decay)'),
+                                                  ('exact_gradient', 'exact_gradient'), ('time sharding', 'time sharding'))),
+    'fleet': ('fleet', _NOT_ON_GLUE),
+    'control_map': ('control_map', _NOT_ON_GLUE),
+    # (transfer: the line runs on sparse operators behind the C ABI, qoc_create_sparse_fleet; this binding keeps its refusal)
+    'sparse_ops': ('sparse_ops (sparse state transfer)', (('transfer', 'transfer'), ('exact_gradient', 'exact_gradient'), ('collapse_ops', 'collapse_ops'),
+                                                          ('time sharding', 'time sharding'), ('Vs', 'Vs (dressed forbidden levels)'), ('Hs', 'a dense Hs'),
+                                                          ('U0', 'U0'), ('another path', 'path %(path)s'))),
+    'collapse_ops': ('collapse_ops (open-system GRAPE)', (('ensemble', 'ensemble'), ('transfer', 'transfer'), ('exact_gradient', 'exact_gradient'),
+                                                          ('time sharding', 'time sharding'))),
+}
+
+
+def _refuse(block, a):
+    """ValueError for the first partner of `block` (_REFUSALS) that HipEngine's arguments `a` hold."""
+    feature, partners = _REFUSALS[block]
+    for asked, partner in partners:
+        if _GIVEN[asked](a) if asked in _GIVEN else a[asked] is not None:
+            raise ValueError('HipEngine: %s does not combine with %s' % (feature, partner % a))
+
+
+# One builder per struct of the C ABI: (the struct, the arrays it points into -- to be kept alive across the call).
+def _ensemble_struct(ensemble, n, k, dt, dense):
+    P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt, dense=dense)
+    return QocEnsemble(members=amp.shape[0], n_perturb=off.shape[1], P=_dp(P.view(np.float64)) if (P is not None and P.shape[0]) else None,
+                       offsets=_dp(off) if off.shape[1] else None, amp_scales=_dp(amp), weights=_dp(wt)), (P, off, amp, wt)
+
+
+def _transfer_struct(transfer, steps):
+    T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
+    if T.ndim != 2 or T.shape[0] != steps:
+        raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, steps))
+    return QocTransfer(n_samples=T.shape[1], T=_dp(T)), T
+
+
+def _map_struct(cm):
+    return QocControlMap(n_terms=cm.n_terms, degree=cm.degree, poly=_dp(cm.alpha), mix=_dp(cm.mix), fixed=_dp(cm.fixed)), cm
+
+
+def _fleet_struct(fleet, ens, k):
+    foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
+    return QocFleet(devices=famp.shape[0], offsets=_dp(foff) if foff.shape[2] else None, amp_scales=_dp(famp)), (foff, famp)
+
+
+def _costs_struct(running_costs, n):
+    L = len(running_costs)
+    cO = np.ascontiguousarray(np.array([r[0] for r in running_costs], dtype=np.complex128).reshape(L, n, n))
+    ca = np.ascontiguousarray(np.array([r[1] for r in running_costs], dtype=np.float64).reshape(L))
+    cp = np.ascontiguousarray(np.array([r[2] for r in running_costs], dtype=np.int32).reshape(L))
+    return QocRunningCosts(n_obs=L, O=_dp(cO.view(np.float64)) if L else None, coeffs=_dp(ca) if L else None,
+                           powers=cp.ctypes.data_as(_IP) if L else None), (cO, ca, cp)
+
+
+def _sparse_structs(sparse, vector_home, row_layout):
+    """(qoc_sparse, qoc_sparse_plan): the plan of the sparse ensemble entry point (row_layout None: 0, as on that entry point without the keyword)."""
+    _, indptr, row, col, val = sparse
+    sp = QocSparse(indptr=indptr.ctypes.data_as(C.POINTER(C.c_int64)), row=row.ctypes.data_as(_IP), col=col.ctypes.data_as(_IP),
+                   val=_dp(val.view(np.float64)), vector_home=VECTOR_HOME[vector_home])
+    return (sp, QocSparsePlan(row_layout=ROW_LAYOUT[0 if row_layout is None else row_layout])), sparse
+
+
+def _decay_struct(D, rates=None, fl=None, kind=QocDecay):
+    """qoc_decay from D_j = sqrt(dt) C_j and the members' table of rate scales (None, the collapse_ops= keyword: no table; kind=QocOpen: qoc_open)."""
+    if rates is not None and fl is not None and rates.shape[0] != fl.devices:
+        raise ValueError('HipEngine: rate_scales are for %d devices, the fleet has %d' % (rates.shape[0], fl.devices))
+    if rates is not None and fl is None and rates.shape[0] != 1:
+        raise ValueError('HipEngine: rate_scales with a device axis need a fleet')
+    dc = kind(n_collapse=D.shape[0], C=_dp(D.view(np.float64)) if D.shape[0] else None)
+    if rates is not None:
+        dc.rate_scales = _dp(rates) if D.shape[0] else None
+    return dc, (D, rates)
+
+
+def _entry_point(cfg, args, s, row_layout_given):
+    """The creation symbol of include/qoc.h that serves the structs `s` (a dict: ensemble, fleet, transfer, control_map, decay -- carried by the
+    members --, open -- the collapse_ops= keyword --, costs, sparse, plan; None where there is none), and its arguments."""
+    ref = lambda x: None if x is None else C.byref(x)
+    glue = ens, fl, tr, cmap = tuple(ref(s[name]) for name in ('ensemble', 'fleet', 'transfer', 'control_map'))
+    dc, op, costs, sp, pl = (ref(s[name]) for name in ('decay', 'open', 'costs', 'sparse', 'plan'))
+    lean, lean_sparse = args[:6] + args[-1:], args[2:8] + args[-1:]     # (no forbidden lists or Vs on an open engine; no Hs, U0 or Vs on a sparse one)
+    composed = row_layout_given or any(g is not None for g in glue)    # (a plain sparse engine stays on qoc_create_sparse)
+    table = (   # (what is there, the symbol, its arguments): the first row whose condition holds
+        (sp and composed, 'qoc_create_sparse_fleet', (cfg, sp, pl) + glue + lean_sparse),
+        (dc and costs, 'qoc_create_open_costs', (cfg, dc, costs) + glue + lean),
+        (dc, 'qoc_create_open_fleet', (cfg, dc) + glue + lean),
+        (fl, 'qoc_create_fleet', (cfg,) + glue + args),
+        (cmap, 'qoc_create_mapped', (cfg, ens, tr, cmap) + args),
+        (sp, 'qoc_create_sparse', (cfg, sp) + lean_sparse),
+        # (the plain open problem with running costs: every glue pointer NULL -- in the library an ensemble engine of one nominal member)
+        (op and costs, 'qoc_create_open_costs', (cfg, op, costs, None, None, None, None) + lean),
+        (op, 'qoc_create_open', (cfg, op) + lean),       # (the state regularisers and Vs stay behind: the library refuses them by name)
+        (tr, 'qoc_create_shaped', (cfg, ens, tr) + args),
+        (ens, 'qoc_create_ensemble', (cfg, ens) + args),
+        (True, 'qoc_create', (cfg,) + args))
+    return next((symbol, call) for given, symbol, call in table if given)
+
+
 class HipEngine(object):
-    """Device-resident GRAPE problem: constants in HBM, n_seeds control sets, one HIP stream.
+    """Device-resident GRAPE problem: constants in HBM, n_seeds control sets, one HIP stream.  What does not combine with what is the table
+    _REFUSALS above: a ValueError before the library is loaded.
 
     ensemble (robust GRAPE, include/qoc.h qoc_create_ensemble): a dict with keys `operators`, `offsets`, `amp_scales`, `weights` (see
     ensemble_arrays); every control set is then optimised for the weighted objective over the members, and the read-backs keep their
@@ -449,38 +573,34 @@ class HipEngine(object):
     rates (helper_functions/open_system.py builds the usual ones; an empty list is the closed limit).  The engine then propagates the operators
     psi_i psi_j^dagger of the states of interest under the Lindblad master equation, with degree taylor_terms and 2^scaling sub-steps per slice in
     both modes; loss, gradient and the optimiser entry points keep their shapes, get_final_density() and get_populations() take the place of
-    get_final_unitary() and get_inter_vecs().  Combines with none of ensemble, transfer, exact_gradient or time sharding (ValueError).
+    get_final_unitary() and get_inter_vecs().
 
     sparse_ops (sparse state transfer, include/qoc.h qoc_create_sparse): a list of k + 1 scipy.sparse matrices -i dt H0, -i dt H_1 .. in place of Hs
-    (pass Hs=None, U0=None).  State transfer only; the engine keeps every operator in ELLPACK and never forms an n x n array, so n = 2^14 and more
-    fit.  vector_home: None / 'auto', 'lds' or 'global' (where the Taylor chain's two vectors live; A/B runs and tests).  Every other entry point
-    works as on a dense state-transfer engine.  Combines with none of transfer, exact_gradient, collapse_ops, Vs or time sharding, and only with path
-    AUTO or PATH_SPARSE (ValueError, before the library is loaded).
+    (pass Hs=None, U0=None).  State transfer only, on path AUTO or PATH_SPARSE; the engine keeps every operator in ELLPACK and never forms an n x n
+    array, so n = 2^14 and more fit.  vector_home: None / 'auto', 'lds' or 'global' (where the Taylor chain's two vectors live; A/B runs and tests).
+    Every other entry point works as on a dense state-transfer engine.
     Sparse ensembles, fleets and maps (include/qoc.h qoc_create_sparse_fleet): with ensemble, fleet, control_map or row_layout the engine is made by
     the sparse ensemble entry point (a line, transfer=, is served by that entry point in C only).  The ensemble's `operators` (Hermitian P_q, scipy.sparse or dense; never densified here) go
     behind the controls as -i dt P_q; with a control_map sparse_ops holds the drift and the r operators the map feeds.  row_layout: None (a plain
     sparse engine stays on qoc_create_sparse), 0 / 'auto', 1 / 'per_operator' (the kernels of a plain sparse engine) or 2 / 'merged' (one list per
-    row over all operators; the same numbers, fewer passes per Taylor term); self.plan['rows'] names what ran.  Decay per member (collapse_ops,
-    rate_scales in the ensemble or the fleet) is refused.
+    row over all operators; the same numbers, fewer passes per Taylor term); self.plan['rows'] names what ran.
 
     control_map (include/qoc.h qoc_create_mapped): a helper_functions.control_map.ControlMap (or a dict alpha / mix / fixed).  Hs then holds the drift
     and the r operators the map feeds, maxA (and one_minus_gauss, the variable, the gradient, get_uks) the k pulses: self.k is the number of pulses,
     self.terms the number of operators.  get_coefficients() gives the (n_seeds, r, steps) coefficients the nominal member's trajectories ran on.
-    Composes with ensemble, transfer, exact_gradient and sparse_ops; not with collapse_ops or time sharding (ValueError, before the library is
-    loaded).
+    Composes with ensemble, transfer, exact_gradient and sparse_ops.
 
     fleet (device fleets, include/qoc.h qoc_create_fleet): a helper_functions.fleet.Fleet, or a dict with keys `offsets` (F x E x q) and `amp_scales`
     (F x E x k).  n_seeds = F R control sets, device-major: control set g is optimised on device g // R's members.  `ensemble` then supplies the
     operators, the weights and the risk (its offsets and amp_scales are not read; a Fleet brings its own when `ensemble` is None; neither: one
     member per device, no perturbation).  self.devices is F; every read-back keeps its (n_seeds, ...) shape.  Composes with transfer, control_map
-    and exact_gradient; not with collapse_ops or time sharding (ValueError, before the library is loaded).
+    and exact_gradient.
 
     decay per member (open-system ensembles and fleets, include/qoc.h qoc_create_open_fleet): an `ensemble` dict with the keys `collapse_ops` (c
     operators as collapse_ops= takes them) and `rate_scales` (E x c, default ones), or a `fleet` with collapse_ops and rate_scales (F x E x c).  Member
     e of device f is then the open problem with the collapse operators sqrt(rate_scales[f, e, j]) C_j; self.open_system is True, get_final_density()
     and get_populations() give member 0 of each control set, member_final_density() every member, and everything an ensemble engine offers (risk,
-    member read-backs, transfer, control_map, the loops) works as it does there.  Not together with the collapse_ops= keyword, exact_gradient,
-    sparse_ops or time sharding (ValueError, before the library is loaded).
+    member read-backs, transfer, control_map, the loops) works as it does there.
 
     running_costs (open-system running costs, include/qoc.h qoc_create_open_costs): a list of at most 16 records (O, coeff, power) as
     helper_functions/open_system.py builds them (level_cost, subspace_cost, observable_cost, dressed_level_cost).  Every trajectory's state regulariser is
@@ -493,52 +613,31 @@ class HipEngine(object):
                  reg_coeffs=None, one_minus_gauss=None, Vs=None, n_seeds=1, device=0, path=PATH_AUTO, chunks=0, variant=0, plan_seeds=0,
                  time_shards=0, time_rank=-1, time_comm=None, ensemble=None, transfer=None, exact_gradient=False, collapse_ops=None,
                  sparse_ops=None, vector_home=None, control_map=None, fleet=None, row_layout=None, running_costs=None):
-        sparse = None
-        decay = None
+        # 1. what the arguments refuse, before the library is loaded (_REFUSALS, and the checks between its blocks)
+        a = dict(Hs=Hs, U0=U0, Vs=Vs, path=path, time_shards=time_shards, time_comm=time_comm, ensemble=ensemble, transfer=transfer,
+                 exact_gradient=exact_gradient, collapse_ops=collapse_ops, sparse_ops=sparse_ops, fleet=fleet)
+        sparse = decay = None
         if sparse_ops is not None:
-            # decay per member needs the open engine, which the sparse route does not have: named before anything is built
-            fget = (lambda key: None) if fleet is None else (fleet.get if isinstance(fleet, dict) else lambda key: getattr(fleet, key, None))
-            for key in ('collapse_ops', 'rate_scales'):
-                if (ensemble is not None and ensemble.get(key) is not None) or fget(key) is not None:
-                    raise ValueError('HipEngine: sparse_ops (sparse state transfer) does not combine with decay per member (%s)' % key)
+            _refuse('sparse_ops with decay', a)
         elif row_layout is not None:
             raise ValueError('HipEngine: row_layout belongs to sparse_ops (sparse state transfer)')
         if (ensemble is not None or fleet is not None) and sparse_ops is None:
-            # (before the fleet's own refusal of collapse_ops=: decay that the members carry is named as such)
             if fleet is not None and ensemble is None and not isinstance(fleet, dict):
                 E_members = int(np.shape(fleet.amp_scales)[1])
             else:
                 E_members = 1 if ensemble is None else int(np.shape(ensemble['amp_scales'])[0])
             decay = decay_arrays(ensemble, fleet, int(np.shape(Hs)[1]), E_members, dt)
         if decay is not None:
-            for name, given in (('the collapse_ops= keyword (the members carry the decay)', collapse_ops is not None),
-                                ('exact_gradient', bool(exact_gradient)), ('time sharding', time_comm is not None or int(time_shards) > 0)):
-                if given:
-                    raise ValueError('HipEngine: an ensemble or fleet with decay does not combine with %s' % name)
+            _refuse('decay', a)
         if fleet is not None:
-            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None),
-                                ('sparse_ops (sparse state transfer) beside a dense Hs', sparse_ops is not None and Hs is not None),
-                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
-                if given:
-                    raise ValueError('HipEngine: fleet does not combine with %s' % name)
+            _refuse('fleet', a)
             if ensemble is None and not isinstance(fleet, dict):
                 ensemble = fleet.device(0)
         if control_map is not None:
-            for name, given in (('collapse_ops (open-system GRAPE)', collapse_ops is not None),
-                                ('sparse_ops (sparse state transfer) beside a dense Hs', sparse_ops is not None and Hs is not None),
-                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
-                if given:
-                    raise ValueError('HipEngine: control_map does not combine with %s' % name)
-            from quantum_optimal_control.helper_functions import control_map as _cmap
+            _refuse('control_map', a)
             control_map = _cmap.validate(control_map, k=np.shape(maxA)[0], r=(len(sparse_ops) if sparse_ops is not None else np.shape(Hs)[0]) - 1, steps=steps)
         if sparse_ops is not None:
-            # (transfer: the line runs on sparse operators behind the C ABI, qoc_create_sparse_fleet; this binding keeps its refusal)
-            for name, given in (('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
-                                ('collapse_ops', collapse_ops is not None), ('time sharding', time_comm is not None or int(time_shards) > 0),
-                                ('Vs (dressed forbidden levels)', Vs is not None), ('a dense Hs', Hs is not None), ('U0', U0 is not None),
-                                ('path %s' % (path,), int(path) not in (PATH_AUTO, PATH_SPARSE))):
-                if given:
-                    raise ValueError('HipEngine: sparse_ops (sparse state transfer) does not combine with %s' % name)
+            _refuse('sparse_ops', a)
             if not state_transfer:
                 raise ValueError('HipEngine: sparse_ops needs state_transfer=True (unitary mode propagates an n x n matrix)')
             if vector_home not in VECTOR_HOME:
@@ -550,21 +649,17 @@ class HipEngine(object):
             # (the ensemble's perturbation operators stand behind the controls, kept sparse)
             sparse = sparse_arrays(list(sparse_ops) + sparse_perturbations(ensemble, dt))
         if collapse_ops is not None:
-            for name, given in (('ensemble', ensemble is not None), ('transfer', transfer is not None), ('exact_gradient', bool(exact_gradient)),
-                                ('time sharding', time_comm is not None or int(time_shards) > 0)):
-                if given:
-                    raise ValueError('HipEngine: collapse_ops (open-system GRAPE) does not combine with %s' % name)
-            from quantum_optimal_control.helper_functions import open_system
+            _refuse('collapse_ops', a)       # (a fleet has refused collapse_ops by now: the ensemble asked about is the caller's)
             collapse_ops = open_system.validate(collapse_ops, np.shape(Hs)[1])
         if running_costs is not None:
             if collapse_ops is None and decay is None:
                 raise ValueError("HipEngine: running_costs need an open engine (collapse_ops=, or decay carried by ensemble or fleet); closed engines take "
                                  "reg_coeffs['forbidden_coeff_list']")
-            from quantum_optimal_control.helper_functions import open_system
             running_costs = open_system.validate_costs(running_costs, np.shape(Hs)[1])
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
+        # 2. the configuration, the caller's arrays and one struct per feature
         if sparse is None:
             Hs = np.ascontiguousarray(np.asarray(Hs, dtype=np.complex128))
             k = Hs.shape[0] - 1 if control_map is None else control_map.n_pulses
@@ -581,25 +676,16 @@ class HipEngine(object):
         maxA = np.ascontiguousarray(np.asarray(maxA, dtype=np.float64))
         assert maxA.shape == (k,)
         rcfg = reg_config(reg_coeffs, total_time)
-        cfg = QocConfig()
-        cfg.n, cfg.k, cfg.steps, cfg.m = n, k, int(steps), m
-        cfg.taylor_terms, cfg.scaling = int(taylor_terms), int(scaling)
-        cfg.state_transfer, cfg.n_seeds = int(bool(state_transfer)), int(n_seeds)
-        cfg.dt, cfg.total_time = float(dt), float(total_time)
-        for name in ('amplitude', 'envelope', 'dwdt', 'd2wdt2', 'speed_up', 'bandpass'):
-            setattr(cfg, 'has_' + name, rcfg['has_' + name])
-            setattr(cfg, 'c_' + name, rcfg['c_' + name])
-        cfg.band_lo, cfg.band_hi = rcfg.get('band_lo', 0), rcfg.get('band_hi', 0)
-        fs = rcfg.get('forbidden_states')
-        fc = rcfg.get('forbidden_coeffs')
-        cfg.n_forbidden = 0 if fs is None else len(fs)
-        use_vs = Vs is not None and cfg.n_forbidden > 0
-        cfg.forbid_dressed = int(use_vs)
-        cfg.device, cfg.path, cfg.chunks, cfg.variant = int(device), int(path), int(chunks), int(variant)
-        cfg.time_shards, cfg.time_rank = int(time_shards), int(time_rank)     # one trajectory sharded along the time axis (csrc/qoc_gemm_ts.h); -1: emulated in this engine
-        cfg.gradient = int(bool(exact_gradient))
+        fs, fc = rcfg.pop('forbidden_states', None), rcfg.pop('forbidden_coeffs', None)
+        use_vs = Vs is not None and fs is not None and len(fs) > 0
+        # time_shards: one trajectory sharded along the time axis (csrc/qoc_gemm_ts.h); time_rank -1: emulated in this engine
+        # plan_seeds 0: plan for n_seeds; > 0: the batch AUTO plans for (sharded restarts: see plan_seeds_for)
+        cfg = QocConfig(n=n, k=k, steps=int(steps), m=m, taylor_terms=int(taylor_terms), scaling=int(scaling), state_transfer=int(bool(state_transfer)),
+                        n_seeds=int(n_seeds), dt=float(dt), total_time=float(total_time), n_forbidden=0 if fs is None else len(fs),
+                        forbid_dressed=int(use_vs), device=int(device), path=int(path), chunks=int(chunks), variant=int(variant),
+                        time_shards=int(time_shards), time_rank=int(time_rank), gradient=int(bool(exact_gradient)), plan_seeds=int(plan_seeds),
+                        **rcfg)       # (what is left of rcfg: the pulse regularisers' has_.. and c_.., band_lo and band_hi)
         self.exact_gradient = bool(exact_gradient)
-        cfg.plan_seeds = int(plan_seeds)       # 0: plan for n_seeds; > 0: the batch AUTO plans for (sharded restarts: see plan_seeds_for)
         omg = None
         if one_minus_gauss is not None:
             omg = np.ascontiguousarray(np.asarray(one_minus_gauss, dtype=np.float64))
@@ -608,119 +694,30 @@ class HipEngine(object):
         args = (None if sparse is not None else _dp(Hs.view(np.float64)), None if U0a is None else _dp(U0a.view(np.float64)), _dp(V.view(np.float64)), _dp(W.view(np.float64)),
                 _dp(maxA), _dp(omg), None if fs is None else fs.ctypes.data_as(_IP), _dp(fc), None if Vsa is None else _dp(Vsa.view(np.float64)),
                 C.byref(self._h))
-        self.members = 0
-        self.open_system = collapse_ops is not None or decay is not None
-        self.samples = None                           # transfer-function GRAPE: P, the length of the variable's rows
-        ens = None
-        if ensemble is not None:
-            P, off, amp, wt = ensemble_arrays(ensemble, n, k, dt, dense=sparse is None)
-            ens = QocEnsemble()
-            ens.members, ens.n_perturb = amp.shape[0], off.shape[1]
-            ens.P = _dp(P.view(np.float64)) if (P is not None and P.shape[0]) else None
-            ens.offsets = _dp(off) if off.shape[1] else None
-            ens.amp_scales, ens.weights = _dp(amp), _dp(wt)
-            self._ens_arrays = (P, off, amp, wt)          # (alive across the call)
-        tr = None
-        self.devices = 0                              # device fleets: F, the devices the n_seeds control sets are spread over
-        if transfer is not None:
-            T = np.ascontiguousarray(np.asarray(transfer, dtype=np.float64))
-            if T.ndim != 2 or T.shape[0] != int(steps):
-                raise ValueError('HipEngine: the transfer matrix has shape %s, expected (%d, P)' % (T.shape, int(steps)))
-            tr = QocTransfer()
-            tr.n_samples, tr.T = T.shape[1], _dp(T)
-        cmap = None
-        if control_map is not None:
-            cmap = QocControlMap()
-            cmap.n_terms, cmap.degree = control_map.n_terms, control_map.degree
-            cmap.poly, cmap.mix, cmap.fixed = _dp(control_map.alpha), _dp(control_map.mix), _dp(control_map.fixed)
-        fl = None
-        if fleet is not None:
-            foff, famp = fleet_arrays(fleet, ens.members if ens is not None else 1, ens.n_perturb if ens is not None else 0, k)
-            fl = QocFleet()
-            fl.devices, fl.offsets, fl.amp_scales = famp.shape[0], (_dp(foff) if foff.shape[2] else None), _dp(famp)
-        rcs = None
-        self.n_costs = 0                              # running costs: L, the observables behind get_expectations()
-        if running_costs is not None:
-            L = len(running_costs)
-            cO = np.ascontiguousarray(np.array([r[0] for r in running_costs], dtype=np.complex128).reshape(L, n, n))
-            ca = np.ascontiguousarray(np.array([r[1] for r in running_costs], dtype=np.float64).reshape(L))
-            cp = np.ascontiguousarray(np.array([r[2] for r in running_costs], dtype=np.int32).reshape(L))
-            rcs = QocRunningCosts()
-            rcs.n_obs, rcs.O, rcs.coeffs, rcs.powers = L, (_dp(cO.view(np.float64)) if L else None), (_dp(ca) if L else None), (cp.ctypes.data_as(_IP) if L else None)
-            self.n_costs = L
-        self.row_layout = None
-        if sparse is not None and (ens is not None or fl is not None or tr is not None or cmap is not None or row_layout is not None):
-            # sparse operators through the ensemble funnel (include/qoc.h, qoc_create_sparse_fleet); a plain sparse engine stays on qoc_create_sparse
-            _, indptr, row, col, val = sparse
-            sp = QocSparse()
-            sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
-            sp.val, sp.vector_home = _dp(val.view(np.float64)), VECTOR_HOME[vector_home]
-            pl = QocSparsePlan()
-            pl.row_layout = ROW_LAYOUT[0 if row_layout is None else row_layout]
-            _check(lib.qoc_create_sparse_fleet(C.byref(cfg), C.byref(sp), C.byref(pl), None if ens is None else C.byref(ens),
-                                               None if fl is None else C.byref(fl), None if tr is None else C.byref(tr),
-                                               None if cmap is None else C.byref(cmap), *(args[2:8] + args[-1:])))
-            if tr is not None:
-                self.samples = int(tr.n_samples)
-            self.devices = 0 if fl is None else int(fl.devices)
-            self.row_layout = int(pl.row_layout)
-        elif decay is not None:
-            D, rates = decay
-            if fl is not None and rates.shape[0] != fl.devices:
-                raise ValueError('HipEngine: rate_scales are for %d devices, the fleet has %d' % (rates.shape[0], fl.devices))
-            if fl is None and rates.shape[0] != 1:
-                raise ValueError('HipEngine: rate_scales with a device axis need a fleet')
-            dc = QocDecay()
-            dc.n_collapse, dc.C, dc.rate_scales = D.shape[0], (_dp(D.view(np.float64)) if D.shape[0] else None), (_dp(rates) if D.shape[0] else None)
-            glue = (None if ens is None else C.byref(ens), None if fl is None else C.byref(fl), None if tr is None else C.byref(tr),
-                    None if cmap is None else C.byref(cmap))
-            if rcs is not None:
-                _check(lib.qoc_create_open_costs(C.byref(cfg), C.byref(dc), C.byref(rcs), *(glue + args[:6] + args[-1:])))
-            else:
-                _check(lib.qoc_create_open_fleet(C.byref(cfg), C.byref(dc), *(glue + args[:6] + args[-1:])))
-            if tr is not None:
-                self.samples = int(tr.n_samples)
-            self.devices = 0 if fl is None else int(fl.devices)
-        elif fleet is not None:
-            _check(lib.qoc_create_fleet(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(fl), None if tr is None else C.byref(tr),
-                                        None if cmap is None else C.byref(cmap), *args))
-            if tr is not None:
-                self.samples = int(tr.n_samples)
-            self.devices = int(fl.devices)
-        elif cmap is not None:
-            _check(lib.qoc_create_mapped(C.byref(cfg), None if ens is None else C.byref(ens), None if tr is None else C.byref(tr), C.byref(cmap), *args))
-            if tr is not None:
-                self.samples = int(tr.n_samples)
-        elif sparse is not None:
-            _, indptr, row, col, val = sparse
-            sp = QocSparse()
-            sp.indptr, sp.row, sp.col = indptr.ctypes.data_as(C.POINTER(C.c_int64)), row.ctypes.data_as(_IP), col.ctypes.data_as(_IP)
-            sp.val, sp.vector_home = _dp(val.view(np.float64)), VECTOR_HOME[vector_home]
-            _check(lib.qoc_create_sparse(C.byref(cfg), C.byref(sp), *(args[2:8] + args[-1:])))
-        elif collapse_ops is not None and rcs is not None:
-            # the plain open problem with running costs: every glue pointer NULL (in the library an ensemble engine of one nominal member; self.members stays 0)
-            D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
-            dc = QocDecay()
-            dc.n_collapse, dc.C, dc.rate_scales = len(collapse_ops), (_dp(D.view(np.float64)) if len(collapse_ops) else None), None
-            _check(lib.qoc_create_open_costs(C.byref(cfg), C.byref(dc), C.byref(rcs), None, None, None, None, *(args[:6] + args[-1:])))
-        elif collapse_ops is not None:
-            # D_j = sqrt(dt) C_j; the state regularisers and Vs stay behind (the library refuses them by name)
-            D = np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
-            op = QocOpen()
-            op.n_collapse, op.C = len(collapse_ops), (_dp(D.view(np.float64)) if len(collapse_ops) else None)
-            _check(lib.qoc_create_open(C.byref(cfg), C.byref(op), *(args[:6] + args[-1:])))
-        elif tr is not None:
-            _check(lib.qoc_create_shaped(C.byref(cfg), None if ens is None else C.byref(ens), C.byref(tr), *args))
-            self.samples = int(tr.n_samples)
-        elif ens is None:
-            _check(lib.qoc_create(C.byref(cfg), *args))
-        else:
-            _check(lib.qoc_create_ensemble(C.byref(cfg), C.byref(ens), *args))
+        none = (None, None)
+        ens, a_ens = _ensemble_struct(ensemble, n, k, dt, sparse is None) if ensemble is not None else none
+        tr, a_tr = _transfer_struct(transfer, int(steps)) if transfer is not None else none
+        cmap, a_map = _map_struct(control_map) if control_map is not None else none
+        fl, a_fl = _fleet_struct(fleet, ens, k) if fleet is not None else none
+        rcs, a_rcs = _costs_struct(running_costs, n) if running_costs is not None else none
+        (sp, pl), a_sp = _sparse_structs(sparse, vector_home, row_layout) if sparse is not None else (none, None)
+        dc, a_dc = _decay_struct(decay[0], decay[1], fl) if decay is not None else none
+        # (the collapse_ops= keyword: qoc_open, and with running costs the qoc_decay of qoc_create_open_costs without a table of rate scales)
+        D = None if collapse_ops is None else np.ascontiguousarray(np.sqrt(float(dt)) * np.array(collapse_ops, dtype=np.complex128).reshape(len(collapse_ops), n, n))
+        op, a_op = _decay_struct(D, kind=QocOpen if rcs is None else QocDecay) if collapse_ops is not None else none
+        # 3. the one call (a_..: the arrays behind the structs, alive across it), and what the structs say about the engine it made
+        symbol, call_args = _entry_point(C.byref(cfg), args, dict(ensemble=ens, fleet=fl, transfer=tr, control_map=cmap, decay=dc, open=op, costs=rcs,
+                                                                  sparse=sp, plan=pl), row_layout is not None)
+        _check(getattr(lib, symbol)(*call_args))
+        by_sparse_fleet = symbol == 'qoc_create_sparse_fleet'
+        self.open_system = op is not None or dc is not None
+        self.samples = None if tr is None else int(tr.n_samples)          # transfer-function GRAPE: P, the length of the variable's rows
+        self.devices = 0 if fl is None else int(fl.devices)                 # device fleets: F, the devices the n_seeds control sets are spread over
+        self.n_costs = 0 if rcs is None else int(rcs.n_obs)                 # running costs: L, the observables behind get_expectations()
+        self.row_layout = int(pl.row_layout) if by_sparse_fleet else None
         self.perturbations = 0 if ens is None else int(ens.n_perturb)     # q: the frozen control rows behind the `terms` rows of every trajectory
-        if ens is not None:
-            self.members = int(ens.members)
-        elif fleet is not None or self.row_layout is not None:
-            self.members = 1                          # (a sparse engine of the ensemble entry point: one nominal member)
+        # (without ensemble: one nominal member on a fleet and on a sparse engine of the ensemble entry point; collapse_ops= with running costs stays 0)
+        self.members = int(ens.members) if ens is not None else int(fl is not None or by_sparse_fleet)
         self.risk = 0.0
         if ensemble is not None and float(ensemble.get('risk', 0.0)) > 0:
             self.set_risk(ensemble['risk'])

@@ -1,6 +1,6 @@
 """Seeded random draws for the glue between the views of an ensemble engine (tests/test_glue_fuzz.py): k_ens_expand / k_ens_reduce(_risk), k_ens_tilt,
 k_shape_expand / k_shape_reduce(_risk)<1|64>, k_map_expand / k_map_reduce, as robust ensembles, risk, transfer lines, control maps, device fleets,
-open-system members and sparse operators reach them through create_members, create_shaped and create_fleet.
+open-system members and sparse operators reach them through create_composed.
 
 Three families, each a pure function of its seed: closed(seed), opened(seed), sparse(seed).  A draw holds the problem, the glue objects (the
 ensemble or the Fleet, the map, the line's matrix, beta, the exact flag), the start points `xs` of its G control sets, `info` (what was drawn: it
