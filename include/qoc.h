@@ -411,6 +411,28 @@ int qoc_create_sparse_fleet(const qoc_config* cfg, const qoc_sparse* ops, const 
                             const qoc_transfer* transfer, const qoc_control_map* map, const double* V, const double* W, const double* maxA,
                             const double* one_minus_gauss, const int32_t* forbidden_states, const double* forbidden_coeffs, qoc_handle* out);
 
+/* ---- noise traces: ensemble members with time-dependent perturbations -------------------------------------------------------------------------
+ * Every member table above holds errors that are constant over the pulse (offsets), and collapse operators hold white noise; a trace table is what
+ * lies between: sampled noise trajectories (1/f-like flux noise, a detuning that drifts during the gate, a switching fluctuator), one per member
+ * and perturbation.  With a table set, frozen row q' of member e of device f has at slice t the value
+ *     offsets[f][e][q'] + traces[f][e][q'][t]
+ * (one fp64 add, formed where the row is written), and everything else is what the engine defines for that control row: the trajectories' k + q
+ * (with a map: r + q) controls on every route -- dense, open (the slice's generator reads every row per slice) and sparse (both row layouts) --,
+ * the member reduction, qoc_set_risk, lines, maps, fleets, gradient = 1, both loops and the stop rule.  The objective is the sample average (or
+ * soft worst case) over the fixed set of traces.  taylor_terms and scaling stay the caller's: choose them for the largest |offsets + traces[t]|.
+ * traces: [F][E][q][steps] with F = the fleet's devices, 1 without a fleet; NULL removes the table.  Without a table an engine launches exactly the
+ * kernels it launched before this entry point existed; while one is set qoc_plan_describe appends traces=1.  Two evaluations are bit-identical; an
+ * all-zero table computes the values of no table, and offsets 0 with constant traces c the values of offsets c (equal under ==).
+ * Valid on every engine with a member table and q >= 1 (qoc_create_ensemble, _shaped, _mapped, _fleet, _open_fleet, _open_costs, _sparse_fleet).
+ * QOC_ERR_STATE, with the cause named: an engine without a member table (qoc_create, qoc_create_open, qoc_create_sparse); q = 0.
+ * QOC_ERR_INVALID: a non-finite entry.  QOC_ERR_NOMEM: the device copy does not fit.
+ * Timing as for qoc_set_risk: it may be called between evaluations or bursts of qoc_iterate / qoc_iterate_lbfgs (fresh draws every N iterations); it
+ * waits for the enqueued work and holds from the next evaluation.  The first call with a table allocates the device copy, later calls overwrite it.
+ * The setter resets NOTHING: Adam moments, the L-BFGS history and accepted point, iteration counters and done flags stay as they are.  A new table is
+ * a new objective: a caller who resamples under L-BFGS owns the consequences (curvature pairs and the Armijo reference value belong to the old
+ * one), and a control set that a loop has finished stays finished. */
+int qoc_set_traces(qoc_handle h, const double* traces);
+
 /* ---- the trainable variable -------------------------------------------------------------------------------------
  * ops_weight_base [n_seeds][k][steps]  (tensorflow_state.py:174; ops_weight_base.assign, run_session.py:121).
  * qoc_set_base also resets the Adam slots and the per-seed iteration counters / done flags. */

@@ -105,6 +105,8 @@ struct qoc_engine {
     // risk-sensitive objective (qoc_set_risk, k_ens_tilt): beta > 0 replaces the weighted mean by the soft worst case over the members
     double risk_beta = 0.0;
     double* risk_pi = nullptr;      // [G][E] tilted weights of the last evaluation, allocated by the first qoc_set_risk with beta > 0
+    // noise traces (qoc_set_traces): [F][E][q][steps] added to the frozen rows per slice; en.tr points at it while a table is set
+    double* traces = nullptr;       // allocated by the first qoc_set_traces with a table, kept (and overwritten) afterwards
     // transfer-function GRAPE (qoc_create_shaped, csrc/qoc_transfer.h): an ensemble engine whose group view is the SAMPLE view (P samples per
     // control in place of the time slices) and whose glue kernels apply the response matrix
     bool shaped = false;
@@ -341,11 +343,14 @@ static void enqueue_controls(const qoc_engine* e, const QocDev& d, const QocDev&
         if (!own_controls && !swap_in) launch_controls(d, e->stream);
     } else if (!e->shaped) {
         // every member's controls from its group's (formed from the variable unless the last tail left them), and the done flags
-        hipLaunchKernelGGL(k_ens_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+        // (a trace table: the instance that adds it to the frozen rows; without one, the kernel of every engine so far)
+        if (e->en.tr) hipLaunchKernelGGL(k_ens_expand_traces, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
+        else hipLaunchKernelGGL(k_ens_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, swap_in ? 0 : 1);
     } else {
         // a pulse response: the samples w_s / u_s from the variable (unless the last tail left them), then the pulse through the response
         if (!swap_in) launch_controls(gd, e->stream);
-        hipLaunchKernelGGL(k_shape_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
+        if (e->en.tr) hipLaunchKernelGGL(k_shape_expand_traces, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
+        else hipLaunchKernelGGL(k_shape_expand, eg, dim3(QOC_BLOCK), 0, e->stream, d, gd, e->en, e->sh);
     }
 }
 // 2. trajectories: exponentials, forward, loss, backward of the engine's path; qoc_profile_read's hipEvent bracket around the dominant one
@@ -1986,6 +1991,25 @@ int qoc_set_risk(qoc_handle e, double beta) {
     return QOC_OK;
 }
 
+int qoc_set_traces(qoc_handle e, const double* traces) {
+    CHECK_H(e);
+    if (!e->ens_E)
+        return fail(QOC_ERR_STATE, "qoc_set_traces: the engine has no member table (qoc_create, qoc_create_open and qoc_create_sparse make none; "
+                                   "qoc_create_ensemble and the entry points after it do)");
+    if (e->en.q < 1) return fail(QOC_ERR_STATE, "qoc_set_traces: the members have no perturbation row to add a trace to (q = 0)");
+    const size_t F = e->fleet_F ? (size_t)e->fleet_F : 1;
+    const size_t cnt = F * (size_t)e->ens_E * (size_t)e->en.q * (size_t)e->d.steps;
+    if (traces)
+        for (size_t i = 0; i < cnt; ++i)
+            if (!std::isfinite(traces[i])) return fail(QOC_ERR_INVALID, "qoc_set_traces: entry %zu of the table is not finite", i);
+    HIP_TRY(hipStreamSynchronize(e->stream));            // (the evaluations enqueued so far keep the table they were enqueued with)
+    if (!traces) { e->en.tr = nullptr; return QOC_OK; }  // (the device copy stays for a later table)
+    if (!e->traces) TRY(dev_alloc(e, &e->traces, cnt));
+    HIP_TRY(hipMemcpy(e->traces, traces, cnt * sizeof(double), hipMemcpyHostToDevice));
+    e->en.tr = e->traces;
+    return QOC_OK;
+}
+
 int qoc_get_member_weights(qoc_handle e, double* pi) {
     CHECK_H(e);
     if (!e->ens_E) return fail(QOC_ERR_STATE, "qoc_get_member_weights: not an ensemble engine (qoc_create_ensemble, qoc_create_shaped)");
@@ -2129,6 +2153,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (e->xg.on) add(" exact_variant=%s exact_lds=%zu exact_grid=%d", e->xg.lds ? "lds" : "global", e->xg.lds_bytes, e->xg.grid);
     // open engines with running costs only (qoc_create_open_costs)
     if (e->lb.on && e->lb.nc > 0) add(" running_costs=%d", e->lb.nc);
+    // while a trace table is set only (qoc_set_traces)
+    if (e->en.tr) add(" traces=1");
     snprintf(buf, (size_t)len, "%s", tmp);
     return QOC_OK;
 }

@@ -18,13 +18,36 @@ struct QocEns {
     const double* a;       // [F][E][k]  amplitude scale of each control
     const double* delta;   // [F][E][q]  value of each frozen perturbation row
     const double* wt;      // [E]        member weights
+    const double* tr;      // [F][E][q][steps] noise traces (qoc_set_traces): frozen row q' of member e runs delta[e][q'] + tr[e][q'][t]; null: none
 };
+
+// One frozen row at one slice with a trace table, for the members 0 .. E-1 in that order: tu[e tstride] = delta[e q] + tr[e estride].  Eight
+// members' loads are issued before their eight stores: the loop is a chain of independent loads `q steps` doubles apart, and one load per trip
+// left a thread of the qubit x 1024-member ensemble waiting for each in turn (0.29 ms per iteration; profiles/noise_traces.txt).  The values and
+// the order of the stores are those of the plain loop.
+#define QOC_TRACE_BATCH 8
+__device__ __forceinline__ void ens_trace_rows(double* __restrict__ tu, size_t tstride, const double* __restrict__ delta, int q,
+                                               const double* __restrict__ tr, size_t estride, int E) {
+    int e = 0;
+    for (; e + QOC_TRACE_BATCH <= E; e += QOC_TRACE_BATCH) {
+        double v[QOC_TRACE_BATCH];
+#pragma unroll
+        for (int i = 0; i < QOC_TRACE_BATCH; ++i) v[i] = delta[(size_t)(e + i) * q] + tr[(size_t)(e + i) * estride];
+#pragma unroll
+        for (int i = 0; i < QOC_TRACE_BATCH; ++i) tu[(size_t)(e + i) * tstride] = v[i];
+    }
+    for (; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * q] + tr[(size_t)e * estride];
+}
 
 // Trajectory controls from the group's: thread per (group, row j < k', slice), a loop over the members.  from_base: the group's controls
 // are formed here from its variable (w = sin(base), u = maxA w: k_controls' arithmetic) and stored to the group view too; else they are the
 // group's u (what the Adam tail left in u2 and the engine swapped in).  Also mirrors the group's done flag into its trajectories: the heavy
 // kernels skip finished trajectories by their own flag.
-__global__ void __launch_bounds__(256) k_ens_expand(QocDev t, QocDev g, QocEns en, int from_base) {
+// TRACES (k_ens_expand_traces, launched while a table is set): a frozen row is delta[e][q'] + tr[e][q'][t], one fp64 add where the row is
+// written.  The slice is the thread's fastest index, so the members' reads are q steps apart and coalesced along t.  Without a table the
+// engine launches k_ens_expand, whose code is what it was before the table existed.
+template <bool TRACES>
+__device__ __forceinline__ void ens_expand_body(const QocDev& t, const QocDev& g, const QocEns& en, int from_base) {
     const int steps = g.steps, k = g.k, kp = t.k, E = en.E;
     const size_t total = (size_t)g.B * kp * steps;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -49,12 +72,20 @@ __global__ void __launch_bounds__(256) k_ens_expand(QocDev t, QocDev g, QocEns e
             for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = a[(size_t)e * k + j] * gu;
         } else {
             const double* delta = en.delta + dev * en.q;
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
+            if (TRACES) {
+                const size_t estride = (size_t)en.q * steps;
+                const double* tr = en.tr + (dev * en.q + (j - k)) * steps + tt;
+                ens_trace_rows(tu, tstride, delta + (j - k), en.q, tr, estride, E);
+            } else {
+                for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
+            }
         }
         if (j == 0 && tt == 0)
             for (int e = 0; e < E; ++e) t.done[(size_t)gi * E + e] = g.done[gi];
     }
 }
+__global__ void __launch_bounds__(256) k_ens_expand(QocDev t, QocDev g, QocEns en, int from_base) { ens_expand_body<false>(t, g, en, from_base); }
+__global__ void __launch_bounds__(256) k_ens_expand_traces(QocDev t, QocDev g, QocEns en, int from_base) { ens_expand_body<true>(t, g, en, from_base); }
 
 // Group gradient and scalars from the members': dLdu_g[j][t] = sum_e (w_e a[e][j]) dLdu_(g,e)[j][t] for j < k, loss_g and reg_state_g the
 // weighted sums of the members' (which stay readable in the trajectory arrays).  Grid (ceil(k steps / 256), G); members summed in the order

@@ -32,8 +32,10 @@ struct QocShape {
 // Trajectory controls from the samples: thread per (control set, row j < k', slice t).  s.w holds w_s of the evaluation (k_controls on the
 // sample view, or what the Adam tail left and the engine swapped in): no sin here.  The row window is summed in ascending p, starting from
 // its first term.  Stores the nominal pulse, every member's scaled copy and the frozen perturbation rows, and mirrors the done flags
-// (as k_ens_expand).
-__global__ void __launch_bounds__(256) k_shape_expand(QocDev t, QocDev s, QocEns en, QocShape sh) {
+// (as k_ens_expand).  TRACES (k_shape_expand_traces, launched while a table is set): a frozen row is delta[e][q'] + tr[e][q'][t], as in
+// k_ens_expand_traces; k_shape_expand itself is the code it was before the table existed.
+template <bool TRACES>
+__device__ __forceinline__ void shape_expand_body(const QocDev& t, const QocDev& s, const QocEns& en, const QocShape& sh) {
 #pragma clang fp contract(off)
     const int steps = t.steps, P = sh.P, k = s.k, kp = t.k, E = en.E;
     const size_t total = (size_t)s.B * kp * steps;
@@ -60,12 +62,20 @@ __global__ void __launch_bounds__(256) k_shape_expand(QocDev t, QocDev s, QocEns
             for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = a[(size_t)e * k + j] * gu;
         } else {
             const double* delta = en.delta + dev * en.q;
-            for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
+            if (TRACES) {
+                const size_t estride = (size_t)en.q * steps;
+                const double* tr = en.tr + (dev * en.q + (j - k)) * steps + tt;
+                ens_trace_rows(tu, tstride, delta + (j - k), en.q, tr, estride, E);
+            } else {
+                for (int e = 0; e < E; ++e) tu[(size_t)e * tstride] = delta[(size_t)e * en.q + (j - k)];
+            }
         }
         if (j == 0 && tt == 0)
             for (int e = 0; e < E; ++e) t.done[(size_t)gi * E + e] = s.done[gi];
     }
 }
+__global__ void __launch_bounds__(256) k_shape_expand(QocDev t, QocDev s, QocEns en, QocShape sh) { shape_expand_body<false>(t, s, en, sh); }
+__global__ void __launch_bounds__(256) k_shape_expand_traces(QocDev t, QocDev s, QocEns en, QocShape sh) { shape_expand_body<true>(t, s, en, sh); }
 
 // the members' weighted gradient of one (j, t) element: members summed 0 .. E-1 from member 0's term (k_ens_reduce's arithmetic); a: the
 // amplitude rows of the control set's device

@@ -117,6 +117,7 @@ _SIGNATURES = {
     'qoc_get_trajectory_gradient': (C.c_int, [C.c_void_p, _DP]),
     'qoc_set_risk': (C.c_int, [C.c_void_p, C.c_double]),
     'qoc_get_member_weights': (C.c_int, [C.c_void_p, _DP]),
+    'qoc_set_traces': (C.c_int, [C.c_void_p, _DP]),
     'qoc_destroy': (C.c_int, [C.c_void_p]),
     'qoc_set_base': (C.c_int, [C.c_void_p, _DP]),
     'qoc_get_base': (C.c_int, [C.c_void_p, _DP]),
@@ -585,6 +586,12 @@ class HipEngine(object):
     sparse engine stays on qoc_create_sparse), 0 / 'auto', 1 / 'per_operator' (the kernels of a plain sparse engine) or 2 / 'merged' (one list per
     row over all operators; the same numbers, fewer passes per Taylor term); self.plan['rows'] names what ran.
 
+    noise traces (include/qoc.h qoc_set_traces): an `ensemble` dict with the key `traces` (E x q x steps), or a `fleet` with traces (F x E x q x steps):
+    frozen row q' of member e then runs offsets[e, q'] + traces[e, q', t] at slice t -- sampled noise trajectories (helper_functions/noise.py) in place
+    of errors that are constant over the pulse.  The table is uploaded after creation (the fleet's stands in front of the ensemble's, as its other rows
+    do), set_traces() replaces or removes it between evaluations or bursts of iterations, and self.plan['traces'] is '1' while one is set.  Works on
+    every engine with members and q >= 1, open and sparse ones included; taylor_terms and scaling are the caller's (robust.choose_taylor's rule).
+
     control_map (include/qoc.h qoc_create_mapped): a helper_functions.control_map.ControlMap (or a dict alpha / mix / fixed).  Hs then holds the drift
     and the r operators the map feeds, maxA (and one_minus_gauss, the variable, the gradient, get_uks) the k pulses: self.k is the number of pulses,
     self.terms the number of operators.  get_coefficients() gives the (n_seeds, r, steps) coefficients the nominal member's trajectories ran on.
@@ -723,9 +730,13 @@ class HipEngine(object):
             self.set_risk(ensemble['risk'])
         self.path = lib.qoc_path_in_use(self._h)
         self.chunks = lib.qoc_chunks_in_use(self._h)
-        buf = C.create_string_buffer(1024)
-        _check(lib.qoc_plan_describe(self._h, buf, 1024))
-        self.plan = dict(kv.split('=', 1) for kv in buf.value.decode().split())
+        self._read_plan()
+        # noise traces: the fleet's table, else the ensemble's (Grape hands device 0 of a fleet over as its ensemble)
+        traces = _getter(fleet)('traces') if fleet is not None else None
+        if traces is None and fleet is None and ensemble is not None:
+            traces = ensemble.get('traces')
+        if traces is not None:
+            self.set_traces(traces)
         if time_comm is not None:
             _check(lib.qoc_set_time_comm(self._h, time_comm._h))
             self._time_comm = time_comm                # keep it alive as long as the engine
@@ -884,6 +895,25 @@ class HipEngine(object):
         mean.  Holds from the next evaluation, so a caller may anneal it between evaluations or bursts of iterations."""
         _check(self._lib.qoc_set_risk(self._h, float(beta)))
         self.risk = float(beta)
+
+    def _read_plan(self):
+        buf = C.create_string_buffer(1024)
+        _check(self._lib.qoc_plan_describe(self._h, buf, 1024))
+        self.plan = dict(kv.split('=', 1) for kv in buf.value.decode().split())
+
+    def set_traces(self, traces):
+        """Ensemble engines with q >= 1: the table of noise traces (include/qoc.h qoc_set_traces), (E, q, steps) -- with a fleet (F, E, q, steps) --
+        added per slice to the frozen perturbation rows; None removes it.  Holds from the next evaluation and resets nothing (Adam moments, L-BFGS
+        history, done flags), so a caller may draw fresh traces between bursts of iterate(); self.plan['traces'] follows."""
+        if traces is None:
+            _check(self._lib.qoc_set_traces(self._h, None))
+        else:
+            shape = ((self.devices,) if self.devices else ()) + (max(self.members, 1), self.perturbations, self.steps)
+            tr = np.ascontiguousarray(np.asarray(traces, dtype=np.float64))
+            if self.perturbations >= 1 and tr.shape != shape:
+                raise ValueError('HipEngine: traces have shape %s, expected %s' % (tr.shape, shape))
+            _check(self._lib.qoc_set_traces(self._h, _dp(tr)))
+        self._read_plan()
 
     def member_weights(self):
         """Ensemble engines: the tilted weights pi_e of the last evaluation, [n_seeds][members] (the members' own weights at risk 0)."""

@@ -8,6 +8,9 @@ One engine holds R control sets per device (``restarts=R``), device-major, and o
 
 Decay per device: a fleet may carry collapse_ops (c operators as Grape(collapse_ops=...) takes them, shared by the devices) and rate_scales
 (F, E, c): member e of device f decays through sqrt(rate_scales[f, e, j]) C_j, and every member is an open problem (qoc_create_open_fleet).
+
+Noise traces: a fleet may carry traces (F, E, q, steps): member e of device f then runs offsets[f, e, q] + traces[f, e, q, t] at slice t
+(helper_functions/robust.py, include/qoc.h qoc_set_traces).
 """
 import numpy as np
 
@@ -17,9 +20,11 @@ from quantum_optimal_control.helper_functions import robust as _robust
 class Fleet(object):
     """offsets (F, E, q), amp_scales (F, E, k), operators (q Hermitian n x n matrices), weights (E,) and risk (beta >= 0).  After a
     Grape(fleet=...) run: losses (F,) of every device's best control set, best (F,) the restart that won, member_losses (F, E) of that
-    control set and iterations (F,) it took.  collapse_ops (c operators, or None: closed devices) and rate_scales (F, E, c), default ones."""
+    control set and iterations (F,) it took.  collapse_ops (c operators, or None: closed devices) and rate_scales (F, E, c), default ones.
+    traces (F, E, q, steps), or None: noise traces added per slice to the offsets."""
 
-    def __init__(self, operators, offsets, amp_scales, weights=None, risk=0.0, collapse_ops=None, rate_scales=None):
+    def __init__(self, operators, offsets, amp_scales, weights=None, risk=0.0, collapse_ops=None, rate_scales=None, traces=None):
+        self.traces = None if traces is None else np.asarray(traces, dtype=np.float64)
         self.operators = [_robust.as_operator(p) for p in operators]
         self.offsets = np.asarray(offsets, dtype=np.float64)
         self.amp_scales = np.asarray(amp_scales, dtype=np.float64)
@@ -48,6 +53,8 @@ class Fleet(object):
             dev['collapse_ops'] = list(self.collapse_ops)
             dev['rate_scales'] = (np.ones((self.n_members, len(self.collapse_ops))) if self.rate_scales is None
                                   else np.array(self.rate_scales[f]))
+        if getattr(self, 'traces', None) is not None:
+            dev['traces'] = np.array(self.traces[f])
         return dev
 
     @property
@@ -64,9 +71,10 @@ def _device_rows(values, F, width, name):
     return a
 
 
-def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=None, rate_scales=None):
+def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=None, rate_scales=None, traces=None):
     """A fleet of one member per device: offsets (F, q), one row of perturbation values per device, and amp_scales (F, k) or None (ones).
-    collapse_ops with rate_scales (F, c) or None (ones): every device decays through its own sqrt(rate_scales[f, j]) C_j."""
+    collapse_ops with rate_scales (F, c) or None (ones): every device decays through its own sqrt(rate_scales[f, j]) C_j.
+    traces (F, q, steps) or None: every device's own noise traces."""
     if k is None:
         raise ValueError('fleet.devices: k (the number of pulses) is required')
     k = int(k)
@@ -93,14 +101,21 @@ def devices(operators=(), offsets=None, amp_scales=None, k=None, collapse_ops=No
     off = np.zeros((F, 1, q)) if not q else offsets.reshape(F, 1, q)
     amp = np.ones((F, 1, k)) if amp_scales is None else amp_scales.reshape(F, 1, k)
     rates = None if rate_scales is None else rate_scales.reshape(F, 1, -1)
-    return validate(Fleet(operators, off, amp, collapse_ops=collapse_ops, rate_scales=rates), None, k, sparse=None)
+    if traces is not None:
+        traces = np.asarray(traces, dtype=np.float64)
+        if traces.ndim != 3 or traces.shape[:2] != (F, q):
+            raise ValueError('fleet: traces have shape %s, expected (%d, %d, steps)' % (traces.shape, F, q))
+        traces = traces[:, None]
+    return validate(Fleet(operators, off, amp, collapse_ops=collapse_ops, rate_scales=rates, traces=traces), None, k, sparse=None)
 
 
-def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, collapse_ops=None, rate_scales=None):
+def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, collapse_ops=None, rate_scales=None, traces=None):
     """Every device gets the ensemble `robust` (a Grape(robust=...) dict over the same operators) centred on it: member e of device f has the
     offsets offsets[f] + robust offsets[e] and the scales amp_scales[f] * robust amp_scales[e].  Weights and risk are the ensemble's.
     Decay: the collapse operators are the fleet's (collapse_ops) or the ensemble's -- the same list when both carry one --, and member e of
-    device f has the rate scales rate_scales[f] * robust rate_scales[e] (either defaults to ones)."""
+    device f has the rate scales rate_scales[f] * robust rate_scales[e] (either defaults to ones).
+    traces (F, E, q, steps) or None: the members' noise traces, device by device; the ensemble's own traces (E, q, steps), when it carries some, are
+    added to every device's."""
     if robust is None:
         raise ValueError('fleet.around: robust (the ensemble every device gets) is required')
     if k is None:
@@ -122,16 +137,23 @@ def around(operators=(), offsets=None, amp_scales=None, robust=None, k=None, col
         F, E, c = off.shape[0], off.shape[1], len(cops)
         dev_r = np.ones((F, 1, c)) if centre.rate_scales is None else centre.rate_scales
         rates = dev_r[:, 0][:, None, :] * (ens['rate_scales'] if 'rate_scales' in ens else np.ones((E, c)))[None, :, :]
-    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=cops, rate_scales=rates), None, int(k),
-                    sparse=None)
+    if traces is not None:
+        traces = np.asarray(traces, dtype=np.float64)
+        if traces.ndim != 4 or traces.shape[:3] != off.shape:
+            raise ValueError('fleet: traces have shape %s, expected %s + (steps,)' % (traces.shape, off.shape))
+    if 'traces' in ens:
+        traces = np.broadcast_to(ens['traces'][None], off.shape + ens['traces'].shape[2:]) + (0.0 if traces is None else traces)
+    return validate(Fleet(centre.operators, off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=cops, rate_scales=rates, traces=traces),
+                    None, int(k), sparse=None)
 
 
-def validate(fleet, n, k, sparse=False):
+def validate(fleet, n, k, sparse=False, steps=None):
     """Checks a Fleet against a problem of n levels (None: from the operators) and k pulses and returns a normalised copy: operators complex
     Hermitian n x n, offsets (F, E, q), amp_scales (F, E, k), weights (E,) summing to 1 (default uniform), risk a finite float >= 0.
     collapse_ops (None, or c complex n x n matrices) and rate_scales (F, E, c), finite and >= 0 (default ones; None without collapse_ops).
     Raises ValueError with the cause.  sparse=True (the sparse state-transfer route): the operators come back as complex CSR and are never
-    densified, and decay is refused; sparse=None (the builders): the operators stay as given (robust.validate's rules)."""
+    densified, and decay is refused; sparse=None (the builders): the operators stay as given (robust.validate's rules).
+    traces (None, or (F, E, q, steps), finite, q >= 1; steps given: checked against it)."""
     if not isinstance(fleet, Fleet):
         raise ValueError('fleet: a helper_functions.fleet.Fleet (fleet.devices, fleet.around)')
     amp = np.array(fleet.amp_scales, dtype=np.float64)            # (copies: the normalised fleet owns its arrays)
@@ -159,11 +181,23 @@ def validate(fleet, n, k, sparse=False):
         if not np.all(np.isfinite(rates)) or np.any(rates < 0):
             raise ValueError('fleet: rate_scales must be finite and >= 0')
         dev0.update(collapse_ops=cops, rate_scales=rates[0])
+    traces = getattr(fleet, 'traces', None)
+    if traces is not None:
+        traces = np.array(traces, dtype=np.float64)
+        if q < 1:
+            raise ValueError('fleet: traces given without operators (a trace is added to a perturbation row: q >= 1)')
+        if traces.ndim != 4 or traces.shape[:3] != (F, E, q) or traces.shape[3] < 1:
+            raise ValueError('fleet: traces have shape %s, expected (%d, %d, %d, steps)' % (traces.shape, F, E, q))
+        if steps is not None and traces.shape[3] != int(steps):
+            raise ValueError('fleet: traces have %d slices, the pulse has %d' % (traces.shape[3], int(steps)))
+        if not np.all(np.isfinite(traces)):
+            raise ValueError('fleet: traces must be finite')
     try:
         ens = _robust.validate(dev0, n, k, sparse=sparse)
     except ValueError as err:
         raise ValueError(str(err).replace('robust:', 'fleet:', 1))
-    return Fleet(ens['operators'], off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=ens.get('collapse_ops'), rate_scales=rates)
+    return Fleet(ens['operators'], off, amp, weights=ens['weights'], risk=ens['risk'], collapse_ops=ens.get('collapse_ops'), rate_scales=rates,
+                 traces=traces)
 
 
 def tile_bases(base, F):
@@ -186,10 +220,11 @@ def select_best(loss, F):
 
 
 def choose_taylor(fleet, H0, Hops, control_map, maxA, U0, total_time, steps, unitary_error, state_transfer, no_scaling):
-    """(Taylor terms, squarings): the maximum over every member of every device of robust.choose_taylor / control_map.choose_taylor."""
+    """(Taylor terms, squarings): the maximum over every member of every device of robust.choose_taylor / control_map.choose_taylor.  With traces a
+    member's problem uses, per operator, the value of offsets + traces[t] of largest magnitude over t (robust.taylor_view)."""
     best_t, best_s = 0, 0
     for f in range(fleet.n_devices):
-        dev = fleet.device(f)
+        dev = _robust.taylor_view(fleet.device(f))
         if control_map is not None:
             from quantum_optimal_control.helper_functions import control_map as _cmap
             t, s = _cmap.choose_taylor(control_map, H0, Hops, dev, maxA, U0, total_time, steps, unitary_error, state_transfer, no_scaling)

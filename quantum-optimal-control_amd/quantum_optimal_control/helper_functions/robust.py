@@ -8,6 +8,10 @@ worst case  max_e c_e + log1p(sum_e w_e expm1(beta (c_e - max_e c_e))) / beta  (
 Decay per member: with the optional keys `collapse_ops` (c operators as Grape(collapse_ops=...) takes them) and `rate_scales` (E, c) a member is
 an OPEN problem: member e decays through sqrt(rate_scales[e, j]) C_j (a scale of 0 switches the channel off; default ones), and Grape scores and
 optimises the pulse under every member's master equation (include/qoc.h, qoc_create_open_fleet).
+
+Noise traces: with the optional key `traces` (E, q, steps) the perturbation of a member is no longer constant over the pulse: at slice t member e
+has the drift H0 + sum_q (offsets[e, q] + traces[e, q, t]) P_q -- sampled noise trajectories, e.g. from helper_functions.noise -- and the pulse is
+optimised for the sample average (or soft worst case) over them (include/qoc.h, qoc_set_traces).
 """
 import itertools
 
@@ -123,7 +127,7 @@ def ensemble_grid(operators=(), offsets=None, amp_scales=None, k=None, weights=N
     return validate(ens, None, k, sparse=None)          # (the operators stay as given: the route's own validate call makes them sparse or dense)
 
 
-def validate(robust, n, k, sparse=False):
+def validate(robust, n, k, sparse=False, steps=None):
     """Checks a robust dict (keys operators, offsets, amp_scales, weights, risk) against a problem of n levels (None: from the operators) and
     k controls and returns it normalised: operators a list of q complex n x n Hermitian matrices, offsets (E, q), amp_scales (E, k)
     (default ones), weights (E,) summing to 1 (default uniform), risk a finite float >= 0 (default 0.0: the weighted mean).  With the key
@@ -131,10 +135,12 @@ def validate(robust, n, k, sparse=False):
     >= 0 (default ones); without it the result has exactly the five keys above.  Raises ValueError.
     sparse=True (the sparse state-transfer route): the operators come back as complex CSR matrices -- a scipy.sparse operator is never densified,
     a dense one is converted once -- and the decay keys are refused; sparse=False densifies scipy.sparse operators; sparse=None (ensemble_grid and
-    the fleet builders, before any route is known) leaves every operator in the kind it was given as and refuses nothing."""
+    the fleet builders, before any route is known) leaves every operator in the kind it was given as and refuses nothing.
+    With the key traces the result also holds traces (E, q, steps), finite, q >= 1, checked against the other rows and -- steps given -- against the
+    number of slices; the key is allowed with sparse=True and with decay.  Without it the result has no such key."""
     if not isinstance(robust, dict):
         raise ValueError('robust: a dict with keys operators, offsets, amp_scales, weights, risk')
-    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk', 'collapse_ops', 'rate_scales'}
+    unknown = set(robust) - {'operators', 'offsets', 'amp_scales', 'weights', 'risk', 'collapse_ops', 'rate_scales', 'traces'}
     if unknown:
         raise ValueError('robust: unknown keys %s' % sorted(unknown))
     try:
@@ -177,6 +183,17 @@ def validate(robust, n, k, sparse=False):
         if offsets.ndim != 2 or offsets.shape[1] != 0:
             raise ValueError('robust: offsets given without operators')
         E = offsets.shape[0]
+    traces = robust.get('traces')
+    if traces is not None:
+        traces = np.asarray(traces, dtype=np.float64)
+        if q < 1:
+            raise ValueError('robust: traces given without operators (a trace is added to a perturbation row: q >= 1)')
+        if traces.ndim != 3 or traces.shape[0] != E or traces.shape[1] != q or traces.shape[2] < 1:
+            raise ValueError('robust: traces have shape %s, expected (%d, %d, steps)' % (traces.shape, E, q))
+        if steps is not None and traces.shape[2] != int(steps):
+            raise ValueError('robust: traces have %d slices, the pulse has %d' % (traces.shape[2], int(steps)))
+        if not np.all(np.isfinite(traces)):
+            raise ValueError('robust: traces must be finite')
     amp = robust.get('amp_scales')
     if amp is not None:
         amp = np.asarray(amp, dtype=np.float64)
@@ -211,6 +228,21 @@ def validate(robust, n, k, sparse=False):
         if not np.all(np.isfinite(rates)) or np.any(rates < 0):
             raise ValueError('robust: rate_scales must be finite and >= 0')
         out['collapse_ops'], out['rate_scales'] = cops, rates
+    if traces is not None:
+        out['traces'] = traces
+    return out
+
+
+def taylor_view(robust):
+    """The ensemble as the Taylor choosers see it.  Without traces: the dict itself.  With traces: a copy without them whose offsets are, per member
+    and operator, the value of offsets[e, q] + traces[e, q, t] of largest magnitude over t -- the largest perturbation any slice of that member
+    runs."""
+    if not isinstance(robust, dict) or robust.get('traces') is None:
+        return robust
+    v = np.asarray(robust['offsets'], dtype=np.float64)[:, :, None] + np.asarray(robust['traces'], dtype=np.float64)
+    t = np.argmax(np.abs(v), axis=2)
+    out = {key: val for key, val in robust.items() if key != 'traces'}
+    out['offsets'] = np.take_along_axis(v, t[:, :, None], axis=2)[:, :, 0]
     return out
 
 
@@ -230,8 +262,10 @@ def member_collapse_ops(robust, e):
 
 
 def choose_taylor(H0, Hops, robust, maxA, U0, total_time, steps, unitary_error, state_transfer, no_scaling):
-    """(Taylor terms, squarings): the maximum over members of what SystemParameters' chooser picks for each member's problem."""
+    """(Taylor terms, squarings): the maximum over members of what SystemParameters' chooser picks for each member's problem.  With traces a
+    member's problem uses, per operator, the value of offsets + traces[t] of largest magnitude over t (taylor_view)."""
     from quantum_optimal_control.core.system_parameters import N_CANDIDATES, SystemParameters
+    robust = taylor_view(robust)
     best_t, best_s = 0, 0
     for e in range(robust['weights'].shape[0]):
         H0e, Hopse = member_hamiltonians(H0, Hops, robust, e)

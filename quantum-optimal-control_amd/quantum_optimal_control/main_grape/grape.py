@@ -170,7 +170,17 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     "stay out of everything above the computational subspace", a truncation guard on the top level.  ``level_cost`` with power 2 is what
     ``reg_coeffs['forbidden_coeff_list']`` is on a closed engine.  Needs an open engine: ``collapse_ops=`` (``[]`` is the closed limit), or a ``robust``
     dict or a ``fleet`` that carries ``collapse_ops``; it then works with whatever that call works with.  Anything else: ValueError, before the library
-    is loaded.  The gradient of the term is first order in dt, as the engine's is."""
+    is loaded.  The gradient of the term is first order in dt, as the engine's is.
+
+    Noise traces (time-dependent perturbations): a ``robust`` dict may carry the key ``traces`` (E x q x steps), a fleet ``traces`` (F x E x q x steps;
+    ``fleet.devices(..., traces=)``, ``fleet.around``): at slice t member e then has the drift H0 + sum_q (offsets[e, q] + traces[e, q, t]) P_q --
+    sampled noise trajectories whose correlation time is comparable to the gate (helper_functions.noise: ``ornstein_uhlenbeck``, ``one_over_f``,
+    ``colored``, and ``noise.ensemble`` for the dict), which neither a constant offset nor a collapse operator models.  The pulse is optimised for the
+    sample average (with ``risk``: the soft worst case) over this fixed set of traces; fresh draws during a run are an engine-level matter
+    (``HipEngine.set_traces`` between bursts of ``iterate``).  The number of slices is checked before the library is loaded; the Taylor order uses,
+    per member and operator, the value of offsets + traces[t] of largest magnitude over t; ``save=True`` logs ``robust_traces`` (``fleet_traces``).
+    Works with whatever the robust or fleet call works with: ``restarts``, ``transfer``, ``control_map``, ``exact_gradient``, risk, decay per member,
+    ``running_costs``, ``'Adam'``, ``'LBFGS'``, ``'EVOLVE'`` and, on a robust call, scipy's methods."""
     grape_start_time = time.time()
     time_unit = _TIME_UNITS[freq_unit]                  # KeyError on an unknown unit, as in the reference
     sparse = _is_sparse(H0, Hops)
@@ -233,7 +243,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
     if fleet is not None:
         from quantum_optimal_control.helper_functions import fleet as _fleet
         _given_fleet = fleet                           # (validate returns a normalised copy: the caller's object gets the results)
-        fleet = _fleet.validate(fleet, len(H0), n_pulses)
+        fleet = _fleet.validate(fleet, len(H0), n_pulses, steps=steps)
         if fleet_guess is not None and (fleet_guess.shape[0] != fleet.n_devices or fleet_guess.shape[1] != n_pulses):
             raise ValueError('Grape: a per-device initial guess of a fleet is (%d, %d, ...), got %s' % (fleet.n_devices, n_pulses, fleet_guess.shape))
     if str(method).upper() == 'LBFGS' and time_comm is not None:
@@ -244,7 +254,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         from quantum_optimal_control.helper_functions import robust as _robust
         if time_comm is not None:
             raise ValueError('Grape: robust ensembles cannot be time-sharded (time_comm)')
-        robust = _robust.validate(robust, len(H0), n_pulses)
+        robust = _robust.validate(robust, len(H0), n_pulses, steps=steps)
     decay_devices = None                               # decay per member: the validated member dicts, one per device
     if fleet is not None and fleet.has_decay:
         decay_devices, _who = [fleet.device(f) for f in range(fleet.n_devices)], 'a fleet with decay'
@@ -302,6 +312,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                     c = len(robust['collapse_ops'])
                     hf.add('robust_collapse_ops', data=np.array(robust['collapse_ops'], dtype=np.complex128).reshape(c, len(H0), len(H0)))
                     hf.add('robust_rate_scales', data=robust['rate_scales'])
+                if 'traces' in robust:
+                    hf.add('robust_traces', data=robust['traces'])
         if transfer is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -319,6 +331,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
                     c = len(fleet.collapse_ops)
                     hf.add('fleet_collapse_ops', data=np.array(fleet.collapse_ops, dtype=np.complex128).reshape(c, len(H0), len(H0)))
                     hf.add('fleet_rate_scales', data=fleet.rate_scales)
+                if fleet.traces is not None:
+                    hf.add('fleet_traces', data=fleet.traces)
         if collapse_ops is not None:
             from quantum_optimal_control.helper_functions.data_management import H5File
             with H5File(file_path) as hf:
@@ -345,7 +359,8 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
 
     if decay_devices is not None and Taylor_terms is None:
         # the largest degree and sub-step count that the Lindblad rule gives any member, with its own Hamiltonians and scaled collapse operators
-        Taylor_terms = _open.choose_taylor_members(H0, Hops, maxAmp, decay_devices, float(total_time) / steps, steps, unitary_error,
+        from quantum_optimal_control.helper_functions.robust import taylor_view as _taylor_view
+        Taylor_terms = _open.choose_taylor_members(H0, Hops, maxAmp, [_taylor_view(d) for d in decay_devices], float(total_time) / steps, steps, unitary_error,
                                                    control_map=control_map)
 
     if fleet is not None and Taylor_terms is None:
@@ -354,7 +369,7 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
 
     if control_map is not None and Taylor_terms is None:
         # the chooser on (H0, Hops, cmax): the largest coefficients the map can deliver stand where maxA stands (every member's, with a robust ensemble)
-        Taylor_terms = _cmap.choose_taylor(control_map, H0, Hops, robust, maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
+        Taylor_terms = _cmap.choose_taylor(control_map, H0, Hops, None if robust is None else _robust.taylor_view(robust), maxAmp, U0, total_time, steps, unitary_error, state_transfer, no_scaling)
 
     if robust is not None and Taylor_terms is None:
         # the largest Taylor order and squaring count any member's own problem would get (both only lower the truncation error)
@@ -440,6 +455,9 @@ def Grape(H0, Hops, Hnames, U, total_time, steps, states_concerned_list, converg
         if _restart_info is not None:
             # (a dict to fill: every control set's final scalars and variable, read before the engine goes -- examples/lbfgs_restarts.py)
             _restart_info.update(tfs.engine.scalars(), base=tfs.engine.get_base(), best=int(SS.seed))
+            if robust is not None:
+                # (a robust call: every member's loss at every control set's last evaluation, (restarts, E) -- examples/qubit_pi_pulse_under_noise.py)
+                _restart_info.update(member_losses=tfs.engine.member_scalars()['loss'])
             if running_costs:
                 # (with running costs: x_l,i(tau) of every control set's last evaluation, (restarts, steps + 1, L, m) -- examples/guarded_transmon_under_decay.py)
                 _restart_info.update(expectations=tfs.engine.get_expectations())
