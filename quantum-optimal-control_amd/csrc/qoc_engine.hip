@@ -2088,6 +2088,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 
 // What AUTO resolved to, as one line of key=value pairs (tests/test_auto_plan.py pins the dispatch table of DESIGN.md section 4 with it):
 // MFMA path:  path=mfma nt=<tiles> expm=<exponential kernel 1..8> chunks=<C> [expm=8: expm_hermitian=<0|1|2>: plain Horner chain | S S with copied accumulators | even/odd chain of symmetric products]
+// mem_policy=<0|1: plain accesses | the policy instances of k_mfma_expm_inplace / k_mfma_downup (qoc_mfma_frag.h, QocMem); same bits>
 // sweeps=<downup|split|row_tile_gradient|latency|latency_sources|one_wave>
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
@@ -2101,9 +2102,11 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
     if (!e || !buf || len < 1) return fail(QOC_ERR_INVALID, "qoc_plan_describe: null handle or buffer");
     char tmp[768];
     if (e->path == QOC_PATH_MFMA) {
-        const int w = snprintf(tmp, sizeof tmp, "path=mfma nt=%d expm=%d chunks=%d sweeps=%s", e->mf.NT, e->mp.expm_variant, e->mf.C, e->mp.sweeps);
+        int w = snprintf(tmp, sizeof tmp, "path=mfma nt=%d expm=%d chunks=%d sweeps=%s", e->mf.NT, e->mp.expm_variant, e->mf.C, e->mp.sweeps);
         // the in-place exponential kernel only: what it makes of exactly anti-Hermitian generators (Taylor order 5, 29 <= n <= 32; qoc_mfma_plan.h)
-        if (e->mp.expm_variant == 8) snprintf(tmp + w, sizeof tmp - w, " expm_hermitian=%d", e->mp.expm_hermitian);
+        if (e->mp.expm_variant == 8) w += snprintf(tmp + w, sizeof tmp - w, " expm_hermitian=%d", e->mp.expm_hermitian);
+        // how k_mfma_expm_inplace and k_mfma_downup request their K and X streams (QocMfmaPlan::mem_policy): 0 plain accesses, 1 the policy instances
+        snprintf(tmp + w, sizeof tmp - w, " mem_policy=%d", e->mp.mem_policy);
     } else if (e->path == QOC_PATH_GEMM) {
         const QocGemm& g = e->gm;
         const bool direct = g.route == QOC_GEMM_DIRECT;

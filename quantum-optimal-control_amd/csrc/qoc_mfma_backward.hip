@@ -10,7 +10,7 @@
 // The choice must not depend on the batch size: the gradient sums associate differently between the kernels, and a seed has
 // to evolve bit-identically whatever batch / GPU it is sharded into.  variant 1 keeps the one-wave 16x16x4 kernel (A/B).
 template <int NT>
-static const char* qoc_resolve_backward(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, bool split_grad) {
+static const char* qoc_resolve_backward(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d, bool split_grad, int mem_policy) {
     const unsigned items = d.B * mf.C, g4 = (items + 3) / 4, slices = d.B * d.steps;
     const bool src = d.n_forb > 0 || d.has_speed, fast = mf.variant != 1;
     const QocOneOf<2, 4> mq{mf.mq <= 2 ? 2 : 4};
@@ -33,7 +33,13 @@ static const char* qoc_resolve_backward(QocMfmaPlan& p, const QocMfma& mf, const
         }
         const char* msg = "MFMA path: cannot reserve LDS for the prefetching backward kernel";
         if (mf.updown) {                                                  // 4 items per workgroup, a wave per half chunk
-            qoc_pick([&](auto KC, auto QA) { p.sweep.set(k_mfma_downup<2, KC, QA>, g4, 512, mf.du_lds); }, kc, qa);
+            // the memory policy of the sweep (QOC_DOWNUP_*): POL = 1 instances exist for KC = 4 and only when a knob differs from plain accesses
+            const int pol = (qoc_downup_has_policy && d.k <= 4) ? mem_policy : 0;
+            p.mem_policy |= pol;
+            qoc_pick([&](auto KC, auto QA, auto POL) {
+                if constexpr (POL != 0 && (!qoc_downup_has_policy || KC != 4)) return;      // (never picked)
+                else p.sweep.set(k_mfma_downup<2, KC, QA, POL>, g4, 512, mf.du_lds);
+            }, kc, qa, QocOneOf<1, 0>{pol});
             msg = "MFMA path: cannot reserve LDS for the fused sweep kernel";
         } else if (mf.BndA) {                                             // 4 pairs of waves per workgroup
             qoc_pick([&](auto MQ, auto KC) { p.sweep.set(k_mfma_backward3<MQ, false, KC, 3>, g4, 512, mf.bwd_lds3); }, mq, kc);
@@ -231,11 +237,14 @@ int qoc_mfma_setup(QocMfma& mf, QocMfmaPlan& plan, const QocDev& d, int chunks_r
     // among the d.k + 1; the scaled copy HsD is the same entries times one real factor).  QOC_EXPERIMENTAL=1 QOC_EXPM_HERM=0: the plain Horner chain
     // (A/B runs), =2: the even/odd chain, whose results differ from the Horner chain's by rounding
     plan.expm_hermitian = !qoc_all_antihermitian(Hs_host, d.n, d.k + 1) || qoc_exp_is("QOC_EXPM_HERM", 0) ? 0 : (qoc_exp_is("QOC_EXPM_HERM", 2) ? 2 : 1);
+    // the memory policy of the two big kernels (qoc_mfma_frag.h, QocMem): 1 unless QOC_EXPERIMENTAL=1 QOC_MEM_POLICY=0 asks for the plain accesses
+    const int mem_policy = qoc_exp_is("QOC_MEM_POLICY", 0) ? 0 : 1;
+    plan.mem_policy = mem_policy;
     const char* err = qoc_mfma_resolve_expm(plan, mf, d);
     qoc_mfma_resolve_expm_inplace(plan, mf, d);
     qoc_mfma_resolve_forward(plan, mf, d);
     if (!err) err = qoc_mfma_resolve_latency(plan, mf, d);
-    if (!err && !lat_own) qoc_pick([&](auto NTc) { err = qoc_resolve_backward<NTc>(plan, mf, d, split_grad); }, QocOneOf<1, 2, 3, 4>{NT});
+    if (!err && !lat_own) qoc_pick([&](auto NTc) { err = qoc_resolve_backward<NTc>(plan, mf, d, split_grad, mem_policy); }, QocOneOf<1, 2, 3, 4>{NT});
     if (err) { msg = err; return -2; }
     return 0;
 }

@@ -51,6 +51,14 @@
 #define QOC_INPLACE_SWAP 0        // 1: the chunk product writes R' into the set the squarings vacated and the two sets swap ROLES for the next slice
                                   // (time loop unrolled by two) instead of copying R' back into R
 #endif
+#ifndef QOC_EXPM_KSTORE
+#define QOC_EXPM_KSTORE PLAIN     // PLAIN | NT | WT (QocMem, qoc_mfma_frag.h): how the instances with POL = 1 store the strips of K_t.  No later kernel reads K_t from the L2
+                                  // that wrote it; written through, no dirty line of it is left to write back at the kernel's end.  P_c / P_c^T stay plain stores (the
+                                  // boundary scan reads them next).  Same bits under every setting.  Measured at C2 x 64 (profiles/downup_cache_policy.txt): this kernel
+                                  // the same to a microsecond either way, the sweep behind it 5.5 us (WT) and 3 us (NT) shorter in one run and no shorter in the
+                                  // next, the scan 0.5 us: inside the run-to-run spread, so PLAIN stays and no POL = 1 instance is built.
+#endif
+constexpr bool qoc_expm_has_policy = QOC_MEM(QOC_EXPM_KSTORE) != QocMem::PLAIN;     // does POL = 1 differ from POL = 0?  (The resolver instantiates and picks it only then.)
 #ifndef QOC_LAP
 #define QOC_LAP(ph)
 #define QOC_LAP_INIT
@@ -223,6 +231,17 @@ __device__ __forceinline__ void product(cplx* img, double* imgs, int lane, Ring<
 __device__ __forceinline__ const cplx* frag_at(const cplx* F, int f) { return F + (f & ~3) * 64; }
 __device__ __forceinline__ cplx* frag_at(cplx* F, int f) { return F + (f & ~3) * 64; }
 
+// strip (J, ib) of K_t -> fragD(K_t) under the store policy of the instance
+template <QocMem POL, int NT, int ib>
+__device__ __forceinline__ void store_kstrip(cplx* Kout, int J, unsigned ulane, const cplx v) {
+    constexpr int QS = 4 * NT;
+    if constexpr (POL == QocMem::PLAIN) frag_at(Kout, J * QS + ib)[((J * QS + ib) & 3) * 64 + ulane] = v;
+    else for_each([&](auto Jc) {
+        constexpr int f = decltype(Jc)::value * QS + ib;
+        if (J == decltype(Jc)::value) qoc_st16_at<POL, (f & 3) * 64>(frag_at(Kout, f), ulane, v);
+    }, std::make_integer_sequence<int, NT>{});
+}
+
 }  // namespace qoc_inplace
 
 // KC = controls handled by the pipelined assembly (k <= KC; surplus controls carry a zero coefficient); EVEN = even Taylor order; S0 = no
@@ -243,10 +262,12 @@ __device__ __forceinline__ cplx* frag_at(cplx* F, int f) { return F + (f & ~3) *
 //       error of its value 1): strip ib of S2 is in SB, strip ib of Q is read from the image rows group ib
 //       has not released yet, one group ahead, and E enters through the accumulators' initial values.
 // The squarings then run on SA (S is dead after P3; SB stays free for the chunk product), everything behind them is unchanged.
-template <int KC, bool EVEN, bool S0, int QA = 8, int HERM = 0>
+// POL = the memory policy (QOC_EXPERIMENTAL=1 QOC_MEM_POLICY): 0 plain stores of K_t, 1 what QOC_EXPM_KSTORE says
+template <int KC, bool EVEN, bool S0, int QA = 8, int HERM = 0, int POL = 0>
 __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma mf) {
     using namespace qoc_inplace;
     constexpr int NT = 2, QS = 4 * NT;
+    constexpr QocMem KST = POL ? QOC_MEM(QOC_EXPM_KSTORE) : QocMem::PLAIN;
     static_assert(!HERM || (QA == 8 && !QOC_INPLACE_SWAP && (HERM == 1 || !EVEN)), "symmetric products: the full 32 x 32 problem; even/odd chain: Taylor order 5");
     __shared__ __attribute__((aligned(16))) cplx img[QNP * ILDS];
     __shared__ __attribute__((aligned(16))) double imgs[QNP * ILDS];
@@ -407,7 +428,7 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
                 if (ib >= 2 * NT && J == 0) { re = mir.x; im = mir.y; su = re + im; }
                 else combine(a[J], bq[J], cq[J], re, im, su);
                 ori[J] = cmake(re, im); osu[J] = su;
-                if constexpr (S0) frag_at(Kout, J * QS + ib)[((J * QS + ib) & 3) * 64 + ulane] = ori[J];
+                if constexpr (S0) store_kstrip<KST, NT, ib>(Kout, J, ulane, ori[J]);
                 if (ib < 2 * NT && J == 1) side_store(ib, fma(2.0, Er, -re), fma(-2.0, Es - Er, im));      // conjugate of 2 E - K0
             }
         }, side);
@@ -455,7 +476,7 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
                     double re, im, su;
                     combine(a[J], bq[J], cq[J], re, im, su);
                     ori[J] = cmake(re, im); osu[J] = su;
-                    if constexpr (S0) { if (i == 0) frag_at(Kout, J * QS + ib)[((J * QS + ib) & 3) * 64 + ulane] = ori[J]; }
+                    if constexpr (S0) { if (i == 0) store_kstrip<KST, NT, ib>(Kout, J, ulane, ori[J]); }
                 }
             };
             if (i > 0) product<NT, QA, false, false, false>(img, imgs, lane, ring, SB, init, epi);
@@ -474,7 +495,7 @@ __global__ void __launch_bounds__(64, 1) k_mfma_expm_inplace(QocDev d, QocMfma m
                     double re, im, su;
                     combine(a[J], bq[J], cq[J], re, im, su);
                     ori[J] = cmake(re, im); osu[J] = su;
-                    if (kout) frag_at(Kout, J * QS + ib)[((J * QS + ib) & 3) * 64 + ulane] = ori[J];      // K_t, strip (J, ib)
+                    if (kout) store_kstrip<KST, NT, ib>(Kout, J, ulane, ori[J]);      // K_t, strip (J, ib)
                 }
             });
         }

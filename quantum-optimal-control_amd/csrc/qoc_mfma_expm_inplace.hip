@@ -11,9 +11,14 @@
 void qoc_mfma_resolve_expm_inplace(QocMfmaPlan& p, const QocMfma& mf, const QocDev& d) {
     const int herm = (p.expm_variant == 8 && d.T == 5 && qoc_active_strips(d.n) == 8) ? p.expm_hermitian : 0;
     p.expm_hermitian = herm;
+    // p.mem_policy on entry: the request; the POL = 1 instances (the K_t stores under QOC_EXPM_KSTORE) exist for KC = 4 and only when the knob is not PLAIN
+    const int pol = (p.expm_variant == 8 && qoc_expm_has_policy && d.k <= 4) ? p.mem_policy : 0;
+    p.mem_policy = pol;                                                   // (the sweep's resolver adds its own)
     if (p.expm_variant != 8) return;
-    qoc_pick([&](auto KC, auto EVEN, auto S0, auto QA, auto HERM) {
+    qoc_pick([&](auto KC, auto EVEN, auto S0, auto QA, auto HERM, auto POL) {
         if constexpr (HERM != 0 && (EVEN != 0 || QA != 8)) return;        // (never picked: herm implies order 5 and QA = 8)
-        else p.expm.set(k_mfma_expm_inplace<KC, EVEN != 0, S0 != 0, QA, HERM>, d.B * mf.C, 64);
-    }, QocOneOf<4, 8>{d.k <= 4 ? 4 : 8}, QocOneOf<1, 0>{(d.T & 1) == 0}, QocOneOf<1, 0>{d.s == 0}, QocOneOf<8, 7, 6, 5>{qoc_active_strips(d.n)}, QocOneOf<1, 2, 0>{herm});
+        else if constexpr (POL != 0 && (!qoc_expm_has_policy || KC != 4)) return;      // (never picked)
+        else p.expm.set(k_mfma_expm_inplace<KC, EVEN != 0, S0 != 0, QA, HERM, POL>, d.B * mf.C, 64);
+    }, QocOneOf<4, 8>{d.k <= 4 ? 4 : 8}, QocOneOf<1, 0>{(d.T & 1) == 0}, QocOneOf<1, 0>{d.s == 0}, QocOneOf<8, 7, 6, 5>{qoc_active_strips(d.n)}, QocOneOf<1, 2, 0>{herm},
+       QocOneOf<1, 0>{pol});
 }

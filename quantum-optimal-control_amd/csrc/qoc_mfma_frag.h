@@ -88,6 +88,40 @@ __device__ __forceinline__ size_t kitem(const QocMfma& mf, int steps, int b, int
     return (size_t)b * ((size_t)steps * mf.FR + (size_t)mf.C * mf.skew_c + mf.skew_b) + (size_t)t * mf.FR + (size_t)(t / mf.L) * mf.skew_c;
 }
 
+// ---- policy-tagged 16-byte accesses ---------------------------------------------------------------------------------
+// How one cplx per lane is requested from the memory system; the value is the same whichever policy moves it.
+//   PLAIN  global_load / global_store_dwordx4
+//   NT     ... nt: loads are served from L2 without allocating in the CU's L1, stores are marked streaming (the line still stays in the XCD's L2)
+//   WT     stores only: ... sc0 sc1, written through -- the line does not stay dirty in the XCD's L2 (nothing is left to write back at the kernel's end)
+// The -D knobs of the kernels name a policy by its word (-DQOC_DOWNUP_KA=NT): QOC_MEM(knob) is the enumerator.
+enum class QocMem { PLAIN, NT, WT };
+#define QOC_MEM_(x) QocMem::x
+#define QOC_MEM(x) QOC_MEM_(x)
+typedef double qoc_d2 __attribute__((ext_vector_type(2)));
+template <QocMem POL>
+__device__ __forceinline__ cplx qoc_ld16(const cplx* p) {
+    static_assert(POL != QocMem::WT, "write-through is a store policy");
+    if constexpr (POL == QocMem::NT) { const qoc_d2 v = __builtin_nontemporal_load((const qoc_d2*)p); return cmake(v.x, v.y); }
+    else return *p;
+}
+template <QocMem POL>
+__device__ __forceinline__ void qoc_st16(cplx* p, const cplx v) {
+    if constexpr (POL == QocMem::NT) __builtin_nontemporal_store((qoc_d2){v.x, v.y}, (qoc_d2*)p);
+    else if constexpr (POL == QocMem::WT) {
+        // (no builtin stores write-through through a global pointer; the nops: the store reads its four data registers after issue)
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"((qoc_d2){v.x, v.y}) : "memory");
+    } else *p = v;
+}
+// the same store at base[IMM + lane], base wave-uniform, IMM < 256 elements (4 KB): scalar base + immediate + 32-bit lane offset, no per-lane 64-bit address is formed
+template <QocMem POL, int IMM>
+__device__ __forceinline__ void qoc_st16_at(cplx* base, unsigned lane, const cplx v) {
+    static_assert(IMM >= 0 && IMM < 256, "13-bit signed immediate of the global instructions");
+    if constexpr (POL == QocMem::WT) {
+        // (the opening nops: a scalar base the compiler has just formed is read by the store)
+        asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3 sc0 sc1\n\ts_nop 1" :: "v"(lane * 16u), "v"((qoc_d2){v.x, v.y}), "s"(base), "n"(IMM * 16) : "memory");
+    } else qoc_st16<POL>(base + (IMM + lane), v);
+}
+
 // ---- fragment helpers ---------------------------------------------------------------------------------------------
 
 // A-operand fragments from a fragD matrix (pass fragD(M^T) to multiply by M, fragD(M) with CONJ to multiply by M^dagger)

@@ -64,5 +64,8 @@ struct QocMfmaPlan {
     int expm_hermitian = 0;            // in: 0, or with every Hamiltonian image exactly anti-Hermitian (qoc_mfma_setup) 1 / 2 (QOC_EXPM_HERM=2); out: what
                                        // k_mfma_expm_inplace runs (qoc_mfma_resolve_expm_inplace) -- 1: S S with copied accumulators, bit-identical to 0;
                                        // 2: the even/odd chain of symmetric products; qoc_plan_describe: expm_hermitian=<0|1|2>
+    int mem_policy = 0;                // in: 1, or 0 with QOC_EXPERIMENTAL=1 QOC_MEM_POLICY=0 (qoc_mfma_setup); out: 1 when a kernel of the iteration runs its POL = 1
+                                       // instance (k_mfma_expm_inplace: QOC_EXPM_KSTORE, k_mfma_downup: QOC_DOWNUP_*; built for k <= 4 only), else 0 -- plain
+                                       // accesses.  Same bits either way; qoc_plan_describe: mem_policy=<0|1>
     const char* expm_name = "";        // qoc_profile_read
 };
