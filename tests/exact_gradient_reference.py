@@ -8,9 +8,7 @@ reports, truncation included ("Exact gradient").
 
 Psi_t enters slice t (Psi_0 = U0 V; the oracle's inter_vecs[0] holds V), Lambda_{t+1} is the costate of the oracle's own backward recursion (forbidden
 levels and speed_up sources included).  Regularisers and the chain rule cos(base) (maxA dL_du + dR/dw) are the oracle's.  The composed versions
-for an ensemble and for a pulse response follow tests/test_robust_gpu.py and tests/test_transfer_gpu.py with this gradient in the oracle's place."""
-from types import SimpleNamespace
-
+for an ensemble and for a pulse response are tests/robust_reference.py: composed / composed_shaped with this `evaluate` in the oracle's place."""
 import numpy as np
 
 from oracle import grape_oracle as go
@@ -86,30 +84,6 @@ def central_differences(sp, base, h=1e-6):
         bm[idx] -= h
         g[idx] = (go.evaluate(sp, bp, want_grad=False)['reg_loss'] - go.evaluate(sp, bm, want_grad=False)['reg_loss']) / (2 * h)
     return g
-
-
-def composed_ensemble(sps, w, base):
-    """tests/test_robust_gpu.py: composed, with every member's exact gradient: the weighted sums over the member systems."""
-    rs = [evaluate(sp, base) for sp in sps]
-    grad = sum(wi * r['grad'] for wi, r in zip(w, rs))
-    return dict(loss=sum(wi * r['loss'] for wi, r in zip(w, rs)), reg_loss=sum(wi * r['reg_loss'] for wi, r in zip(w, rs)),
-                unitary_scale=sum(wi * r['unitary_scale'] for wi, r in zip(w, rs)), grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)))
-
-
-def composed_response(sps, w, T, theta, pulse_rc, total_time):
-    """tests/test_transfer_gpu.py: composed, with the exact dL_du: T^T applied to the members' weighted dL_du, then the sample view's chain rule.
-    sps carry the state regularisers only; the pulse regularisers act on the samples."""
-    k, Pn = theta.shape
-    ws = np.sin(theta)
-    wf = ws @ T.T
-    rs = [evaluate(sp, np.arcsin(wf)) for sp in sps]
-    view = SimpleNamespace(reg_coeffs=pulse_rc, steps=Pn, dt=total_time / Pn, k=k, total_time=total_time, use_gpu=True, one_minus_gauss=None)
-    val, dR = go.pulse_regularisers(view, ws)
-    maxA = sps[0].maxA
-    dLdu = sum(wi * r['dL_du'] for wi, r in zip(w, rs))
-    grad = np.cos(theta) * (maxA[:, None] * (dLdu @ T) + dR)
-    return dict(loss=sum(wi * r['loss'] for wi, r in zip(w, rs)), reg_loss=sum(wi * r['reg_loss'] for wi, r in zip(w, rs)) + val,
-                unitary_scale=sum(wi * r['unitary_scale'] for wi, r in zip(w, rs)), grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)))
 
 
 # ---- the rows of the issue's table (recipes of tests/test_hip_parity.py: parity_cases unless spelled out) ---------------------------------

@@ -2,21 +2,21 @@
 
 Control set g of a fleet with R control sets per device belongs to device g // R, and every quantity of it is what the ensemble engine defines for an
 ensemble with that device's rows.  So device f's expectation is the expectation of ONE ensemble -- Fleet.device(f) -- from the modules that already
-compose it from the unchanged oracle: tests/test_robust_gpu.py (composed: the weighted mean of the members' oracle evaluations) and
+compose it from the unchanged oracle: tests/robust_reference.py (composed: the weighted mean of the members' oracle evaluations) and
 tests/control_map_reference.py (evaluate: the same with a line, a control map, a risk and the exact gradient).  Nothing is computed here."""
 import numpy as np
 
 from quantum_optimal_control.helper_functions import fleet as fl_mod
 from quantum_optimal_control.helper_functions.synthetic_systems import herm
 from tests import control_map_reference as ref
-from tests import test_robust_gpu as rg
+from tests import robust_reference as rr
 
 REGS_UNITARY = {'dwdt': 0.1, 'amplitude': 0.2}
 REGS_STATE = {'dwdt': 0.1, 'forbidden_coeff_list': [5.0], 'states_forbidden_list': [4], 'speed_up': 0.3}
 
 
 def problem(kind, n=None, k=2, r=None, steps=None, m=None, regs=None, seed=0):
-    """tests/control_map_reference.py: problem, with the keys tests/test_robust_gpu.py: member_systems reads.  unitary: n = 4, steps = 8, m = 3;
+    """tests/control_map_reference.py: problem, with the keys tests/robust_reference.py: member_systems reads.  unitary: n = 4, steps = 8, m = 3;
     state: n = 5, m = 2, steps = 7, a forbidden level and speed_up."""
     st = kind == 'state'
     n, steps, m = n or (5 if st else 4), steps or (7 if st else 8), m or (2 if st else 3)
@@ -42,13 +42,13 @@ def device(fl, f):
 
 
 def member_systems(c, fl, f):
-    """tests/test_robust_gpu.py: member_systems of device f, with the problem's (T, s)."""
-    return rg.member_systems(c, device(fl, f), c['Taylor_terms'])
+    """tests/robust_reference.py: member_systems of device f, with the problem's (T, s)."""
+    return rr.member_systems(c, device(fl, f), c['Taylor_terms'])
 
 
 def composed(c, fl, f, base):
-    """tests/test_robust_gpu.py: composed, with device f's rows."""
-    return rg.composed(member_systems(c, fl, f), fl.weights, base)
+    """tests/robust_reference.py: composed, with device f's rows."""
+    return rr.composed(member_systems(c, fl, f), fl.weights, base)
 
 
 def evaluate(c, cm, fl, f, x, T=None, exact=False):

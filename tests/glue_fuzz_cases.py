@@ -27,6 +27,7 @@ from quantum_optimal_control.helper_functions import robust as rb
 from quantum_optimal_control.helper_functions import transfer as tf
 from quantum_optimal_control.helper_functions.synthetic_systems import herm
 from tests import control_map_reference as ref
+from tests.composed_reference import pulse_view, run_adam
 
 CLOSED_SEEDS, OPEN_SEEDS, SPARSE_SEEDS = 96, 32, 32
 CLOSED_N = (2, 5, 12, 13, 16, 17, 24, 31, 32, 33, 40, 47, 48, 49, 63, 64, 65, 70)
@@ -116,32 +117,8 @@ def draw_map(rng, k, r, steps, seed):
 
 
 def envelope_constant(k, width):
-    """one_minus_gauss as the references form it for `width` slices (tests/control_map_reference.py: evaluate)."""
-    grid = np.linspace(-2, 2, width)
-    shape = np.ones(width) - np.exp(-np.power(grid, 2.) / 2.)
-    return np.tile(shape * (shape > 0) + 0.01 * np.ones(width), (k, 1))
-
-
-class recorded(object):
-    """Inside the block every call of `module.trajectory` leaves its unitary_scale in `.scales`: the members' own figures, which the composed
-    references only return as their weighted sum."""
-
-    def __init__(self, module):
-        self.module, self.scales = module, []
-
-    def __enter__(self):
-        self.real = self.module.trajectory
-
-        def trajectory(*args, **kw):
-            r = self.real(*args, **kw)
-            self.scales.append(float(r['unitary_scale']))
-            return r
-        self.module.trajectory = trajectory
-        return self
-
-    def __exit__(self, *exc):
-        self.module.trajectory = self.real
-        return False
+    """one_minus_gauss as the references form it for `width` slices (tests/composed_reference.py: pulse_view)."""
+    return pulse_view(k, width, 1.0, {'envelope': 1.0}).one_minus_gauss
 
 
 class Draw(SimpleNamespace):
@@ -365,34 +342,24 @@ FAMILIES = {'closed': (closed, CLOSED_SEEDS), 'open': (opened, OPEN_SEEDS), 'spa
 _EVALUATE = {'closed': _closed_at, 'open': _open_at, 'sparse': _sparse_at}
 
 
-def _reference_module(family):
-    if family == 'closed':
-        return ref
-    if family == 'open':
-        from tests import open_fleet_reference as ofr
-        return ofr
-    from tests import sparse_ensemble_reference as ser
-    return ser
-
-
 @functools.lru_cache(maxsize=None)
 def _expected(family, seed):
-    """The reference of every control set at its start point, with member_unitary_scale: computed once, shared by every test and engine."""
+    """The reference of every control set at its start point, with member_unitary_scale (the members' own figures, which the composed references
+    return only as their weighted sum) in place of the members' trajectories: computed once, shared by every test and engine."""
     d = FAMILIES[family][0](seed)
     out = []
     for g in range(d.G):
-        with recorded(_reference_module(family)) as rec:
-            o = d.evaluate_at(g, d.xs[g])
-        o['member_unitary_scale'] = np.array(rec.scales)
+        o = d.evaluate_at(g, d.xs[g])
+        o['member_unitary_scale'] = np.array([float(r['unitary_scale']) for r in o.pop('members')])
         out.append(o)
     return out
 
 
 @functools.lru_cache(maxsize=None)
 def _adam_reference(family, seed, g):
-    """Four iterations of the device loop's semantics from control set g's start point (control_map_reference.run_adam): dict(base, loss, reg_loss)."""
+    """Four iterations of the device loop's semantics from control set g's start point (composed_reference.run_adam): dict(base, loss, reg_loss, ..)."""
     d = FAMILIES[family][0](seed)
-    return ref.run_adam(lambda x: d.evaluate_at(g, x), d.xs[g], ADAM)
+    return run_adam(lambda x: d.evaluate_at(g, x), d.xs[g], ADAM)
 
 
 # ---- which kernel family takes a closed draw --------------------------------------------------------------------------------------------------------

@@ -7,9 +7,12 @@ With H' = -i dt H (sp.Hs) and D_j = sqrt(dt) C_j:
     L_t(X) = A_t X + X A_t^dagger + sum_j D_j X D_j^dagger,    L_t^dagger(Y) = A_t^dagger Y + Y A_t + sum_j D_j^dagger Y D_j
 Slice map: N = 2^s sub-steps of X <- sum_{j = 0 .. T} (L_t / N)^j X / j! (chain X_j = (L_t / N) X_{j-1}, ascending sums), T = sp.exp_terms and
 s = sp.scaling in BOTH modes."""
+import math
+
 import numpy as np
 
 from oracle import grape_oracle as go
+from tests.composed_reference import run_adam as loop
 
 
 def scaled_ops(sp, collapse_ops):
@@ -128,17 +131,16 @@ def liouvillian(A, Ds):
 def run_adam(sp, collapse_ops, convergence, base):
     """The run_session loop (oracle.grape_oracle.run_adam) over this reference: dict(base, iterations, last (the evaluation that ended the loop),
     uks, history (one row (loss, reg_loss, grad_squared, unitary_scale) per evaluation))."""
-    conv = dict(go.CONVERGENCE_DEFAULTS)
-    conv.update(convergence)
-    base = np.array(base, dtype=np.float64)
-    opt = go.Adam(base.shape)
-    iterations = 0
-    hist = []
-    while True:
-        r = evaluate(sp, collapse_ops, base)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared'], r['unitary_scale']))
-        if (r['loss'] < conv['conv_target']) or (r['grad_squared'] < conv['min_grad']) or (iterations >= conv['max_iterations']):
-            break
-        iterations += 1
-        base = opt.step(base, r['grad'], float(conv['rate']) * np.exp(-float(iterations) / conv['learning_rate_decay']))
-    return dict(base=base, iterations=iterations, last=r, uks=sp.maxA[:, None] * np.sin(base), history=np.array(hist))
+    out = loop(lambda b: evaluate(sp, collapse_ops, b), base, dict(go.CONVERGENCE_DEFAULTS, **convergence))
+    return dict(out, uks=sp.maxA[:, None] * np.sin(out['base']))
+
+
+def collapse_list(n, c, seed):
+    """c collapse operators of spectral norm sqrt(rate): a lowering operator, a number operator, then random complex matrices."""
+    rng = np.random.default_rng(1000 + seed)
+    a = np.diag(np.sqrt(np.arange(1, n)), 1).astype(complex)
+    pool = [a, a.conj().T @ a]
+    while len(pool) < c:
+        pool.append(rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n)))
+    rates = [0.30, 0.20, 0.15, 0.10, 0.12, 0.08, 0.05, 0.04]
+    return [math.sqrt(rates[j]) * pool[j] / np.linalg.norm(pool[j], 2) for j in range(c)]

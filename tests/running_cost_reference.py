@@ -8,16 +8,14 @@ tests/lindblad_reference.py (generator, slice_map, propagate, loss_of), over all
 A cost is a record (O, a, p), as helper_functions/open_system.py builds them.  Also here: the Adam loop over this evaluation, and the composition of
 members into a control set (the weighted mean, the soft worst case of include/qoc.h with the members' costs c_e = loss_e + R_e, the line, the map) as
 tests/open_fleet_reference.py composes members without costs."""
-from types import SimpleNamespace
-
 import numpy as np
 
 from oracle import grape_oracle as go
-from quantum_optimal_control.helper_functions import control_map as cmap
 from quantum_optimal_control.helper_functions import robust as rb
-from tests import control_map_reference as ref
 from tests import lindblad_reference as lr
 from tests import open_fleet_reference as ofr
+from tests.composed_reference import at_coefficients, combine, split_regs
+from tests.composed_reference import run_adam as loop
 
 
 def expectations(costs, hist):
@@ -96,70 +94,22 @@ def continue_from(sp, collapse_ops, costs, u, hist, tau):
 
 def run_adam(sp, collapse_ops, costs, convergence, base):
     """lindblad_reference.run_adam over this evaluation (the stop rule reads the loss, the step follows the gradient of reg_loss)."""
-    conv = dict(go.CONVERGENCE_DEFAULTS)
-    conv.update(convergence)
-    base = np.array(base, dtype=np.float64)
-    opt = go.Adam(base.shape)
-    iterations = 0
-    hist = []
-    while True:
-        r = evaluate(sp, collapse_ops, costs, base)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared'], r['unitary_scale']))
-        if (r['loss'] < conv['conv_target']) or (r['grad_squared'] < conv['min_grad']) or (iterations >= conv['max_iterations']):
-            break
-        iterations += 1
-        base = opt.step(base, r['grad'], float(conv['rate']) * np.exp(-float(iterations) / conv['learning_rate_decay']))
-    return dict(base=base, iterations=iterations, last=r, uks=sp.maxA[:, None] * np.sin(base), history=np.array(hist))
+    out = loop(lambda b: evaluate(sp, collapse_ops, costs, b), base, dict(go.CONVERGENCE_DEFAULTS, **convergence))
+    return dict(out, uks=sp.maxA[:, None] * np.sin(out['base']))
 
 
 def trajectory(p, H0e, coeff, ops, costs, want_grad=True):
     """tests/open_fleet_reference.py: trajectory with the running costs: evaluate at the coefficients coeff (r x steps), dL_du = d(loss + R)/dc."""
-    S = 2.0 * np.max(np.abs(coeff), axis=1)
-    S[S == 0.0] = 1.0
-    return evaluate(ofr.member_system(p, H0e, S), ops, costs, np.arcsin(coeff / S[:, None]), want_grad=want_grad)
+    S, base = at_coefficients(coeff)
+    return evaluate(ofr.member_system(p, H0e, S), ops, costs, base, want_grad=want_grad)
 
 
 def evaluate_members(p, cm, ens, costs, x, T=None, beta=None, want_grad=True):
     """tests/open_fleet_reference.py: evaluate with the running costs.  The members' R_e are their state regularisers: with the weights w (sum 1) the
     control set has reg_state = sum_e w_e R_e and reg_loss = sum_e w_e (loss_e + R_e) + the pulse regularisers; under a risk beta > 0 the members'
     costs are c_e = loss_e + R_e, J and the tilted weights pi_e those of include/qoc.h, reg_state = sum_e pi_e R_e, loss = J - reg_state and
-    reg_loss = J + the pulse regularisers.  Adds member_reg_state (E,), reg_state and expectations (member 0) to that function's dict."""
-    maxA = np.asarray(p['maxA'], dtype=np.float64)
-    k = len(maxA)
-    x = np.asarray(x, dtype=np.float64).reshape(k, -1)
-    beta = float(ens.get('risk', 0.0)) if beta is None else float(beta)
-    _, pulse_rc = ref.split_regs(p['reg_coeffs'])
-    ws = np.sin(x)
-    wf = ws if T is None else ws @ T.T
-    u = maxA[:, None] * wf
-    w = np.asarray(ens['weights'], dtype=np.float64)
-    E = len(w)
-    rs, vs = [], []
-    for e in range(E):
-        H0e, _ = rb.member_hamiltonians(p['H0'], [], ens, e)
-        v = ens['amp_scales'][e][:, None] * u
-        vs.append(v)
-        rs.append(trajectory(p, H0e, v if cm is None else cmap.apply(cm, v), rb.member_collapse_ops(ens, e), costs, want_grad))
-    loss_e = np.array([r['loss'] for r in rs])
-    state_e = np.array([r['reg_state'] for r in rs])
-    Pn = x.shape[1]
-    view = SimpleNamespace(reg_coeffs=pulse_rc, steps=Pn, dt=p['total_time'] / Pn, k=k, total_time=p['total_time'], use_gpu=True, one_minus_gauss=None)
-    val, dR = go.pulse_regularisers(view, ws)
-    if beta > 0 and E > 1:
-        J, pi = ref.tilt(loss_e + state_e, w, beta)
-        reg_state = float(np.sum(pi * state_e))
-        loss, reg_loss = J - reg_state, J + val
-    else:
-        pi = w
-        reg_state = float(np.sum(w * state_e))
-        loss, reg_loss = float(np.sum(w * loss_e)), float(np.sum(w * (loss_e + state_e))) + val
-    out = dict(loss=float(loss), reg_loss=float(reg_loss), reg_state=reg_state, unitary_scale=float(np.sum(w * np.array([r['unitary_scale'] for r in rs]))),
-               member_loss=loss_e, member_reg_state=state_e, weights=pi, pulse=u, uks=maxA[:, None] * ws, rho_final=rs[0]['rho_final'],
-               populations=rs[0]['populations'], expectations=rs[0]['expectations'], member_rho=np.stack([r['rho_final'] for r in rs]))
-    if not want_grad:
-        return out
-    back = (lambda v, g: g) if cm is None else (lambda v, g: cmap.pullback(cm, v, g))
-    dJdu = sum(pi[e] * ens['amp_scales'][e][:, None] * back(vs[e], rs[e]['dL_du']) for e in range(E))
-    grad = np.cos(x) * (maxA[:, None] * (dJdu if T is None else dJdu @ T) + dR)
-    out.update(grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)))
+    reg_loss = J + the pulse regularisers (tests/composed_reference.py: combine).  Adds expectations (member 0) to that function's read-backs."""
+    run = lambda e, coeff: trajectory(p, rb.member_hamiltonians(p['H0'], [], ens, e)[0], coeff, rb.member_collapse_ops(ens, e), costs, want_grad)
+    out = ofr.read_backs(combine(x, p['maxA'], ens, p['total_time'], split_regs(p['reg_coeffs'])[1], run, cm=cm, T=T, beta=beta, want_grad=want_grad))
+    out['expectations'] = out['members'][0]['expectations']
     return out

@@ -264,13 +264,7 @@ def test_adam_loop_matches_a_python_loop_over_the_reference():
     conv = dict(rate=0.05, learning_rate_decay=50, conv_target=-1.0, min_grad=-1.0, max_iterations=10)
 
     def python_loop(x0, conv):
-        hist = []
-
-        def at(x):
-            r = ref.evaluate(c, cm, ens, x, T=T)
-            hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-            return r
-        return dict(ref.run_adam(at, x0, conv), history=np.array(hist))
+        return ref.run_adam(lambda x: ref.evaluate(c, cm, ens, x, T=T), x0, conv)
 
     free = [python_loop(x, conv) for x in xs]
     target, stops = _choose_target([f['history'] for f in free], 10)

@@ -17,6 +17,7 @@ from quantum_optimal_control.helper_functions import transfer as tf
 from tests import exact_gradient_reference as xr
 from tests.golden import cases
 from tests.helpers import oracle_system
+from tests.robust_reference import composed, composed_shaped
 from tests.test_adam_tail import LOOP_ATOL
 from tests.test_hip_parity import G_RTOL, S_RTOL, check_eval
 from tests.test_robust_gpu import ensemble, member_systems, nominal_system
@@ -194,7 +195,7 @@ def test_composes_with_an_ensemble(name):
         eng.set_base(np.stack(bases))
         r = eng.evaluate()
         for g, b in enumerate(bases):
-            o = xr.composed_ensemble(sps, ens['weights'], b)
+            o = composed(sps, ens['weights'], b, evaluate=xr.evaluate)
             for key in ('loss', 'reg_loss', 'unitary_scale', 'grad_squared'):
                 assert_scalar('%s %s[%d]' % (name, key, g), r[key][g], o[key])
             assert_gradient('%s ensemble grad[%d]' % (name, g), r['grad'][g], o['grad'])
@@ -218,7 +219,7 @@ def test_composes_with_a_response(name, kind, with_ensemble):
         eng.set_base(thetas)
         r = eng.evaluate()
         for g in range(2):
-            o = xr.composed_response(sps, w, T, thetas[g], pulse_rc, nominal.total_time)
+            o = composed_shaped(sps, w, T, thetas[g], pulse_rc, nominal.total_time, evaluate=xr.evaluate)
             for key in ('loss', 'reg_loss', 'unitary_scale', 'grad_squared'):
                 assert_scalar('%s %s[%d]' % (name, key, g), r[key][g], o[key])
             assert_gradient('%s %s grad[%d]' % (name, kind, g), r['grad'][g], o['grad'])

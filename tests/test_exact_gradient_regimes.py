@@ -19,9 +19,9 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import grape_oracle as go
 from quantum_optimal_control.core import hip_engine
 from tests import exact_gradient_reference as xr
+from tests.composed_reference import run_adam
 from tests.golden import cases
 from tests.helpers import oracle_system
 from tests.test_adam_tail import LOOP_ATOL, _choose_target
@@ -137,14 +137,7 @@ def test_state_transfer_past_the_degree_limit_is_refused():
 
 def python_loop(sp, base, conv):
     """tests/test_transfer_gpu.py: python_loop with the reference's exact gradient: go.Adam, run_adam's stop rule and learning-rate schedule."""
-    opt, it, hist = go.Adam(base.shape), 0, []
-    while True:
-        r = xr.evaluate(sp, base)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-        if r['loss'] < conv['conv_target'] or r['grad_squared'] < conv['min_grad'] or it >= conv['max_iterations']:
-            return dict(base=base, iterations=it, history=np.array(hist), r=r)
-        it += 1
-        base = opt.step(base, r['grad'], conv['rate'] * np.exp(-float(it) / conv['learning_rate_decay']))
+    return run_adam(lambda b: xr.evaluate(sp, b), base, conv)
 
 
 @pytest.mark.parametrize('name', ['n4_allreg', 'state_small'])
@@ -171,7 +164,7 @@ def test_device_loop_with_unequal_stops(name):
         for g, ref in enumerate(refs):
             print('%s set %d: max |base - reference| %.3e' % (name, g, np.max(np.abs(base[g] - ref['base']))))
             np.testing.assert_allclose(base[g], ref['base'], rtol=0, atol=LOOP_ATOL)
-            o = ref['r']                                                       # the reference at this set's own final base
+            o = ref['last']                                                       # the reference at this set's own final base
             for key in ('loss', 'reg_loss', 'grad_squared', 'unitary_scale'):
                 assert abs(s[key][g] - o[key]) <= LOOP_ATOL * max(1.0, abs(o[key])), (key, g, s[key][g], o[key])
             np.testing.assert_allclose(inter[g], o['inter_vecs'], rtol=0, atol=LOOP_ATOL * max(1.0, np.max(np.abs(o['inter_vecs']))))

@@ -158,16 +158,9 @@ def glue_adapter(name):
         return ref.evaluate(c, ref_map, members[b], x, T=T, exact=g['exact'], beta=g['beta'])
 
     def loop(conv, x0, b):
-        hist = []
-
-        def at(x):
-            r = evaluate(x, b)
-            hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-            at.last = r
-            return r
-        run = ref.run_adam(at, x0, conv)
-        return dict(base=run['base'], iterations=run['iterations'], history=np.array(hist), vectors=dict(base=run['base']),
-                    scalars={key: at.last[key] for key in SCALARS})
+        run = ref.run_adam(lambda x: evaluate(x, b), x0, conv)
+        return dict(base=run['base'], iterations=run['iterations'], history=run['history'], vectors=dict(base=run['base']),
+                    scalars={key: run['last'][key] for key in SCALARS})
 
     def at_base(base, b):
         o = evaluate(base, b)
@@ -218,7 +211,7 @@ def family_adapter(name):
         _, ens, _, sps = parts()
         run = python_loop(sps, ens['weights'], x0, conv)
         return dict(base=run['base'], iterations=run['iterations'], history=run['history'], vectors=dict(base=run['base']),
-                    scalars={key: run['r'][key] for key in SCALARS})
+                    scalars={key: run['last'][key] for key in SCALARS})
 
     def at(base, b):
         c, ens, nominal, sps = parts()

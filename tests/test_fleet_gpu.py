@@ -264,7 +264,7 @@ def test_adam_loop_with_devices_that_finish_at_different_iterations():
         for f, run in enumerate(refs):
             assert np.max(np.abs(base[f] - run['base'])) < 1e-9, (f, np.max(np.abs(base[f] - run['base'])))
             for key in KEYS:
-                assert abs(s[key][f] - run['r'][key]) < 1e-10 * max(1.0, abs(run['r'][key])), (key, f, s[key][f], run['r'][key])
+                assert abs(s[key][f] - run['last'][key]) < 1e-10 * max(1.0, abs(run['last'][key])), (key, f, s[key][f], run['last'][key])
             o = fr.composed(c, fl, f, base[f])
             for key in KEYS:
                 assert abs(s[key][f] - o[key]) <= TIGHT['s'] * max(1.0, abs(o[key])), (key, f, s[key][f], o[key])

@@ -15,23 +15,13 @@ from quantum_optimal_control.helper_functions import open_system
 from quantum_optimal_control.helper_functions.synthetic_systems import herm, random_unitary
 from quantum_optimal_control.main_grape.grape import Grape, GrapeSharded, GrapeTimeSharded
 from tests import lindblad_reference as lr
+from tests.lindblad_reference import collapse_list
 
 G_RTOL = 1e-11          # the constants of tests/test_hip_parity.py (restated: that module needs nothing this file does)
 S_RTOL = 1e-12
 
 
 # ---- systems shared with tests/test_open_system_gpu.py ----------------------------------------------------------------------------------
-
-def collapse_list(n, c, seed):
-    """c collapse operators of spectral norm sqrt(rate): a lowering operator, a number operator, then random complex matrices."""
-    rng = np.random.default_rng(1000 + seed)
-    a = np.diag(np.sqrt(np.arange(1, n)), 1).astype(complex)
-    pool = [a, a.conj().T @ a]
-    while len(pool) < c:
-        pool.append(rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n)))
-    rates = [0.30, 0.20, 0.15, 0.10, 0.12, 0.08, 0.05, 0.04]
-    return [math.sqrt(rates[j]) * pool[j] / np.linalg.norm(pool[j], 2) for j in range(c)]
-
 
 def open_case(n, k, m, steps, taylor, c, seed, state_transfer=False, reg_coeffs=None, dt=0.4, **kw):
     """(OracleSystem, collapse operators): generators of norm 1 (drift) and 1/2 (controls), amplitudes up to 1 + k / 4."""

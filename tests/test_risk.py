@@ -1,4 +1,4 @@
-"""Risk-sensitive robust GRAPE without a GPU: the NumPy statement of the soft worst case (tests/risk_reference.py) against an extended-precision
+"""Risk-sensitive robust GRAPE without a GPU: the NumPy statement of the soft worst case (tests/composed_reference.py) against an extended-precision
 restatement and against central differences, the composed ensemble's gradient against central differences of its own value, the `risk` key of
 helper_functions/robust.py, and the routing of the risk through HipEngine and Grape with the library replaced by a recorder."""
 import numpy as np
@@ -7,7 +7,8 @@ import pytest
 from oracle import grape_oracle as go
 from quantum_optimal_control.core import hip_engine
 from quantum_optimal_control.helper_functions import robust as rb
-from tests.risk_reference import composed_risk, soft_worst_case
+from tests.composed_reference import soft_worst_case
+from tests.robust_reference import composed
 from tests.test_robust_gpu import ensemble, member_systems, problem
 
 BETAS = [1e-9, 1e-3, 1.0, 200.0, 1e6]
@@ -82,7 +83,7 @@ def test_tilted_weights_are_the_derivative_of_the_value(beta, E):
 
 
 def test_composed_gradient_is_the_derivative_of_the_composed_value():
-    """problem('state', 'pulse'), E = 3, beta = 200, six elements of `base`, central differences of step h = 1e-6 of composed_risk's own reg_loss.
+    """problem('state', 'pulse'), E = 3, beta = 200, six elements of `base`, central differences of step h = 1e-6 of the composed ensemble's own reg_loss.
 
     The admissible error is derived, not fitted.  (1) grad = sum_e pi_e grad_e with sum pi = 1 is a convex combination, and sum_e pi_e dc_e is the exact
     derivative of J; so grad misses it by at most max_e err_e, where err_e = |grad_e - central difference of member e's own reg_loss| is the existing
@@ -95,14 +96,14 @@ def test_composed_gradient_is_the_derivative_of_the_composed_value():
     sps = member_systems(c, ens, c['Taylor_terms'])
     w, beta, h = ens['weights'], 200.0, 1e-6
     base = sps[0].base0.copy()
-    r0 = composed_risk(sps, w, beta, base)
+    r0 = composed(sps, w, base, beta=beta)
     assert np.max(np.abs(r0['pi'] - w)) >= 0.02
     rng = np.random.default_rng(0)
     for _ in range(6):
         j, t = int(rng.integers(base.shape[0])), int(rng.integers(base.shape[1]))
         d = np.zeros_like(base)
         d[j, t] = h
-        up, dn = composed_risk(sps, w, beta, base + d), composed_risk(sps, w, beta, base - d)
+        up, dn = composed(sps, w, base + d, beta=beta), composed(sps, w, base - d, beta=beta)
         fd = (up['reg_loss'] - dn['reg_loss']) / (2 * h)
         cu = np.array([m['reg_loss'] for m in up['members']])
         cd = np.array([m['reg_loss'] for m in dn['members']])

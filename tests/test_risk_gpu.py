@@ -1,5 +1,5 @@
 """Risk-sensitive robust GRAPE on the GPU (qoc_set_risk, k_ens_tilt, DESIGN.md 6b'): an ensemble engine with a risk against the soft worst case
-composed from the unchanged oracle (tests/risk_reference.py) on every path that hosts ensembles, with the exact gradient and behind a response
+composed from the unchanged oracle (tests/robust_reference.py) on every path that hosts ensembles, with the exact gradient and behind a response
 matrix; bit identity of risk 0 with no risk, of two evaluations, of a one-member ensemble; the large-beta limit; beta changed on a live engine; the
 device Adam and L-BFGS loops; the refusals of the two entry points; and the capability through Grape(robust=ensemble_grid(..., risk=...))."""
 import contextlib
@@ -18,7 +18,8 @@ from quantum_optimal_control.helper_functions import robust as rb
 from quantum_optimal_control.helper_functions import transfer as tf
 from tests import exact_gradient_reference as xr
 from tests import lbfgs_reference as ref
-from tests.risk_reference import composed_risk, composed_risk_shaped
+from tests.composed_reference import run_adam
+from tests.robust_reference import composed, composed_shaped
 from tests.test_hip_parity import G_RTOL, S_RTOL
 from tests.test_robust_gpu import bases_for, ensemble, make_engine, member_systems, nominal_system, problem
 
@@ -48,7 +49,7 @@ def row(kind, regs, E, q):
 def reference(kind, regs, E, q, beta=BETA, exact=False):
     """The composed oracle of a row at its three bases: computed once, shared by every path.  Asserts the row's condition here, before any engine."""
     _, ens, nominal, sps = row(kind, regs, E, q)
-    out = [composed_risk(sps, ens['weights'], beta, b, evaluate=xr.evaluate if exact else go.evaluate) for b in bases_for(nominal, 3)]
+    out = [composed(sps, ens['weights'], b, beta=beta, evaluate=xr.evaluate if exact else go.evaluate) for b in bases_for(nominal, 3)]
     if beta == BETA:
         for o in out:
             tilt = float(np.max(np.abs(o['pi'] - ens['weights'])))
@@ -118,7 +119,7 @@ def shaped_reference(resp):
     T = tf.hold(nominal.steps, 10).matrix if resp == 'hold10' else tg.response('dense5', nominal.steps, nominal.total_time)
     th = tg.thetas(nominal.k, T.shape[1], 3)
     _, pulse_rc = tg.split_regs(c['reg_coeffs'])
-    out = [composed_risk_shaped(sps, w, BETA, T, th[g], pulse_rc, nominal.total_time) for g in range(3)]
+    out = [composed_shaped(sps, w, T, th[g], pulse_rc, nominal.total_time, beta=BETA) for g in range(3)]
     for o in out:
         tilt = float(np.max(np.abs(o['pi'] - w)))
         print('shaped %s: largest |pi - w| %.3f' % (resp, tilt))
@@ -270,15 +271,8 @@ def test_set_risk_between_evaluations():
 # ---- 5. loops ---------------------------------------------------------------------------------------------------------------------------------
 
 def python_loop(sps, w, beta, base, conv):
-    """tests/test_robust_gpu.py python_loop over composed_risk: go.Adam, run_adam's stop rule and learning-rate schedule."""
-    opt, it, hist = go.Adam(base.shape), 0, []
-    while True:
-        r = composed_risk(sps, w, beta, base)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-        if r['loss'] < conv['conv_target'] or r['grad_squared'] < conv['min_grad'] or it >= conv['max_iterations']:
-            return dict(base=base, iterations=it, history=np.array(hist), r=r)
-        it += 1
-        base = opt.step(base, r['grad'], conv['rate'] * np.exp(-float(it) / conv['learning_rate_decay']))
+    """tests/test_robust_gpu.py python_loop over the composed risk ensemble: go.Adam, run_adam's stop rule and learning-rate schedule."""
+    return run_adam(lambda b: composed(sps, w, b, beta=beta), base, conv)
 
 
 def choose_target(hists, max_it):
@@ -322,9 +316,9 @@ def test_adam_loop_matches_the_composed_oracle():
         for g, rf in enumerate(refs):
             assert its[g] == rf['iterations'], (its, stops)
             assert np.max(np.abs(base[g] - rf['base'])) < 1e-9, np.max(np.abs(base[g] - rf['base']))
-            assert abs(s['loss'][g] - rf['r']['loss']) < 1e-10 * max(1.0, abs(rf['r']['loss']))
-            assert abs(s['reg_loss'][g] - rf['r']['reg_loss']) < 1e-10 * max(1.0, abs(rf['r']['reg_loss']))
-            assert np.max(np.abs(pi[g] - rf['r']['pi'])) < 1e-6            # (beta times the bases' 1e-9 times the members' gradients)
+            assert abs(s['loss'][g] - rf['last']['loss']) < 1e-10 * max(1.0, abs(rf['last']['loss']))
+            assert abs(s['reg_loss'][g] - rf['last']['reg_loss']) < 1e-10 * max(1.0, abs(rf['last']['reg_loss']))
+            assert np.max(np.abs(pi[g] - rf['last']['pi'])) < 1e-6            # (beta times the bases' 1e-9 times the members' gradients)
     finally:
         eng.close()
 
@@ -345,7 +339,7 @@ def test_a_finished_control_set_keeps_its_weights():
             seen.append((s['done'].copy(), eng.member_weights(), s['loss'].copy()))
         done_at = next(i for i, (d, _, _) in enumerate(seen) if d[first])
         assert done_at == stops[first], (done_at, stops)
-        o = composed_risk(sps, ens['weights'], BETA, eng.get_base()[first])        # (a stopped set is not moved: evaluated where it stands)
+        o = composed(sps, ens['weights'], eng.get_base()[first], beta=BETA)        # (a stopped set is not moved: evaluated where it stands)
         assert np.max(np.abs(seen[done_at][1][first] - o['pi'])) <= S_RTOL
         for d, pi, loss in seen[done_at + 1:]:
             assert d[first] and np.array_equal(pi[first], seen[done_at][1][first]) and loss[first] == seen[done_at][2][first]
@@ -356,14 +350,14 @@ def test_a_finished_control_set_keeps_its_weights():
 
 
 def test_lbfgs_steps_follow_the_reference_on_the_composed_oracle():
-    """tests/test_lbfgs_gpu.py's "oracle as evaluator" row with composed_risk as the evaluator: branches, points (LOOP_ATOL) and values."""
+    """tests/test_lbfgs_gpu.py's "oracle as evaluator" row with the composed risk ensemble as the evaluator: branches, points (LOOP_ATOL) and values."""
     from tests import test_lbfgs_gpu as lg
     c = problem('unitary', 'none')
     ens, nominal = ensemble(c, 3, 1), nominal_system(c)
     sps = member_systems(c, ens, (nominal.exp_terms, nominal.scaling))
     eng = make_engine(nominal, 1, with_risk(ens, BETA))
     try:
-        lg.compare_with_reference(eng, lambda x: composed_risk(sps, ens['weights'], BETA, x), nominal.base0, dict(lg.BASE), 6, 'risk', with_f=True)
+        lg.compare_with_reference(eng, lambda x: composed(sps, ens['weights'], x, beta=BETA), nominal.base0, dict(lg.BASE), 6, 'risk', with_f=True)
     finally:
         eng.close()
 

@@ -484,7 +484,7 @@ def test_loop_against_the_composed_oracle(r, rate, spread):
             print('  group %d base: %.3e' % (g, np.max(np.abs(base[g] - ref['base']))))
             assert np.max(np.abs(base[g] - ref['base'])) < STEP_ATOL, (g, np.max(np.abs(base[g] - ref['base'])))
             for key in ('loss', 'reg_loss', 'grad_squared', 'unitary_scale'):
-                assert abs(s[key][g] - ref['r'][key]) < 1e-10 * max(1.0, abs(ref['r'][key])), (key, g, s[key][g], ref['r'][key])
+                assert abs(s[key][g] - ref['last'][key]) < 1e-10 * max(1.0, abs(ref['last'][key])), (key, g, s[key][g], ref['last'][key])
         ms = eng.member_scalars()
         Uf = eng.get_final_unitary() if unitary else None
         for g in range(G):
@@ -650,7 +650,7 @@ def grape_reference(c, ens, restarts, unitary_error=1e-4):
     conv = dict(rate=GRAPE_CONV['rate'], learning_rate_decay=GRAPE_CONV['learning_rate_decay'], conv_target=GRAPE_CONV['conv_target'], min_grad=1e-25,
                 max_iterations=GRAPE_CONV['max_iterations'])
     runs = [python_loop(sps, ens['weights'], b, conv) for b in bases]
-    best = int(np.argmin([run['r']['loss'] for run in runs]))
+    best = int(np.argmin([run['last']['loss'] for run in runs]))
     return sps, runs, best, taylor
 
 
@@ -664,7 +664,7 @@ def test_grape_robust_restarts_returns_the_winning_seed_of_the_composed_oracle()
     c = grape_problem()
     ens = ensemble(c, 4, 1)
     sps, runs, best, taylor = grape_reference(c, ens, 3)
-    losses = sorted(run['r']['loss'] for run in runs)
+    losses = sorted(run['last']['loss'] for run in runs)
     assert losses[1] - losses[0] > 1e-6, losses                        # the winner is not decided by round-off
     np.random.seed(c['np_seed'])
     out = io.StringIO()

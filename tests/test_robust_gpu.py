@@ -10,12 +10,12 @@ import sys
 import numpy as np
 import pytest
 
-from oracle import grape_oracle as go
 from quantum_optimal_control.core import hip_engine
 from quantum_optimal_control.helper_functions import robust as rb
 from quantum_optimal_control.helper_functions.synthetic_systems import herm
+from tests.composed_reference import run_adam
 from tests.golden import cases
-from tests.helpers import resolve_dressed
+from tests.robust_reference import composed, member_systems, nominal_system          # noqa: F401  (also imported from here by other tests)
 from tests.test_adam_tail import _choose_target
 
 pytestmark = pytest.mark.gpu
@@ -60,33 +60,6 @@ def ensemble(c, E, q, seed=5):
     if E == 1:
         off, amp, w = np.zeros((1, q)), np.ones((1, k)), np.ones(1)
     return rb.validate(dict(operators=ops, offsets=off, amp_scales=amp, weights=w), n, k)
-
-
-def member_systems(c, ens, taylor):
-    """go.OracleSystem of every member (the unchanged oracle), with the engine's (T, s)."""
-    out = []
-    for e in range(len(ens['weights'])):
-        H0e, Hopse = rb.member_hamiltonians(c['H0'], c['Hops'], ens, e)
-        np.random.seed(c['np_seed'])
-        out.append(go.OracleSystem(H0e, Hopse, c['U'], c['total_time'], c['steps'], c['states_concerned_list'], U0=c['U0'],
-                                   reg_coeffs=c['reg_coeffs'], dressed_info=resolve_dressed(c), maxA=c['maxA'],
-                                   state_transfer=c['state_transfer'], Taylor_terms=taylor))
-    return out
-
-
-def nominal_system(c):
-    """The problem without perturbations: what the engine is given beside the ensemble."""
-    return member_systems(c, dict(operators=[], offsets=np.zeros((1, 0)), amp_scales=np.ones((1, len(c['Hops']))), weights=np.ones(1)),
-                          c['Taylor_terms'])[0]
-
-
-def composed(sps, w, base, want_inter=False):
-    """The ensemble's expected values at `base` (k x steps) from the members' oracle evaluations (`members`: the evaluations themselves)."""
-    rs = [go.evaluate(sp, base, want_inter=want_inter) for sp in sps]
-    grad = sum(wi * r['grad'] for wi, r in zip(w, rs))
-    return dict(loss=sum(wi * r['loss'] for wi, r in zip(w, rs)), reg_loss=sum(wi * r['reg_loss'] for wi, r in zip(w, rs)),
-                unitary_scale=sum(wi * r['unitary_scale'] for wi, r in zip(w, rs)), grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)),
-                member_loss=np.array([r['loss'] for r in rs]), U0=rs[0]['U_final'] if not sps[0].state_transfer else None, members=rs)
 
 
 def make_engine(sp, G, ens, path=P.PATH_AUTO, variant=0, chunks=0, plan_seeds=0):
@@ -191,14 +164,7 @@ def test_one_nominal_member_is_bit_identical_to_the_plain_engine(path, variant, 
 
 def python_loop(sps, w, base, conv):
     """run_session.start_adam_optimizer over the composed ensemble: go.Adam, run_adam's stop rule and learning-rate schedule."""
-    opt, it, hist = go.Adam(base.shape), 0, []
-    while True:
-        r = composed(sps, w, base)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-        if r['loss'] < conv['conv_target'] or r['grad_squared'] < conv['min_grad'] or it >= conv['max_iterations']:
-            return dict(base=base, iterations=it, history=np.array(hist), r=r)
-        it += 1
-        base = opt.step(base, r['grad'], conv['rate'] * np.exp(-float(it) / conv['learning_rate_decay']))
+    return run_adam(lambda b: composed(sps, w, b), base, conv)
 
 
 @pytest.mark.parametrize('kind,regs,path', [('unitary', 'pulse', P.PATH_AUTO), ('unitary', 'state', P.PATH_GEMM),
@@ -224,8 +190,8 @@ def test_adam_loop_matches_the_composed_oracle(kind, regs, path):
         for g, ref in enumerate(refs):
             assert its[g] == ref['iterations'], (its, stops)
             assert np.max(np.abs(base[g] - ref['base'])) < 1e-9, np.max(np.abs(base[g] - ref['base']))
-            assert abs(s['loss'][g] - ref['r']['loss']) < 1e-10 * max(1.0, abs(ref['r']['loss']))
-            assert abs(s['reg_loss'][g] - ref['r']['reg_loss']) < 1e-10 * max(1.0, abs(ref['r']['reg_loss']))
+            assert abs(s['loss'][g] - ref['last']['loss']) < 1e-10 * max(1.0, abs(ref['last']['loss']))
+            assert abs(s['reg_loss'][g] - ref['last']['reg_loss']) < 1e-10 * max(1.0, abs(ref['last']['reg_loss']))
     finally:
         eng.close()
 

@@ -11,15 +11,15 @@ import io
 import os
 import subprocess
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from oracle import grape_oracle as go
 from quantum_optimal_control.core import hip_engine
 from quantum_optimal_control.helper_functions import transfer as tf
+from tests.composed_reference import run_adam, split_regs
 from tests.golden import cases
+from tests.robust_reference import composed_shaped
 from tests.test_adam_tail import _choose_target
 from tests.test_robust_gpu import STATE_PATHS, UNITARY_PATHS, bases_for, ensemble, member_systems, nominal_system, problem
 
@@ -29,7 +29,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U_ATOL, G_RTOL, S_RTOL = 1e-12, 1e-11, 1e-12          # tests/test_hip_parity.py
 P = hip_engine
 PULSE_REGS = dict(amplitude=0.01, dwdt=0.001, d2wdt2=1e-5, bandpass=0.01, band=[0.5, 5.0])     # (no envelope: it is defined per time slice)
-PULSE_KEYS = ('amplitude', 'dwdt', 'd2wdt2', 'bandpass', 'band')
 
 
 # ---- problems, responses, the composed oracle -------------------------------------------------------------------------------------------
@@ -64,27 +63,6 @@ def thetas(k, Pn, G):
     return rng.normal(0.0, 0.7, size=(3, k, Pn))[:G]
 
 
-def split_regs(rc):
-    """(state regularisers, pulse regularisers) of a reg_coeffs dict."""
-    return {key: v for key, v in rc.items() if key not in PULSE_KEYS}, {key: v for key, v in rc.items() if key in PULSE_KEYS}
-
-
-def composed(sps, w, T, theta, pulse_rc, total_time):
-    """Expected values at the variable theta (k x P) from the unchanged oracle: sps are the members' systems with the state regularisers only."""
-    k, Pn = theta.shape
-    ws = np.sin(theta)
-    wf = ws @ T.T
-    rs = [go.evaluate(sp, np.arcsin(wf)) for sp in sps]
-    view = SimpleNamespace(reg_coeffs=pulse_rc, steps=Pn, dt=total_time / Pn, k=k, total_time=total_time, use_gpu=True, one_minus_gauss=None)
-    val, dR = go.pulse_regularisers(view, ws)
-    maxA = sps[0].maxA
-    dLdu = sum(wi * r['dL_du'] for wi, r in zip(w, rs))
-    grad = np.cos(theta) * (maxA[:, None] * (dLdu @ T) + dR)
-    return dict(loss=sum(wi * r['loss'] for wi, r in zip(w, rs)), reg_loss=sum(wi * r['reg_loss'] for wi, r in zip(w, rs)) + val,
-                unitary_scale=sum(wi * r['unitary_scale'] for wi, r in zip(w, rs)), grad=grad, grad_squared=0.5 * float(np.sum(grad * grad)),
-                pulse=maxA[:, None] * wf, U0=rs[0]['U_final'] if not sps[0].state_transfer else None)
-
-
 def systems(c, ens):
     """(nominal system as the engine gets it, member systems with the state regularisers only, weights)."""
     nominal = nominal_system(c)
@@ -104,7 +82,7 @@ def reference(kind, regs, resp, Eq):
     T = response(resp, nominal.steps, nominal.total_time)
     th = thetas(nominal.k, T.shape[1], 3)
     _, pulse_rc = split_regs(c['reg_coeffs'])
-    return [composed(sps, w, T, th[g], pulse_rc, nominal.total_time) for g in range(3)]
+    return [composed_shaped(sps, w, T, th[g], pulse_rc, nominal.total_time) for g in range(3)]
 
 
 def make_engine(sp, G, T, ens=None, path=P.PATH_AUTO, variant=0, chunks=0, reg_coeffs=None):
@@ -195,7 +173,7 @@ def _split_case():
     T = T / np.maximum(1.0, np.sum(np.abs(T), axis=1))[:, None]
     _, pulse_rc = split_regs(c['reg_coeffs'])
     th = thetas(nominal.k, 2100, 1)
-    return c, T, [composed(sps, w, T, th[0], pulse_rc, nominal.total_time)]
+    return c, T, [composed_shaped(sps, w, T, th[0], pulse_rc, nominal.total_time)]
 
 
 @pytest.mark.parametrize('path', [P.PATH_AUTO, P.PATH_MFMA, P.PATH_GEMM])
@@ -238,14 +216,7 @@ def test_identity_response_is_bit_identical_to_the_plain_engine(path, variant, r
 
 def python_loop(sps, w, T, theta, pulse_rc, total_time, conv):
     """run_session.start_adam_optimizer over the composed oracle: go.Adam, run_adam's stop rule and learning-rate schedule."""
-    opt, it, hist = go.Adam(theta.shape), 0, []
-    while True:
-        r = composed(sps, w, T, theta, pulse_rc, total_time)
-        hist.append((r['loss'], r['reg_loss'], r['grad_squared']))
-        if r['loss'] < conv['conv_target'] or r['grad_squared'] < conv['min_grad'] or it >= conv['max_iterations']:
-            return dict(base=theta, iterations=it, history=np.array(hist), r=r)
-        it += 1
-        theta = opt.step(theta, r['grad'], conv['rate'] * np.exp(-float(it) / conv['learning_rate_decay']))
+    return run_adam(lambda th: composed_shaped(sps, w, T, th, pulse_rc, total_time), theta, conv)
 
 
 @pytest.mark.parametrize('kind,regs,resp,path', [('unitary', 'pulse', 'hold7', P.PATH_AUTO), ('state', 'none', 'gauss13', P.PATH_AUTO)])
@@ -272,8 +243,8 @@ def test_adam_loop_matches_the_composed_oracle(kind, regs, resp, path):
             assert its[g] == ref['iterations'], (its, stops)
             print('set %d: base error %.3e' % (g, np.max(np.abs(base[g] - ref['base']))))
             assert np.max(np.abs(base[g] - ref['base'])) < 1e-9, np.max(np.abs(base[g] - ref['base']))
-            assert abs(s['loss'][g] - ref['r']['loss']) < 1e-10 * max(1.0, abs(ref['r']['loss']))
-            assert abs(s['reg_loss'][g] - ref['r']['reg_loss']) < 1e-10 * max(1.0, abs(ref['r']['reg_loss']))
+            assert abs(s['loss'][g] - ref['last']['loss']) < 1e-10 * max(1.0, abs(ref['last']['loss']))
+            assert abs(s['reg_loss'][g] - ref['last']['reg_loss']) < 1e-10 * max(1.0, abs(ref['last']['reg_loss']))
     finally:
         eng.close()
 
