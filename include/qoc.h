@@ -46,6 +46,8 @@ extern "C" {
 
 #define QOC_PATH_SPARSE 7      /* engines made by qoc_create_sparse only: state transfer on sparse operators, any n; ELLPACK mat-vecs, the state vector of a
                                 * (control set, column) resident in the LDS of one compute unit up to n = 5088, in global scratch above (csrc/qoc_sparse.h) */
+#define QOC_PATH_LINDBLAD_TILED 8 /* engines made by qoc_create_open* only, and only by name (AUTO stays QOC_PATH_LINDBLAD): n <= 128, any n_collapse <= 8; the
+                                * operators in per-workgroup global scratch, n x n products on v_mfma_f64_16x16x4 tiles (csrc/qoc_lindblad_tiled.h) */
 
 typedef struct qoc_engine* qoc_handle;
 
@@ -287,7 +289,10 @@ int qoc_create_fleet(const qoc_config* cfg, const qoc_ensemble* ens, const qoc_f
  * Accepted: n_collapse = 0 (the closed limit), cfg.path AUTO or QOC_PATH_LINDBLAD, both modes, any n_seeds.  QOC_ERR_INVALID, before any device is
  * touched: forbidden levels, speed_up, forbid_dressed; gradient = 1; time_shards > 0; any other explicit path; n > 32, n_collapse > 8, m > n or
  * (n_collapse + 4) n (n | 1) 16 bytes > 159 KiB of LDS; taylor_terms < 1 or > 60; scaling > 12.  qoc_get_final_unitary, qoc_get_inter_vecs and the
- * member and pulse read-backs return QOC_ERR_STATE on such an engine; the two read-backs below return it on every other engine. */
+ * member and pulse read-backs return QOC_ERR_STATE on such an engine; the two read-backs below return it on every other engine.
+ * cfg.path = QOC_PATH_LINDBLAD_TILED (this entry point and the two below; never chosen by AUTO) lifts the size limits to 1 <= n <= 128 with any
+ * n_collapse <= 8 and no LDS rule: the same mathematics on 16 x 16 tiles in global scratch, 5 NP^2 16 bytes per (control set, pair), NP = 16 ceil(n / 16);
+ * QOC_ERR_NOMEM when that scratch cannot be allocated.  Everything else above holds as it stands. */
 typedef struct qoc_open {
     int32_t n_collapse;         /* c >= 0 */
     const double* C;            /* [c][n][n] complex: sqrt(dt) C_j; NULL when c = 0 */

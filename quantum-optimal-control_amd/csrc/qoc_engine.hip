@@ -31,6 +31,7 @@
 #include "qoc_control_map.h"
 #include "qoc_exact_grad.h"
 #include "qoc_lindblad.h"
+#include "qoc_lindblad_tiled.h"
 #include "qoc_sparse.h"
 #include "qoc_sparse_host.h"
 #include "qoc_lbfgs.h"
@@ -120,6 +121,8 @@ struct qoc_engine {
     QocExact xg{};
     // open-system GRAPE (qoc_create_open, csrc/qoc_lindblad.h): density operators of the pairs of states of interest under a Lindblad master equation
     QocLb lb{};
+    // the same past the LDS rule (QOC_PATH_LINDBLAD_TILED, csrc/qoc_lindblad_tiled.h): the operators in global scratch, the products on the matrix pipe
+    QocLbt lbt{};
     // sparse state transfer (qoc_create_sparse, csrc/qoc_sparse.h): ELLPACK operators, no n x n array anywhere (d.Hs, d.U0 and d.Xfinal stay null)
     QocSparse sp{};
     std::vector<int> sp_widths;     // [k+1] W_j, for qoc_plan_describe
@@ -392,6 +395,11 @@ static int enqueue_trajectories(qoc_engine* e, const QocDev& d, const QocAdamDev
         qoc_lb_forward(e->lb, d, e->stream);
         TRY(prof_end(e));
         qoc_lb_backward(e->lb, d, e->stream);
+    } else if (e->path == QOC_PATH_LINDBLAD_TILED) {                    // the same on tiles in global scratch (csrc/qoc_lindblad_tiled.h)
+        TRY(prof_begin(e));
+        qoc_lbt_forward(e->lb, e->lbt, d, e->stream);
+        TRY(prof_end(e));
+        qoc_lbt_backward(e->lb, e->lbt, d, e->stream);
     } else if (e->path == QOC_PATH_SPARSE) {                            // sparse state transfer: forward, loss, costates + gradient (csrc/qoc_sparse.h)
         TRY(prof_begin(e));
         qoc_sp_forward(e->sp, d, e->stream);
@@ -1160,6 +1168,32 @@ static int setup_lindblad(qoc_engine* e, const Problem& p, const DecayHost* op) 
         TRY(dev_alloc(e, &L.cost_partial, B * L.R));
         TRY(dev_alloc(e, &L.expct, B * (d.steps + 1) * nc * d.m));
     }
+    if (e->path == QOC_PATH_LINDBLAD_TILED) {
+        // the tiled kernels: no LDS to reserve; the table of D_j padded to NP x NP and scaled per row (lb_setup's product), the workgroups' scratch
+        QocLbt& W = e->lbt;
+        const int NP = qoc_lbt_np(n);
+        const size_t mat = (size_t)NP * NP;
+        W.on = 1; W.NP = NP; W.work_bytes = B * L.R * QOC_LBT_MATS * mat * sizeof(cplx);
+        L.S = NP; L.lds_bytes = 0;
+        if (c > 0) {
+            std::vector<double> dp(2 * mat * (size_t)c * rows, 0.0);
+            for (int row = 0; row < rows; ++row)
+                for (int j = 0; j < c; ++j) {
+                    const double sc = op->scales ? rs[(size_t)row * c + j] : 1.0;
+                    const double* D = op->C + 2 * nn * (size_t)j;
+                    double* o = dp.data() + 2 * mat * ((size_t)row * c + j);
+                    for (int a = 0; a < n; ++a)
+                        for (int b = 0; b < n; ++b) {
+                            // (no table: D_j as it came, nothing scaled)
+                            o[2 * ((size_t)a * NP + b)] = op->scales ? D[2 * (a * n + b)] * sc : D[2 * (a * n + b)];
+                            o[2 * ((size_t)a * NP + b) + 1] = op->scales ? D[2 * (a * n + b) + 1] * sc : D[2 * (a * n + b) + 1];
+                        }
+                }
+            TRY(dev_upload(e, &W.Dp, (const cplx*)dp.data(), mat * c * rows));
+        }
+        TRY(dev_alloc(e, &W.work, B * L.R * QOC_LBT_MATS * mat));
+        return QOC_OK;
+    }
     HIP_TRY_MSG(qoc_lb_lds_opt_in(L), "%s: cannot reserve %zu bytes of LDS for the open-system kernels", op->who, L.lds_bytes);
     return QOC_OK;
 }
@@ -1239,7 +1273,8 @@ static int create_engine(const qoc_config* cfg, const Problem& p, const EnsArgs*
     AutoPlan plan{};
     // (an open engine has been through build_trajectory_view like every engine: d.inter, d.Xfinal, d.ztau and zfin are allocated there and never
     // touched by the open path -- (steps + 1) n m + n^2 numbers per control set, small beside its history; left so as not to fork that helper)
-    if (open) plan.path = QOC_PATH_LINDBLAD;                     // (one home, as the exact gradient has: no table to consult)
+    // (AUTO is the LDS path, as it was: no table to consult, and no crossover measured; the tiled path is taken by name)
+    if (open) plan.path = cfg->path == QOC_PATH_LINDBLAD_TILED ? QOC_PATH_LINDBLAD_TILED : QOC_PATH_LINDBLAD;
     else if (p.sparse) plan.path = QOC_PATH_SPARSE;
     else TRY(choose_path(*cfg, d, antiherm, ens != nullptr, plan));
     e->path = plan.path; e->chunks = 1;
@@ -1306,13 +1341,16 @@ static int check_open(const char* who, const qoc_config* cfg, int c, const doubl
     if (cfg->forbid_dressed) return fail(QOC_ERR_INVALID, "%s: forbid_dressed is not available under a master equation", who);
     if (cfg->gradient != 0) return fail(QOC_ERR_INVALID, "%s: the exact gradient is not available under a master equation (gradient = %d)", who, cfg->gradient);
     if (cfg->time_shards > 0) return fail(QOC_ERR_INVALID, "%s: an open system cannot be time-sharded (time_shards = %d)", who, cfg->time_shards);
-    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_LINDBLAD)
+    const bool tiled = cfg->path == QOC_PATH_LINDBLAD_TILED;     // (taken by name only: 1 .. 128 levels, no LDS rule)
+    if (cfg->path != QOC_PATH_AUTO && cfg->path != QOC_PATH_LINDBLAD && !tiled)
         return fail(QOC_ERR_INVALID, "%s: an open system runs on QOC_PATH_LINDBLAD (or AUTO), not on path %d", who, cfg->path);
     if (c < 0 || (c > 0 && !C)) return fail(QOC_ERR_INVALID, "%s: n_collapse = %d (>= 0) with its operators", who, c);
-    if (n < 1 || n > QOC_LB_MAX_N) return fail(QOC_ERR_INVALID, "%s: n = %d (1 .. %d levels)", who, n, QOC_LB_MAX_N);
+    if (tiled && (n < 1 || n > QOC_LBT_MAX_N))
+        return fail(QOC_ERR_INVALID, "%s: n = %d (1 .. %d levels on QOC_PATH_LINDBLAD_TILED)", who, n, QOC_LBT_MAX_N);
+    if (!tiled && (n < 1 || n > QOC_LB_MAX_N)) return fail(QOC_ERR_INVALID, "%s: n = %d (1 .. %d levels)", who, n, QOC_LB_MAX_N);
     if (c > QOC_LB_MAX_C) return fail(QOC_ERR_INVALID, "%s: n_collapse = %d (at most %d collapse operators)", who, c, QOC_LB_MAX_C);
     if (cfg->m < 1 || cfg->m > n) return fail(QOC_ERR_INVALID, "%s: m = %d states of interest (1 .. n = %d)", who, cfg->m, n);
-    if (qoc_lb_lds_bytes(n, c) > QOC_LB_LDS_LIMIT)
+    if (!tiled && qoc_lb_lds_bytes(n, c) > QOC_LB_LDS_LIMIT)
         return fail(QOC_ERR_INVALID, "%s: n = %d with %d collapse operators needs %zu bytes of LDS (limit %zu)", who, n, c, qoc_lb_lds_bytes(n, c),
                     QOC_LB_LDS_LIMIT);
     if (cfg->taylor_terms < 1 || cfg->taylor_terms > QOC_LB_MAX_T)
@@ -2060,7 +2098,7 @@ int qoc_profile_read(qoc_handle e, const char** kernel_name, int64_t* launches, 
     CHECK_H(e);
     TRY(prof_collect(e));
     if (kernel_name)
-        *kernel_name = e->path == QOC_PATH_SPARSE ? "k_sp_forward" : e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
+        *kernel_name = e->path == QOC_PATH_SPARSE ? "k_sp_forward" : e->path == QOC_PATH_LINDBLAD ? "k_lb_forward" : e->path == QOC_PATH_LINDBLAD_TILED ? "k_lbt_forward" : e->path == QOC_PATH_SMALL ? "k_small_iter (whole iterations)"
                        : e->path == QOC_PATH_GEMM ? (e->gm.route == QOC_GEMM_DIRECT ? "k_gemm_taylor_chain (backward chain + sources + gradient products)"
                            : e->gm.N <= 64 ? "k_gemm_expm_fused (+ product tree)" : "k_zgemm_wg + k_zgemm32 (batched matexp sequence)")
                        : e->path == QOC_PATH_MFMA ? e->mp.expm_name             // (the kernel of the exponentials, by its variant)
@@ -2093,6 +2131,7 @@ int qoc_chunks_in_use(qoc_handle e) { return e ? e->chunks : QOC_ERR_INVALID; }
 //   GEMM path:  path=gemm route=<unitary|propagator|direct> chunks=<NC> slices_per_chunk=<S> chains=<persistent|launches>
 //   others:     path=generic | path=st_fused
 //   open engines (qoc_create_open, qoc_create_open_fleet): path=lindblad collapse=<c> pairs=<R> lds=<bytes of dynamic LDS>
+//   the same with cfg.path = QOC_PATH_LINDBLAD_TILED: path=lindblad_tiled collapse=<c> pairs=<R> np=<NP> work=<bytes of the workgroups' scratch>
 //   (qoc_create_open_costs with n_obs > 0 ends the line with running_costs=<L>)
 //   sparse engines (qoc_create_sparse): path=sparse nnz=<stored entries> ell=<W_0,..,W_k> vector_home=<lds|global> lds=<bytes of dynamic LDS> threads=<256|1024 of a sweep>
 //   grad_grid=<workgroups of k_sp_grad>; engines of qoc_create_sparse_fleet add rows=<per_operator|merged> merged_width=<Wm, 0 per operator>
@@ -2121,6 +2160,8 @@ int qoc_plan_describe(qoc_handle e, char* buf, int32_t len) {
                              : "butterfly");
     } else if (e->path == QOC_PATH_LINDBLAD) {
         snprintf(tmp, sizeof tmp, "path=lindblad collapse=%d pairs=%d lds=%zu", e->lb.c, e->lb.R, e->lb.lds_bytes);
+    } else if (e->path == QOC_PATH_LINDBLAD_TILED) {
+        snprintf(tmp, sizeof tmp, "path=lindblad_tiled collapse=%d pairs=%d np=%d work=%zu", e->lb.c, e->lb.R, e->lbt.NP, e->lbt.work_bytes);
     } else if (e->path == QOC_PATH_SPARSE) {
         const QocSparse& sp = e->sp;
         int w = snprintf(tmp, sizeof tmp, "path=sparse nnz=%lld ell=", sp.stored);

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get('QOC_HIP_LIBRARY') or os.path.normpath(os.path.join(_H
 PATH_AUTO, PATH_GENERIC, PATH_MFMA, PATH_ST_FUSED, PATH_GEMM, PATH_SMALL = 0, 1, 2, 3, 4, 5
 PATH_LINDBLAD = 6          # open engines only (HipEngine(collapse_ops=...))
 PATH_SPARSE = 7            # sparse engines only (HipEngine(sparse_ops=...))
+PATH_LINDBLAD_TILED = 8    # open engines past PATH_LINDBLAD's size rule, up to 128 levels (helper_functions/open_system.choose_path)
 
 
 class QocConfig(C.Structure):
@@ -574,7 +575,9 @@ class HipEngine(object):
     rates (helper_functions/open_system.py builds the usual ones; an empty list is the closed limit).  The engine then propagates the operators
     psi_i psi_j^dagger of the states of interest under the Lindblad master equation, with degree taylor_terms and 2^scaling sub-steps per slice in
     both modes; loss, gradient and the optimiser entry points keep their shapes, get_final_density() and get_populations() take the place of
-    get_final_unitary() and get_inter_vecs().
+    get_final_unitary() and get_inter_vecs().  Given path=PATH_AUTO, an open engine (this keyword, or decay carried by ensemble or fleet) runs on
+    PATH_LINDBLAD where its size rule holds (n <= 32 within 159 KiB of LDS) and on PATH_LINDBLAD_TILED up to n = 128
+    (helper_functions/open_system.choose_path); an explicit path= is passed through.
 
     sparse_ops (sparse state transfer, include/qoc.h qoc_create_sparse): a list of k + 1 scipy.sparse matrices -i dt H0, -i dt H_1 .. in place of Hs
     (pass Hs=None, U0=None).  State transfer only, on path AUTO or PATH_SPARSE; the engine keeps every operator in ELLPACK and never forms an n x n
@@ -663,6 +666,11 @@ class HipEngine(object):
                 raise ValueError("HipEngine: running_costs need an open engine (collapse_ops=, or decay carried by ensemble or fleet); closed engines take "
                                  "reg_coeffs['forbidden_coeff_list']")
             running_costs = open_system.validate_costs(running_costs, np.shape(Hs)[1])
+        if int(path) == PATH_AUTO and (collapse_ops is not None or decay is not None):
+            # an open engine: PATH_LINDBLAD wherever its size rule holds (every engine that ran before this path existed), the tiled path above.  The
+            # library's AUTO IS PATH_LINDBLAD, so where the rule holds the configuration goes over as it always did, with AUTO in it
+            if open_system.choose_path(int(np.shape(Hs)[1]), len(collapse_ops) if collapse_ops is not None else int(decay[0].shape[0])) == PATH_LINDBLAD_TILED:
+                path = PATH_LINDBLAD_TILED
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()

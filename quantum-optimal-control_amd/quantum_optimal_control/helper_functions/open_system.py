@@ -30,6 +30,24 @@ def validate(collapse_ops, n):
     return out
 
 
+# ---- where an open engine runs ------------------------------------------------------------------------------------------------------------------
+PATH_LINDBLAD, PATH_LINDBLAD_TILED = 6, 8          # include/qoc.h QOC_PATH_LINDBLAD, QOC_PATH_LINDBLAD_TILED (hip_engine has the same numbers)
+LDS_MAX_N, LDS_LIMIT, TILED_MAX_N = 32, 159 * 1024, 128
+
+
+def choose_path(n, c):
+    """The path of an open engine of n levels with c collapse operators: PATH_LINDBLAD (the operators of a pair in the LDS of one compute unit)
+    wherever its size rule holds -- n <= 32 and (c + 4) n (n | 1) 16 bytes <= 159 KiB --, else PATH_LINDBLAD_TILED (global scratch, 16 x 16 tiles
+    on the matrix pipe) up to n = 128.  ValueError above."""
+    n, c = int(n), int(c)
+    if n <= LDS_MAX_N and (c + 4) * n * (n | 1) * 16 <= LDS_LIMIT:
+        return PATH_LINDBLAD
+    if n <= TILED_MAX_N:
+        return PATH_LINDBLAD_TILED
+    raise ValueError('open-system GRAPE: n = %d levels; PATH_LINDBLAD holds up to %d levels within %d bytes of LDS, PATH_LINDBLAD_TILED up to %d levels'
+                     % (n, LDS_MAX_N, LDS_LIMIT, TILED_MAX_N))
+
+
 def _lowering(n):
     return np.diag(np.sqrt(np.arange(1, n)), 1).astype(np.complex128)
 
